@@ -11,6 +11,12 @@ tile sort -> render (forward), L1 loss against a fixed random target, render bac
 backward, and for N > 1 the exchange (sum) of the Gaussian gradients over RCCL (view-parallel,
 SURVEY.md 8(e)).  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the per-step
+hipEvent times).  `--full` adds everything else the line has carried: forward-only time, stage breakdown, roofline,
+the `geo` / `trained_geo` objects, the extra keys, the exchange object and the CPU baseline.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds
+given the same arguments can be compared output for output.
+
 `--gpus N` with no WORLD_SIZE in the environment spawns the N ranks itself as child processes BEFORE
 anything in this process touches the GPU (a process that has initialised HIP must never exec), binds
 rank r to GPU r and fails (exit code 2) when the box has fewer than N devices.  IBGS_BENCH_SHARE_GPU=1
@@ -173,6 +179,7 @@ class Workload:
     ANISOTROPY = None
     SCALE_SIGMA = 0.0
     torch_l1 = True          # the loss of every timed step is the reference's own expression (utils/loss_utils.py:23-24); the one-pass fused L1 is an extra key
+    keep_outputs = False     # --dump-outputs: every step keeps (detached) what it returned to its caller in `last`
 
     def __init__(self, cfg, view, dev, opacity, geo, forward_only, target_seed, cluster=None, anisotropy="default", scale_sigma=None):
         c = syn.CONFIGS[cfg]
@@ -226,6 +233,7 @@ class Workload:
         # geo line: L1 terms on the normal map (target 0), the median depth (0) and the warped source colours (0.5)
         self.geo_targets = (torch.zeros(3, H, W, device=dev), torch.zeros(1, H, W, device=dev), torch.full((15, H, W), 0.5, device=dev)) if geo else None
         self.R = 0
+        self.last = None
 
     def hop_to(self, view):
         """Point the (colour) workload at another orbit camera: same Gaussians, same target, new matrices."""
@@ -245,8 +253,10 @@ class Workload:
     def fwd_only(self):
         from ibgs_amd import rasterizer as _r
         with torch.no_grad():
-            self._call()
+            outs = self._call()
         self.R = _r.LAST_NUM_RENDERED
+        if self.keep_outputs:
+            self.last = {"outs": outs, "loss": None}
 
     def local_step(self, backward=None):
         """forward + loss + backward of this rank's view; `backward(loss)` lets the caller wrap autograd (gradient capture)."""
@@ -261,6 +271,8 @@ class Workload:
         if self.geo:   # every differentiable geo output takes part: normal map, median depth, warped source colours
             loss = loss + l1(outs[2], self.geo_targets[0]) + l1(outs[3], self.geo_targets[1]) + l1(outs[5], self.geo_targets[2])
         self.R = outs[0].grad_fn.num_rendered
+        if self.keep_outputs:          # detached: the autograd node (and what it holds) is released after the backward as usual
+            self.last = {"outs": tuple(o.detach() for o in outs), "loss": loss.detach()}
         if backward is None:
             loss.backward()
         else:
@@ -291,6 +303,13 @@ def fence(world):
 
 
 def measure(wl, step, steps, warmup, world, n_stage_steps=3, n_fwd=10):
+    """timed_steps + untimed_breakdown: the headline's timing and what `--full` reports beside it."""
+    m = timed_steps(wl, step, steps, warmup, world)
+    m.update(untimed_breakdown(wl, step, world, n_stage_steps, n_fwd))
+    return m
+
+
+def timed_steps(wl, step, steps, warmup, world):
     """W untimed warm-ups, then EXACTLY K steps between barrier + synchronize on both sides (wall clock, max over ranks);
     every timed step is also bracketed by hipEvents on the op's stream (= torch's current stream) for the median."""
     kstage = "render_fwd" if wl.forward_only else "render_bwd"
@@ -335,6 +354,12 @@ def measure(wl, step, steps, warmup, world, n_stage_steps=3, n_fwd=10):
         tt = torch.tensor([dt], device=wl.dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    return {"dt": dt, "ms_step": dt / steps * 1e3, "median_ms": statistics.median(per_step), "min_ms": min(per_step), "max_ms": max(per_step),
+            "per_step": [round(x, 3) for x in per_step], "kernel_ms": tm[kstage][0] / max(tm[kstage][1], 1)}
+
+
+def untimed_breakdown(wl, step, world, n_stage_steps=3, n_fwd=10):
+    """Extra passes after the timed steps, untimed for `value`: the forward alone, and the per-stage breakdown."""
     # forward-only time of the same workload (SURVEY 8(d): "report fwd-only and fwd+bwd separately"), untimed for `value`
     fence(world)
     tf = time.perf_counter()
@@ -349,9 +374,7 @@ def measure(wl, step, steps, warmup, world, n_stage_steps=3, n_fwd=10):
     torch.cuda.synchronize()
     stages = {k: v[0] / float(n_stage_steps) for k, v in _lib.timing_collect().items()}
     _lib.timing_enable([])
-    return {"dt": dt, "ms_step": dt / steps * 1e3, "median_ms": statistics.median(per_step), "min_ms": min(per_step), "max_ms": max(per_step),
-            "per_step": [round(x, 3) for x in per_step],
-            "kernel_ms": tm[kstage][0] / max(tm[kstage][1], 1), "fwd_ms": fwd_ms, "stages": stages}
+    return {"fwd_ms": fwd_ms, "stages": stages}
 
 
 def walked_entries(wl):
@@ -367,6 +390,44 @@ def walked_entries(wl):
     ipt = int(img[moff:moff + 128].view(torch.int32)[10].item())          # waves per tile of the forward variant that ran: the words lie at [tile * ipt + wave]
     tw = img[off:off + tiles * ipt * 4].view(torch.int32).view(tiles, ipt)
     return int(tw.max(dim=1).values.to(torch.int64).sum().item())
+
+
+OUTPUT_NAMES = ("color", "radii", "normal_map", "median_depth", "cam_feat", "warped_image", "min_depth_diff", "camera_ray", "use_first_src_frame")
+DUMP_SAMPLE = 65536           # Gaussians / pixels in the fixed sample that stands for an array too large to write whole
+DUMP_WHOLE_MAX = 8 << 20      # elements: the image and the radii are written whole up to this size
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, one DIR/<name>.npy each (float32; the loss float64).  The image and the
+    radii whole; the geo planes (render_geo only) at a fixed seeded sample of pixels; the gradients of the leaves at a fixed seeded sample of
+    Gaussians (every Gaussian when there are at most DUMP_SAMPLE).  Same arguments, same inputs, same samples: two builds compare file by file."""
+    last = wl.last
+    HW = wl.H * wl.W
+    dev = last["outs"][0].device
+    gs = torch.as_tensor(np.sort(np.random.default_rng(0).choice(wl.P, min(wl.P, DUMP_SAMPLE), replace=False)), device=dev)
+    px = torch.as_tensor(np.sort(np.random.default_rng(1).choice(HW, min(HW, DUMP_SAMPLE), replace=False)), device=dev)
+    arrays = {}
+    for k, (name, t) in enumerate(zip(OUTPUT_NAMES, last["outs"])):
+        if k >= 2 and not wl.geo:
+            break          # the colour pass returns placeholders for the geo planes
+        t = t.detach().float()
+        if k == 1:
+            arrays[name] = t if t.numel() <= DUMP_WHOLE_MAX else t[gs]
+        else:
+            arrays[name] = t if (k == 0 and t.numel() <= DUMP_WHOLE_MAX) else t.reshape(-1, HW)[:, px]
+    if last["loss"] is not None:
+        arrays["loss"] = last["loss"].double()
+    for key, leaf in wl.leaves.items():
+        if leaf.grad is not None:
+            arrays["grad_" + key] = leaf.grad.detach().float()[gs]
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def roofline(wl, m, workload_tag, walked=None):
@@ -745,7 +806,7 @@ def main():
                     help="NOT the BASELINE workload: shape of the Gaussians (synthetic.make_gaussians): plane = what IBGS / PGSR train towards")
     ap.add_argument("--scale-sigma", type=float, default=0.0,
                     help="NOT the BASELINE workload: log-normal spread of the Gaussian sizes (a heavy tail of large ones, as densification leaves it)")
-    ap.add_argument("--no-trained-geo-line", action="store_true", help="skip the `trained_geo` object (the trainer's steady-state workload) of the default line")
+    ap.add_argument("--no-trained-geo-line", action="store_true", help="skip the `trained_geo` object (the trainer's steady-state workload) of the --full line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--exchange", default="factored", choices=["factored", "dense"],
                     help="N > 1: factored = all-gather 3-float dL/dRGB per view + local SH expansion (default); dense = all-reduce of every gradient")
@@ -754,10 +815,15 @@ def main():
     ap.add_argument("--forward-only", action="store_true", help="time the forward render alone (BASELINE configs[1]: --config C2 --forward-only)")
     ap.add_argument("--geo", action="store_true", help="make render_geo=True, n_src=4, L=4 the timed workload (second line of SURVEY 8(d))")
     ap.add_argument("--wave-shape", default=None, choices=["tile", "quadrant"], help="force the blend kernels' work decomposition (experiments)")
-    ap.add_argument("--no-geo-line", action="store_true", help="skip the extra (untimed for `value`) geo measurement in the default line")
+    ap.add_argument("--no-geo-line", action="store_true", help="skip the extra (untimed for `value`) geo measurement in the --full line")
     ap.add_argument("--force-exchange", action="store_true", help="--gpus 1 only: initialise a process group of ONE rank (nccl = RCCL) and run the view-parallel exchange through it -- every "
-                    "collective of the N-GPU step is issued at world size 1; the line gains the `rccl` object (exchange_ms = the fixed cost of the path)")
+                    "collective of the N-GPU step is issued at world size 1; with --full the line gains the `rccl` object (exchange_ms = the fixed cost of the path)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra keys (view hopping, test-time frame, torch-L1 step, C1 CPU baseline protocol)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: forward-only time, stage breakdown, roofline, the geo / trained_geo lines, the extra keys, the "
+                         "exchange object, the CPU baseline (each still subject to its --no-* switch).  Without it the run times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -789,6 +855,7 @@ def main():
         from ibgs_amd import rasterizer as _rz
         _rz.WAVE_SHAPE = a.wave_shape
     wl = Workload(a.config, rank % 8, dev, a.opacity, a.geo, a.forward_only, 1234 + rank)
+    wl.keep_outputs = bool(a.dump_outputs)
     reducer = None
     if world > 1 or forced:
         # the leaves go into the rasterizer as they are: its backward writes their gradients straight into the all-reduce bucket
@@ -806,9 +873,14 @@ def main():
         wl.local_step(bw)
         reducer.reduce()
 
-    m = measure(wl, step, a.steps, a.warmup, world)
+    m = timed_steps(wl, step, a.steps, a.warmup, world)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(wl, a.dump_outputs)
+    # everything below the headline is --full's
+    if a.full:
+        m.update(untimed_breakdown(wl, step, world))
     rccl = None
-    if (world > 1 or forced) and not a.forward_only:
+    if a.full and (world > 1 or forced) and not a.forward_only:
         # serial cost of the exchange alone (hipEvents around reduce() on the compute stream, which waits for the collectives),
         # and the step without any exchange; neither enters `value`
         n_x = 5
@@ -841,7 +913,7 @@ def main():
 
     extras = {}
     skip = set(filter(None, os.environ.get("IBGS_BENCH_SKIP", "").split(",")))          # diagnostics: leave named extras out (torch_l1, abs, hint, impl, hop)
-    if world == 1 and not (a.geo or a.forward_only) and not a.no_extras:
+    if a.full and world == 1 and not (a.geo or a.forward_only) and not a.no_extras:
         from ibgs_amd import rasterizer as _r
         # (e) the same step with the one-pass fused L1 (ibgs_amd.losses: value + gradient in one kernel each) instead of the reference's expression (six
         # small torch kernels): what the out-of-scope loss costs the step.  Never `value` (round 5: until round 4 the fused loss WAS the timed step's)
@@ -923,7 +995,7 @@ def main():
                 "num_rendered": int(gwl.R), "gaussians_in_frustum": vis, "gaussians_radius_gt_128px": big, "stages_ms": gm["stages"], "roofline": grf}
 
     geo_line = trained_geo = None
-    if world == 1 and not (a.geo or a.forward_only or a.no_geo_line):
+    if a.full and world == 1 and not (a.geo or a.forward_only or a.no_geo_line):
         # second line of SURVEY 8(d) under the same clock: C3 + render_geo, n_src 4, L 4 (extra key; never part of `value`)
         del step
         torch.cuda.empty_cache()
@@ -932,7 +1004,7 @@ def main():
         del gwl
         torch.cuda.empty_cache()          # the next workload's blocks are then allocated during ITS warm-up (a 54 ms step appeared once in the middle of
                                           # the trained_geo line: the caching allocator releasing and re-allocating the previous workload's blocks)
-    if world == 1 and not (a.geo or a.forward_only or a.no_trained_geo_line):
+    if a.full and world == 1 and not (a.geo or a.forward_only or a.no_trained_geo_line):
         # what train.py:289-292 runs for ~77 % of its iterations: render_geo on TRAINED Gaussians -- plane-like (scene/gaussian_model.py:156-173),
         # a heavy tail of sizes (densification, :580-604), an uneven image (30 % of them in one blob), trained-like opacities.  Extra key; never `value`
         twl = Workload(a.config, rank % 8, dev, "trained", True, False, 1234 + rank, cluster=0.3, anisotropy="plane", scale_sigma=1.0)
@@ -940,14 +1012,13 @@ def main():
         del twl
         torch.cuda.empty_cache()
 
-    if world == 1 and not (a.geo or a.forward_only) and not a.no_extras:
+    if a.full and world == 1 and not (a.geo or a.forward_only) and not a.no_extras:
         extras["test_frame"] = test_frame(dev, wl.c)
         if "small_frame" not in skip:
             extras["small_frame"] = small_frame(dev, max(10, min(30, a.steps)))
         if "train_iter" not in skip and a.config == "C3":
             extras["train_iter"] = train_iter(dev, wl.c, max(8, min(16, a.steps)))
     if rank == 0:
-        rf = roofline(wl, m, workload_tag(a.config, a.geo, a.forward_only, a.opacity, a.cluster, a.anisotropy, a.scale_sigma))
         out = {
             "metric": ("forward render fps " + a.config) if a.forward_only else
                       ("train-step fps (fwd+bwd raster) @1080p, 1M Gaussians" if a.config == "C3" else "train-step fps (fwd+bwd raster) " + a.config),
@@ -957,20 +1028,20 @@ def main():
             "config": {"workload": wl.describe(a.opacity, world, a.exchange), "num_rendered": int(wl.R), "parallelism": "view-parallel x%d" % world},
             "median_ms_hipevent": m["median_ms"], "min_ms_hipevent": m["min_ms"], "max_ms_hipevent": m["max_ms"],
             "per_step_ms_hipevent": m["per_step"],          # every timed step: where the wall clock differs from the median, it is these outliers
-            "forward_only_ms": m["fwd_ms"],
-            "roofline": rf,
-            "stages_ms": m["stages"],
         }
+        if forced and not a.forward_only:
+            out["forced_exchange"] = True          # the timed step ran the N-GPU exchange at world size 1 (its fixed cost is inside `value`)
+        if a.full:
+            out.update({"forward_only_ms": m["fwd_ms"], "stages_ms": m["stages"],
+                        "roofline": roofline(wl, m, workload_tag(a.config, a.geo, a.forward_only, a.opacity, a.cluster, a.anisotropy, a.scale_sigma))})
         if rccl is not None:
             out["rccl"] = rccl
-            if forced:
-                out["forced_exchange"] = True          # the timed step ran the N-GPU exchange at world size 1 (its fixed cost is inside `value`)
         if geo_line is not None:
             out["geo"] = geo_line
         if trained_geo is not None:
             out["trained_geo"] = trained_geo
         out.update(extras)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl.inp, a.config)
             if not a.no_extras:
                 out["cpu_baseline"]["c1_protocol"] = cpu_baseline_c1(dev)

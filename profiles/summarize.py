@@ -2,9 +2,9 @@
 """Condenses rocprofv3 CSV output (gpurun_out/<round>_{stats,fetch,write,sq,tcc}) into the small
 summaries committed under profiles/.  Usage: python profiles/summarize.py r01
 
-Commands that produced the inputs (on the MI355X box, `cd /tmp && export TMPDIR=/tmp`):
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r01_stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE  ... -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline   (own pass)
+Commands that produced the inputs (on the MI355X box, `cd /tmp && export TMPDIR=/tmp`; tools/profile_round.sh runs them all):
+  rocprofv3 --kernel-trace --stats --output-format csv -d <out>/r01_stats -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE  ... -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline   (own pass)
   rocprofv3 --kernel-trace --pmc WRITE_SIZE  ... (own pass)
   rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE ...
   rocprofv3 --kernel-trace --pmc TCC_EA0_ATOMIC_sum TCC_HIT_sum TCC_MISS_sum ...
@@ -46,7 +46,7 @@ def main():
     if st:
         rows = list(csv.DictReader(open(st)))
         with open(os.path.join(ROOT, "profiles", tag + "_kernel_stats.csv"), "w") as f:
-            f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline (23 steps + 3 stage-timing steps + 10 forward-only passes)\n")
+            f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline (23 steps + 3 stage-timing steps + 10 forward-only passes)\n")
             f.write("kernel,calls,total_ms,avg_us,min_us,max_us,pct\n")
             for r in rows[:24]:
                 f.write("%s,%s,%.3f,%.2f,%.2f,%.2f,%s\n" % (short(r["Name"]), r["Calls"], float(r["TotalDurationNs"]) / 1e6,

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("extra", [[], ["--geo"], ["--forward-only"]])
 def test_bench_emits_one_contract_line(extra):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "C1",
-                        "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--no-cpu-baseline", "--full"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -44,13 +44,49 @@ def test_bench_emits_one_contract_line(extra):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--geo"]])
+def test_bench_plain_line_and_dumped_outputs(extra, tmp_path):
+    """Without --full the line holds the headline alone; --dump-outputs writes what the last timed step computed (float32 / float64, at most
+    64 MB): the image and radii whole, the geo planes at a pixel sample, the gradients of every leaf (all 10 k Gaussians of C1)."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "C1",
+                        "--dump-outputs", str(out)] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and len(d["per_step_ms_hipevent"]) == 3
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "stages_ms", "forward_only_ms", "geo", "trained_geo", "cpu_baseline", "test_frame", "view_hopping"):
+        assert k not in d, k
+    a = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    P = 10000
+    assert a["color"].shape == (3, 400, 400) and a["radii"].shape == (P,) and a["loss"].shape == () and a["loss"] > 0
+    assert (a["radii"] > 0).sum() > 0 and np.abs(a["grad_means3D"]).sum() > 0
+    for k, n in (("means3D", 3), ("opacities", 1), ("scales", 3), ("rotations", 4), ("means2D", 3), ("means2D_abs", 3)):
+        assert a["grad_" + k].shape == (P, n), k
+    assert a["grad_shs"].shape[0] == P
+    if extra:
+        assert a["grad_all_map"].shape == (P, 5)
+        for k, c in (("normal_map", 3), ("median_depth", 1), ("warped_image", 15)):
+            assert a[k].shape == (c, 65536), k
+    else:
+        assert "normal_map" not in a
+
+
+@pytest.mark.gpu
 def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` with no launcher starts two ranks itself.  On this 1-GPU box: (a) with RCCL it must refuse
     loudly (exit code 2, nothing on stdout); (b) with the ranks allowed to share the device over gloo it must print n_gpus = 2
     and the exchange object."""
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "C1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "C1", "--no-cpu-baseline", "--full"]
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert r.returncode == 2 and not r.stdout.strip() and "refusing" in r.stderr, (r.returncode, r.stdout, r.stderr[-500:])
@@ -75,7 +111,7 @@ def test_bench_eight_view_step_on_one_gpu():
     (An 8-GPU RCCL run is the driver's; this checks the code path it will take.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(IBGS_BENCH_SHARE_GPU="1", IBGS_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--config", "C1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--config", "C1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

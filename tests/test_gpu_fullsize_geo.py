@@ -1,4 +1,4 @@
-"""The two geo workloads of bench.py's default line at FULL size against the oracle, in the suite the driver runs (round 5; until round 4 these
+"""The two geo workloads of bench.py's `--full` line at FULL size against the oracle, in the suite the driver runs (round 5; until round 4 these
 tables were `tools/parity_c3.py geo ...` text files under profiles/):
 
   `geo`          C3 (1 M random-init Gaussians, 1920 x 1080, SH 3) + render_geo, 4 sources, L = 4          (SURVEY.md 8(d) "second line")

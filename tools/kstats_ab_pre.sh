@@ -2,7 +2,7 @@
 # per-kernel averages (rocprofv3 --kernel-trace --stats) of the preprocess stage's kernels for the current library and an older one, alternating, on one box
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-B="--no-cpu-baseline --no-extras --no-geo-line --no-trained-geo-line"
+B="--full --no-cpu-baseline --no-extras --no-geo-line --no-trained-geo-line"
 other=${1:-ibgs_amd/_exp/libibgs_rast_r06b.so}
 for rep in 1 2; do
   for lib in "" "$other"; do
