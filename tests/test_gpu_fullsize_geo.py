@@ -20,6 +20,7 @@ import oracle
 from ibgs_amd import rasterizer
 from tests import hipref
 from tests.metrics import l1, psnr, rel_l2
+from tests.scenes import valid_source_histogram
 from tests.test_gpu_anisotropic import F64_K
 from tests.test_gpu_parity import GRAD_PAIRS, canon_valid
 
@@ -43,7 +44,9 @@ def bench_geo_inputs(opacity, **shape):
     return inp
 
 
-def full_size_geo_parity(name, inp):
+def full_size_geo_parity(name, inp, min_mean_valid=None, min_all_valid=None, extra_checks=None):
+    """min_mean_valid / min_all_valid: bars on the oracle's valid-source histogram (mean count per covered pixel / share of covered pixels with all n_src
+    valid) -- a scene that is to exercise the warp path says how much of it; extra_checks(o, ist, say) -> list of failures: more checks on the HIP outputs."""
     H, W = int(inp["H"]), int(inp["W"])
     lines = []
 
@@ -97,6 +100,17 @@ def full_size_geo_parity(name, inp):
     say("    (the oracle against its own fma-contracted build: windows equal on %.6f, valid-source sets differ on %d pixels, n_contrib equal on %.6f)"
         % (tw_win, int((~tw_same).sum()), (tw["n_contrib"] == ref["n_contrib"]).mean()))
     assert first > 0.05, "the scene does not exercise the warp path"
+    # ---- how many sources the warp finds valid per covered pixel: HIP and oracle, and the regime the caller asks for
+    n_src = int(inp["n_src"])
+    h_ref, m_ref = valid_source_histogram(ref["valid_src_idx"], ref["final_T"], n_src)
+    h_hip, m_hip = valid_source_histogram(ist["valid_idx"], ist["final_T"], n_src)
+    say("valid sources per covered pixel: oracle mean %.3f [%s], HIP mean %.3f [%s]" % (m_ref, " ".join("%.4f" % x for x in h_ref), m_hip,
+                                                                                   " ".join("%.4f" % x for x in h_hip)))
+    # (the two histograms can differ only by the pixels whose valid-source sets differ: asserted below)
+    if min_mean_valid is not None:
+        assert m_ref >= min_mean_valid, "the scene has drifted out of the multi-view-consistent regime"
+    if min_all_valid is not None:
+        assert h_ref[n_src] >= min_all_valid, "too few pixels with every source valid"
     assert win > 0.9999 and (~same).mean() <= 1e-4, "median-buffer windows / valid-source sets differ on more pixels than rounding explains"
     assert (1 - win) <= max(1e-5, 3 * (1 - tw_win)) and (~same).sum() <= max(20, 3 * int((~tw_same).sum())), "more decision flips than the reference's own arithmetic leaves open"
     ok = same.reshape(H, W)
@@ -128,6 +142,8 @@ def full_size_geo_parity(name, inp):
         say("    %-12s %.2e | %.2e | %.2e   %s" % (lk, e32, e64, floor, verdict))
         if verdict == "FAIL":
             failed.append(lk)
+    if extra_checks is not None:
+        failed += extra_checks(o, ist, say)
     out_dir = os.path.join(ROOT, "gpurun_out")
     if os.path.isdir(out_dir):
         with open(os.path.join(out_dir, "parity_fullsize_%s.txt" % name), "w") as f:
