@@ -3,7 +3,8 @@
 No torch.utils.cpp_extension here: under ROCm it would hipify the sources, and the library has no
 torch types in its ABI anyway.  One hipcc invocation per translation unit (parallel), then a link.
 preprocess.hip is compiled with -ffp-contract=off so its integer outputs are bit-identical to the
-C oracle (see the header of that file).
+C oracle (see the header of that file); so is scan_sort.hip, whose depth sort launches also run the SH
+colours (sh_color.h).
 """
 import os
 import subprocess
@@ -17,6 +18,7 @@ LIB = os.path.join(HERE, "libibgs_rast.so")
 SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
+    "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
     # no SLP packing: v_pk_*_f32 is not faster than two scalar VALU ops on gfx950 and costs v_mov / s_nop glue
     "render_fwd": ["-fno-slp-vectorize"],
     "render_bwd": ["-fno-slp-vectorize", "-fno-signed-zeros"],

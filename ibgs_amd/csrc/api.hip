@@ -8,6 +8,7 @@
 // Everything is enqueued on the caller's stream; no device-wide synchronisation, no allocation
 // (arenas are caller-owned), no persistent library state.
 #include "common.h"
+#include "sh_color.h"
 #include <sched.h>
 #include <time.h>
 #include <string.h>
@@ -312,6 +313,8 @@ void ibgs_last_forward_stats(int64_t* out)
 // (evaluation renders, the last forward of a run).  wait != 0: the stream is drained first, the answer is then final; else only what has arrived is reported.
 // tests only: the look-back patience of the depth sort's single-launch passes (0 = give up at the first unpublished word: provokes the asynchronous error path)
 void ibgs_debug_set_lookback_spins(uint32_t v) { radix_set_lookback_spins(v); }
+// tests only: whether a hinted forward's SH colours ride in the depth sort's launches (1, the default) or run in front of it (0)
+void ibgs_debug_set_sh_ride(int32_t on) { radix_set_sh_ride(on != 0); }
 int32_t ibgs_check_async(void* stream, int32_t wait)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -391,6 +394,8 @@ int64_t ibgs_forward(const ibgs_forward_args* ap)
     RSlot* rs = rslot(s, true);
     if (!rs) return -IBGS_ERR_HIP;
     uint32_t ticket = 0;
+    ShRide ride;
+    bool riding = false;          // the SH colours (and the note) travel with the depth sort's launches (scan_sort.hip)
     { StageTimer t(s, IBGS_STAGE_PREPROCESS);
       if ((rc = launch_preprocess(s, a, g, deferred ? 1 : 0))) return rc;
       if (deferred) {
@@ -400,8 +405,13 @@ int64_t ibgs_forward(const ibgs_forward_args* ap)
           // worth of GPU latency -- ~45 us of a 0.34 ms call pair, profiles/r05_host_split.txt -- before it could queue the loss and the backward.)
           ticket = ++rs->seq;          // (wraps after 4 G forwards on one stream: the comparison below is for equality)
           const RenderedNote note{g.tile_partial, (uint32_t)nwaves, ticket, rs->host};
-          if ((rc = launch_preprocess(s, a, g, 2, &note)) < 0) return rc;          // (1: the SH colour kernel's first workgroup carries the note -- one launch fewer)
-          if (rc == 0) { hipLaunchKernelGGL(rendered_note_kernel, dim3(1), dim3(1024), 0, s, note); IBGS_HIP(hipGetLastError()); }
+          // (round 7) the SH colours of a single view ride in the depth sort's launches, the note in its first one: the sort's five launches are
+          // latency-bound and leave most CUs idle, the SH pass is HBM-bound.  Else the SH kernel runs here, in front of the sort.
+          riding = radix_takes_sh_ride((size_t)Pn, 32) && preprocess_sh_ride(a, g, &note, &ride);
+          if (!riding) {
+              if ((rc = launch_preprocess(s, a, g, 2, &note)) < 0) return rc;          // (1: the SH colour kernel's first workgroup carries the note -- one launch fewer)
+              if (rc == 0) { hipLaunchKernelGGL(rendered_note_kernel, dim3(1), dim3(1024), 0, s, note); IBGS_HIP(hipGetLastError()); }
+          }
       }
     }
     if ((rc = stage_check(s, debug, "preprocess"))) return rc;
@@ -410,7 +420,7 @@ int64_t ibgs_forward(const ibgs_forward_args* ap)
       // sized from a hint: that one travels back together with them --, and [Pn + 3], [Pn + 4])
       // Gaussians without tiles (key 0xFFFFFFFF) are not carried through the sort; [Pn + 3] = how many others there are
       if ((rc = radix_sort_pairs(s, g.sort_key, g.sort_val, (size_t)Pn, 32, g.hist, g.hist_elems, deferred ? g.tile_partial + nwaves : g.offsets + Pn + 1,
-                                 g.offsets + Pn + 3, true, g.offsets + Pn + 4))) return rc; }
+                                 g.offsets + Pn + 3, true, g.offsets + Pn + 4, riding ? &ride : nullptr))) return rc; }
     if ((rc = stage_check(s, debug, "depth sort"))) return rc;
     // R = total number of (Gaussian, tile) pairs.  The binning arena is sized from it, and it is only known on the device.
     //  * no hint (first call of a shape, or debug): the tiles-touched counts are scanned, R travels to the host through a pinned

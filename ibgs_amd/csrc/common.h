@@ -424,9 +424,12 @@ __device__ __forceinline__ void rendered_note_block(const RenderedNote& n, unsig
         __hip_atomic_store(n.host + 2, n.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+struct ShRide;          // sh_color.h: the SH colours of a hinted forward, carried by the depth sort's launches
 // phase 0: everything; 1: the geometry kernel(s) alone; 2: what phase 1 left out (the SH colours).  note (phase 2): carried by the SH kernel's first workgroup when
 // such a kernel is launched -- the return value is then 1 (0: the caller launches rendered_note_kernel itself; < 0: error)
 int launch_preprocess(hipStream_t s, const ibgs_forward_args& a, const GeomState& g, int phase = 0, const RenderedNote* note = nullptr);
+// phase 2 of a single view as an ShRide instead of a launch (false: no SH kernel to carry -- precomputed colours, depth-only, several views)
+bool preprocess_sh_ride(const ibgs_forward_args& a, const GeomState& g, const RenderedNote* note, ShRide* out);
 int launch_mark_visible(hipStream_t s, int P, const float* means3D, const float* vm, uint8_t* present);
 
 // device-wide primitives (scan_sort.hip)
@@ -434,7 +437,10 @@ size_t radix_hist_elems(size_t n);      // scratch (uint32 elements) needed by r
 // Stable LSD radix sort of (key,val) pairs on key bits [0, nbits). Result lands in keys[0]/vals[0].
 int radix_sort_pairs(hipStream_t s, uint32_t* keys[2], uint32_t* vals[2], size_t n, int nbits,
                      uint32_t* hist, size_t hist_elems, uint32_t* err_dev = nullptr, uint32_t* kept_dev = nullptr, bool scratch_is_zero = false,
-                     uint32_t* result_alt = nullptr);
+                     uint32_t* result_alt = nullptr, const ShRide* ride = nullptr);
+// ride: the SH colours of a hinted forward run in the sort's launches (scan_sort.hip, sh_color.h); only where radix_takes_sh_ride(n, nbits) says so
+bool radix_takes_sh_ride(size_t n, int nbits);
+void radix_set_sh_ride(bool on);          // tests: off = the standalone sh_color_kernel in front of the sort
 // result_alt: device word (zeroed by the caller).  When given (32-bit keys, single-launch passes), a LAST pass in which every key carries the same digit --
 //          the top byte of depths within [2, 8), say -- moves nothing and sets *result_alt = 1: the result is then in keys[1] / vals[1] (else, as always, in [0])
 size_t radix_zero_elems(size_t n, int nbits);      // leading words of `hist` the sort needs zeroed (see scratch_is_zero)

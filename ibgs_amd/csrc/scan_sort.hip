@@ -10,6 +10,7 @@
 // per-wave LDS counters; scatter is staged through LDS so that global writes are runs of
 // consecutive addresses.
 #include "common.h"
+#include "sh_color.h"
 #include <cstdlib>
 
 namespace ibgs {
@@ -293,52 +294,65 @@ constexpr int OS_MAX_PASS = 4;
 constexpr int OS_HIST_THREADS = 1024;      // few, large workgroups: every workgroup ends with one global atomic per non-empty bin
 constexpr int OS_THREADS = 512, OS_WAVES = OS_THREADS / 64, OS_ITEMS = RS_CHUNK / OS_THREADS;      // same chunk as the classic passes, twice the waves: the ranking is a chain of LDS round trips per item
 
+// one workgroup of the histogram launch: blocks [0, nblk) stride over the keys (nblk: the launch's histogram workgroups, whatever else it carries)
+template <int NT>
+__device__ __forceinline__ void onesweep_hist_block(const uint32_t* __restrict__ keys, size_t n, int npass, int dbits, uint32_t* __restrict__ ghist,
+                                                    int drop_max, uint32_t* __restrict__ n_kept, unsigned nblk, uint32_t (*h)[RS_MAX_BINS], uint32_t* s_kept)
+{
+    for (int k = threadIdx.x; k < OS_MAX_PASS * RS_MAX_BINS; k += NT) (&h[0][0])[k] = 0;
+    if (threadIdx.x == 0) *s_kept = 0;
+    __syncthreads();
+    const uint32_t mask = (1u << dbits) - 1u;
+    const size_t stride = (size_t)nblk * NT;
+    uint32_t kept = 0;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += stride) {
+        const uint32_t k = keys[i];
+        if (drop_max && k == 0xFFFFFFFFu) continue;
+        kept++;
+        for (int p = 0; p < npass; p++) atomicAdd(&h[p][(k >> (p * dbits)) & mask], 1u);
+    }
+    if (kept) atomicAdd(s_kept, kept);
+    __syncthreads();
+    if (threadIdx.x == 0 && *s_kept) atomicAdd(n_kept, *s_kept);
+    for (int k = threadIdx.x; k < npass * RS_MAX_BINS; k += NT) {
+        const uint32_t c = (&h[0][0])[k];
+        if (c) atomicAdd(&ghist[k], c);
+    }
+}
+
 __global__ void __launch_bounds__(OS_HIST_THREADS) onesweep_hist_kernel(const uint32_t* __restrict__ keys, size_t n, int npass, int dbits,
                                                                    uint32_t* __restrict__ ghist /* npass x 256 */,
                                                                    int drop_max /* keys 0xFFFFFFFF take no part */, uint32_t* __restrict__ n_kept)
 {
     __shared__ uint32_t h[OS_MAX_PASS][RS_MAX_BINS];
     __shared__ uint32_t s_kept;
-    for (int k = threadIdx.x; k < OS_MAX_PASS * RS_MAX_BINS; k += OS_HIST_THREADS) (&h[0][0])[k] = 0;
-    if (threadIdx.x == 0) s_kept = 0;
-    __syncthreads();
-    const uint32_t mask = (1u << dbits) - 1u;
-    const size_t stride = (size_t)gridDim.x * OS_HIST_THREADS;
-    uint32_t kept = 0;
-    for (size_t i = (size_t)blockIdx.x * OS_HIST_THREADS + threadIdx.x; i < n; i += stride) {
-        const uint32_t k = keys[i];
-        if (drop_max && k == 0xFFFFFFFFu) continue;
-        kept++;
-        for (int p = 0; p < npass; p++) atomicAdd(&h[p][(k >> (p * dbits)) & mask], 1u);
-    }
-    if (kept) atomicAdd(&s_kept, kept);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_kept) atomicAdd(n_kept, s_kept);
-    for (int k = threadIdx.x; k < npass * RS_MAX_BINS; k += OS_HIST_THREADS) {
-        const uint32_t c = (&h[0][0])[k];
-        if (c) atomicAdd(&ghist[k], c);
-    }
+    onesweep_hist_block<OS_HIST_THREADS>(keys, n, npass, dbits, ghist, drop_max, n_kept, gridDim.x, h, &s_kept);
 }
 
-__global__ void __launch_bounds__(OS_THREADS) onesweep_pass_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
-                                                                   uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
-                                                                   size_t n, int shift, int nbits, int nbins,
-                                                                   const uint32_t* __restrict__ ghist /* 256, this pass */,
-                                                                   uint32_t* __restrict__ status /* nblocks x 256, zeroed */,
-                                                                   uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
-                                                                   int drop_here /* first pass of a sort that drops the 0xFFFFFFFF keys */,
-                                                                   const uint32_t* __restrict__ n_kept /* items that take part (device) */,
-                                                                   uint32_t* __restrict__ stays /* last pass only, or nullptr: a pass that would move nothing may leave its input where it is and say so */,
-                                                                   uint32_t spin_limit /* look-back: sleeps on an unpublished word before the pass gives up (sets *err) */)
+struct OsPassLds {          // a pass workgroup's LDS (59 KB)
+    unsigned long long ptab[OS_WAVES][RS_MAX_BINS];      // match-any slots (wave_rank)
+    uint32_t wcnt[OS_WAVES][RS_MAX_BINS];
+    uint32_t dstart[RS_MAX_BINS];
+    uint32_t delta[RS_MAX_BINS];
+    uint32_t lds_wave[4];
+    uint32_t skey[RS_CHUNK];
+    uint32_t sval[RS_CHUNK];
+    uint32_t s_bid;
+};
+
+__device__ __forceinline__ void onesweep_pass_block(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                   uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                   size_t n, int shift, int nbits, int nbins,
+                                                   const uint32_t* __restrict__ ghist /* 256, this pass */,
+                                                   uint32_t* __restrict__ status /* nblocks x 256, zeroed */,
+                                                   uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
+                                                   int drop_here /* first pass of a sort that drops the 0xFFFFFFFF keys */,
+                                                   const uint32_t* __restrict__ n_kept /* items that take part (device) */,
+                                                   uint32_t* __restrict__ stays /* last pass only, or nullptr: a pass that would move nothing may leave its input where it is and say so */,
+                                                   uint32_t spin_limit /* look-back: sleeps on an unpublished word before the pass gives up (sets *err) */,
+                                                   OsPassLds& L)
 {
-    __shared__ uint32_t wcnt[OS_WAVES][RS_MAX_BINS];
-    __shared__ unsigned long long ptab[OS_WAVES][RS_MAX_BINS];      // match-any slots (wave_rank)
-    __shared__ uint32_t dstart[RS_MAX_BINS];
-    __shared__ uint32_t delta[RS_MAX_BINS];
-    __shared__ uint32_t lds_wave[4];
-    __shared__ uint32_t skey[RS_CHUNK];
-    __shared__ uint32_t sval[RS_CHUNK];
-    __shared__ uint32_t s_bid;
+    auto& wcnt = L.wcnt; auto& ptab = L.ptab; auto& dstart = L.dstart; auto& delta = L.delta; auto& lds_wave = L.lds_wave; auto& skey = L.skey; auto& sval = L.sval; auto& s_bid = L.s_bid;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t kept = *n_kept;
@@ -460,6 +474,72 @@ __global__ void __launch_bounds__(OS_THREADS) onesweep_pass_kernel(const uint32_
     }
 }
 
+__global__ void __launch_bounds__(OS_THREADS) onesweep_pass_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                                   uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                                   size_t n, int shift, int nbits, int nbins,
+                                                                   const uint32_t* __restrict__ ghist /* 256, this pass */,
+                                                                   uint32_t* __restrict__ status /* nblocks x 256, zeroed */,
+                                                                   uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
+                                                                   int drop_here /* first pass of a sort that drops the 0xFFFFFFFF keys */,
+                                                                   const uint32_t* __restrict__ n_kept /* items that take part (device) */,
+                                                                   uint32_t* __restrict__ stays /* last pass only, or nullptr: a pass that would move nothing may leave its input where it is and say so */,
+                                                                   uint32_t spin_limit /* look-back: sleeps on an unpublished word before the pass gives up (sets *err) */)
+{
+    __shared__ OsPassLds L;
+    onesweep_pass_block(keys_in, vals_in, keys_out, vals_out, n, shift, nbits, nbins, ghist, status, ticket, err, drop_here, n_kept, stays, spin_limit, L);
+}
+
+// ---- the SH colours of a hinted forward, riding in the depth sort's launches (sh_color.h: ShRide) ------------------------------------------------------------
+// Behind the sort's workgroups each launch carries SH workgroups of as many waves as its own (16 in the hist launch, 8 in a pass): a slice [wave0, wave1)
+// of the waves sh_color_kernel would run, the same sh_color_wave, so records and clamp bits do not depend on where it ran.  An SH workgroup decides its
+// role from blockIdx alone: it takes no ticket, and no chunk ever waits for it (a chunk only looks back at tickets taken before its own, by workgroups that
+// run), whatever the dispatch order.  The LDS of the two roles is one union: a pass workgroup keeps its 59 KB (two per CU, as the plain pass), a hist
+// workgroup grows to 106 KB (one per CU: 16 waves, as many SH waves per CU as in a pass).  The hist launch's first SH workgroup first adds the tile sums up
+// for the host (the note: R).
+constexpr int OS_HIST_WAVES = OS_HIST_THREADS / 64;
+union OsHistShLds {
+    struct { uint32_t h[OS_MAX_PASS][RS_MAX_BINS]; uint32_t kept; } hist;
+    float sh[OS_HIST_WAVES][SHC_WAVE_FLOATS];
+};
+union OsPassShLds {
+    OsPassLds sort;
+    float sh[OS_WAVES][SHC_WAVE_FLOATS];
+};
+
+template <bool SPLIT, int WAVES /* per workgroup */>
+__device__ __forceinline__ void sh_ride_block(const ShRide& r, unsigned j /* SH workgroup of this launch */, int wave0, int wave1, float (*sh)[SHC_WAVE_FLOATS])
+{
+    const int wave = wave0 + (int)j * WAVES + (int)(threadIdx.x >> 6);
+    if (wave < wave1) sh_color_wave<SPLIT>(r.p, r.cam, wave, sh[threadIdx.x >> 6]);          // (the stage is private to the wave)
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(OS_HIST_THREADS) onesweep_hist_sh_kernel(const uint32_t* __restrict__ keys, size_t n, int npass, int dbits, uint32_t* __restrict__ ghist,
+                                                                      int drop_max, uint32_t* __restrict__ n_kept, unsigned nhist, ShRide r, int wave0, int wave1)
+{
+    __shared__ OsHistShLds L;
+    if (blockIdx.x < nhist) { onesweep_hist_block<OS_HIST_THREADS>(keys, n, npass, dbits, ghist, drop_max, n_kept, nhist, L.hist.h, &L.hist.kept); return; }
+    const unsigned j = blockIdx.x - nhist;
+    if (j == 0 && r.p.note.host != nullptr) {          // (workgroup-uniform) R for the host, before anything else: it sizes the tile lists with it
+        __shared__ unsigned long long s_note[OS_HIST_WAVES];
+        rendered_note_block<OS_HIST_THREADS>(r.p.note, s_note);
+    }
+    sh_ride_block<SPLIT, OS_HIST_WAVES>(r, j, wave0, wave1, L.sh);
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(OS_THREADS) onesweep_pass_sh_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                                      uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                                      size_t n, int shift, int nbits, int nbins, const uint32_t* __restrict__ ghist,
+                                                                      uint32_t* __restrict__ status, uint32_t* __restrict__ ticket, uint32_t* __restrict__ err,
+                                                                      int drop_here, const uint32_t* __restrict__ n_kept, uint32_t* __restrict__ stays, uint32_t spin_limit,
+                                                                      unsigned nsort, ShRide r, int wave0, int wave1)
+{
+    __shared__ OsPassShLds L;
+    if (blockIdx.x >= nsort) { sh_ride_block<SPLIT, OS_WAVES>(r, blockIdx.x - nsort, wave0, wave1, L.sh); return; }          // (workgroup-uniform; before any ticket)
+    onesweep_pass_block(keys_in, vals_in, keys_out, vals_out, n, shift, nbits, nbins, ghist, status, ticket, err, drop_here, n_kept, stays, spin_limit, L.sort);
+}
+
 // Measured on MI355X (C3): depth sort (P = 1M, 245 chunks) 0.154 -> 0.135 ms, tile sort (R = 12.5M, 3052 chunks)
 // 0.189 -> 0.254 ms: when ~1000 workgroups start together their look-back walks hundreds of AGGREGATE rows before
 // the first INCLUSIVE prefix appears.  So it is used where it wins -- sorts of at most OS_AUTO_MAX_CHUNKS chunks (the
@@ -470,6 +550,26 @@ static int g_use_onesweep = getenv("IBGS_RADIX_ONESWEEP") ? atoi(getenv("IBGS_RA
 // every pass REPORT a time-out that did not happen (a real one cannot be staged: workgroups start in order, a predecessor has practically always published by the
 // time its successor looks) -- how tests/test_gpu_async_sort_error.py drives the asynchronous error path; the sort itself stays sound
 static uint32_t g_lookback_spins = 1u << 26;
+// How the SH waves of a hinted forward spread over the depth sort's launches: weights of the hist launch and of passes 0..3 (C3: ~13 us of hist, three
+// passes of ~18 us that move keys, one of ~5 us that finds the top byte constant and gets none).  Six splits measured at C3 (same box, twice): preprocess +
+// depth sort 0.150-0.159 ms for all of them against 0.184-0.188 for the standalone pass, this one the lowest both times.  IBGS_SH_RIDE="w0,w1,w2,w3,w4" sets them, "0" turns riding off (the
+// standalone sh_color_kernel then runs in front of the sort, as without a hint); read once, when the library is loaded.  ibgs_debug_set_sh_ride: tests.
+static int g_sh_ride_w[1 + OS_MAX_PASS] = {5, 18, 18, 18, 0};
+static int g_sh_ride = [] {
+    const char* e = getenv("IBGS_SH_RIDE");
+    if (!e) return 1;
+    int w[1 + OS_MAX_PASS] = {0, 0, 0, 0, 0}, k = 0, sum = 0;
+    for (const char* c = e; *c && k <= OS_MAX_PASS; k++) {
+        w[k] = atoi(c);
+        sum += w[k] > 0 ? w[k] : 0;
+        while (*c && *c != ',') c++;
+        if (*c == ',') c++;
+    }
+    if (sum <= 0) return 0;
+    for (int i = 0; i <= OS_MAX_PASS; i++) g_sh_ride_w[i] = w[i] > 0 ? w[i] : 0;
+    return 1;
+}();
+void radix_set_sh_ride(bool on) { g_sh_ride = on ? 1 : 0; }
 void radix_set_onesweep(bool on) { g_use_onesweep = on ? 1 : 0; }
 void radix_set_lookback_spins(uint32_t v) { g_lookback_spins = v; }
 constexpr size_t OS_AUTO_MAX_CHUNKS = 4096;          // (round 1: 512 -- with 256-thread chunks the look-back of ~3000 workgroups lost against hist + scan + scatter; with 512-thread chunks and
@@ -482,7 +582,8 @@ static size_t onesweep_elems(size_t n)
 }
 
 static int radix_sort_pairs_onesweep(hipStream_t s, uint32_t* keys[2], uint32_t* vals[2], size_t n, int npass, int dbits,
-                                     uint32_t* scratch, size_t scratch_elems, uint32_t* err_dev, uint32_t* kept_dev, bool scratch_is_zero, uint32_t* result_alt)
+                                     uint32_t* scratch, size_t scratch_elems, uint32_t* err_dev, uint32_t* kept_dev, bool scratch_is_zero, uint32_t* result_alt,
+                                     const ShRide* ride)
 {
     const unsigned nblocks = (unsigned)((n + RS_CHUNK - 1) / RS_CHUNK);
     const int nbins = 1 << dbits;
@@ -492,16 +593,47 @@ static int radix_sort_pairs_onesweep(hipStream_t s, uint32_t* keys[2], uint32_t*
     uint32_t* tickets = scratch + OS_MAX_PASS * RS_MAX_BINS;      // per pass ticket counters, [32] = error flag, [33] = keys that take part
     uint32_t* status = tickets + 64;
     if (!scratch_is_zero) IBGS_HIP(hipMemsetAsync(scratch, 0, need * sizeof(uint32_t), s));
+    // the SH waves a ride brings: launch k (0 = hist, 1 + pass) takes [cut[k], cut[k + 1]) by the weights of the launches there are
+    int cut[2 + OS_MAX_PASS] = {0, 0, 0, 0, 0, 0};
+    if (ride) {
+        int wsum = 0;
+        for (int k = 0; k <= npass; k++) wsum += g_sh_ride_w[k];
+        if (wsum <= 0) { set_error("SH ride without weights"); return -IBGS_ERR_INVALID; }
+        int acc = 0;
+        for (int k = 0; k <= npass; k++) { acc += g_sh_ride_w[k]; cut[k + 1] = (int)((int64_t)ride->waves * acc / wsum); }
+    }
+    auto sh_groups = [&](int k, int waves) { return (unsigned)((cut[k + 1] - cut[k] + waves - 1) / waves); };
+    const uint32_t* kept_arg = kept_dev ? kept_dev : tickets + 33;
     const unsigned hb = (unsigned)((n + 8u * OS_HIST_THREADS - 1) / (8u * OS_HIST_THREADS));          // ~8 keys per thread (4 and 16 measured: 12.1 / 17.2 us against 12.2)
     const unsigned hblocks = hb < 256u ? (hb ? hb : 1u) : 256u;
-    hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hblocks), dim3(OS_HIST_THREADS), 0, s, keys[0], n, npass, dbits, ghist, kept_dev ? 1 : 0, kept_dev ? kept_dev : tickets + 33);
+    if (!ride) {
+        hipLaunchKernelGGL(onesweep_hist_kernel, dim3(hblocks), dim3(OS_HIST_THREADS), 0, s, keys[0], n, npass, dbits, ghist, kept_dev ? 1 : 0, kept_dev ? kept_dev : tickets + 33);
+    } else {
+        unsigned g = sh_groups(0, OS_HIST_WAVES);
+        if (g == 0 && ride->p.note.host) g = 1;          // the note's workgroup
+        const dim3 grid(hblocks + g);
+        if (ride->split) hipLaunchKernelGGL(onesweep_hist_sh_kernel<true>, grid, dim3(OS_HIST_THREADS), 0, s, keys[0], n, npass, dbits, ghist, kept_dev ? 1 : 0, kept_dev ? kept_dev : tickets + 33, hblocks, *ride, cut[0], cut[1]);
+        else hipLaunchKernelGGL(onesweep_hist_sh_kernel<false>, grid, dim3(OS_HIST_THREADS), 0, s, keys[0], n, npass, dbits, ghist, kept_dev ? 1 : 0, kept_dev ? kept_dev : tickets + 33, hblocks, *ride, cut[0], cut[1]);
+    }
     IBGS_HIP(hipGetLastError());
     int cur = 0;
     for (int pass = 0; pass < npass; pass++) {
-        hipLaunchKernelGGL(onesweep_pass_kernel, dim3(nblocks), dim3(OS_THREADS), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1],
-                           n, pass * dbits, dbits, nbins, ghist + pass * RS_MAX_BINS, status + (size_t)pass * nblocks * RS_MAX_BINS,
-                           tickets + pass, err_dev ? err_dev : tickets + 32, (kept_dev && pass == 0) ? 1 : 0, kept_dev ? kept_dev : tickets + 33,
-                           (result_alt && npass == 4 && pass == 3) ? result_alt : (uint32_t*)nullptr, g_lookback_spins);
+        uint32_t* st = status + (size_t)pass * nblocks * RS_MAX_BINS;
+        uint32_t* e = err_dev ? err_dev : tickets + 32;
+        const int drop = (kept_dev && pass == 0) ? 1 : 0;
+        uint32_t* stays = (result_alt && npass == 4 && pass == 3) ? result_alt : (uint32_t*)nullptr;
+        const unsigned g = ride ? sh_groups(1 + pass, OS_WAVES) : 0u;
+        if (g == 0)
+            hipLaunchKernelGGL(onesweep_pass_kernel, dim3(nblocks), dim3(OS_THREADS), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1],
+                               n, pass * dbits, dbits, nbins, ghist + pass * RS_MAX_BINS, st, tickets + pass, e, drop, kept_arg, stays, g_lookback_spins);
+        else if (ride->split)
+            hipLaunchKernelGGL(onesweep_pass_sh_kernel<true>, dim3(nblocks + g), dim3(OS_THREADS), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1],
+                               n, pass * dbits, dbits, nbins, ghist + pass * RS_MAX_BINS, st, tickets + pass, e, drop, kept_arg, stays, g_lookback_spins,
+                               nblocks, *ride, cut[1 + pass], cut[2 + pass]);
+        else
+            hipLaunchKernelGGL(onesweep_pass_sh_kernel<false>, dim3(nblocks + g), dim3(OS_THREADS), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1],
+                               n, pass * dbits, dbits, nbins, ghist + pass * RS_MAX_BINS, st, tickets + pass, e, drop, kept_arg, stays, g_lookback_spins,
+                               nblocks, *ride, cut[1 + pass], cut[2 + pass]);
         IBGS_HIP(hipGetLastError());
         cur ^= 1;
     }
@@ -550,8 +682,17 @@ size_t radix_zero_elems(size_t n, int nbits_total)
     return (size_t)OS_MAX_PASS * RS_MAX_BINS + 64 + (size_t)npass * nblocks * RS_MAX_BINS;
 }
 
+bool radix_takes_sh_ride(size_t n, int nbits_total)
+{
+    if (!g_sh_ride || n == 0 || nbits_total <= 0) return false;
+    const size_t nblocks = (n + RS_CHUNK - 1) / RS_CHUNK;
+    const int npass = (nbits_total + 7) / 8;
+    const bool want_os = g_use_onesweep >= 0 ? g_use_onesweep != 0 : nblocks <= OS_AUTO_MAX_CHUNKS;
+    return want_os && npass <= OS_MAX_PASS && n < (size_t)OS_VAL_MASK;
+}
+
 int radix_sort_pairs(hipStream_t s, uint32_t* keys[2], uint32_t* vals[2], size_t n, int nbits_total,
-                     uint32_t* hist, size_t hist_elems, uint32_t* err_dev, uint32_t* kept_dev, bool scratch_is_zero, uint32_t* result_alt)
+                     uint32_t* hist, size_t hist_elems, uint32_t* err_dev, uint32_t* kept_dev, bool scratch_is_zero, uint32_t* result_alt, const ShRide* ride)
 {
     if (n == 0 || nbits_total <= 0) return 0;
     const unsigned nblocks = (unsigned)((n + RS_CHUNK - 1) / RS_CHUNK);
@@ -560,7 +701,8 @@ int radix_sort_pairs(hipStream_t s, uint32_t* keys[2], uint32_t* vals[2], size_t
     const int nbins = 1 << dbits;
     const bool want_os = g_use_onesweep >= 0 ? g_use_onesweep != 0 : nblocks <= OS_AUTO_MAX_CHUNKS;
     if (want_os && npass <= OS_MAX_PASS && n < (size_t)OS_VAL_MASK)
-        return radix_sort_pairs_onesweep(s, keys, vals, n, npass, dbits, hist, hist_elems, err_dev, kept_dev, scratch_is_zero, result_alt);
+        return radix_sort_pairs_onesweep(s, keys, vals, n, npass, dbits, hist, hist_elems, err_dev, kept_dev, scratch_is_zero, result_alt, ride);
+    if (ride) { set_error("radix sort: an SH ride needs the single-launch passes (radix_takes_sh_ride)"); return -IBGS_ERR_INVALID; }
     const size_t hist_n = (size_t)nbins * nblocks;
     if (hist_elems < hist_n + 1 + 64) { set_error("radix scratch too small"); return -IBGS_ERR_ALLOC; }
     uint32_t* scan_scratch = hist + hist_n + 1 + 63;
