@@ -4,7 +4,7 @@ No torch.utils.cpp_extension here: under ROCm it would hipify the sources, and t
 torch types in its ABI anyway.  One hipcc invocation per translation unit (parallel), then a link.
 preprocess.hip is compiled with -ffp-contract=off so its integer outputs are bit-identical to the
 C oracle (see the header of that file); so is scan_sort.hip, whose depth sort launches also run the SH
-colours (sh_color.h).
+colours (sh_color.h); so is tsdf.hip, whose f32 operation order is part of the TSDF contract (its header, tests/tsdf_ref.py).
 """
 import os
 import subprocess
@@ -15,15 +15,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
+    "tsdf": ["-ffp-contract=off"],                 # the update / marching-cubes operation order is the contract (tests/tsdf_ref.py restates it)
     # no SLP packing: v_pk_*_f32 is not faster than two scalar VALU ops on gfx950 and costs v_mov / s_nop glue
     "render_fwd": ["-fno-slp-vectorize"],
     "render_bwd": ["-fno-slp-vectorize", "-fno-signed-zeros"],
 }
 ARCH = "gfx950"
+# headers that only one unit includes: hashed into that unit's profile stamp alone (tu_shas), rebuild triggers like the others
+UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")]}
 
 
 def _hipcc():
@@ -36,6 +39,7 @@ def _hipcc():
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "..", "include", "ibgs_rast.h"))
+    deps += [h for hs in UNIT_HEADERS.values() for h in hs]
     return max(os.path.getmtime(d) for d in deps)
 
 
@@ -63,7 +67,7 @@ def csrc_sha():
 
 # which translation unit a kernel of the step lives in (substring of its name -> TU): profile-derived numbers of a kernel stay valid while ITS
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
-KERNEL_TU = (("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+KERNEL_TU = (("tsdf_", "tsdf"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"))
@@ -88,6 +92,8 @@ def tu_shas():
     for name in SOURCES:
         h = hdr.copy()
         h.update(_code_only(open(os.path.join(CSRC, name + ".hip"), "r").read()).encode())
+        for u in UNIT_HEADERS.get(name, []):
+            h.update(_code_only(open(u, "r").read()).encode())
         h.update(" ".join(EXTRA.get(name, [])).encode())
         out[name] = h.hexdigest()[:12]
     return out
@@ -110,7 +116,8 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(OBJ, name + ".o")
-        if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_time):
+        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
+        if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
         cmd = [hipcc, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-c", src, "-o", obj] + EXTRA.get(name, [])
         if verbose:

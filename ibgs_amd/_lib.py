@@ -122,6 +122,32 @@ EXPORTS = ["ibgs_required_geom", "ibgs_required_img", "ibgs_required_binning", "
            "ibgs_depth_normal_forward", "ibgs_depth_normal_backward", "ibgs_activate_forward", "ibgs_activate_backward",
            "ibgs_last_error", "ibgs_version"]
 
+# every symbol include/ibgs_tsdf.h declares (a list of its own: EXPORTS mirrors ibgs_rast.h, tests/test_abi.py compares the two)
+TSDF_EXPORTS = ["ibgs_tsdf_sizeof_volume", "ibgs_tsdf_sizeof_view", "ibgs_tsdf_sizeof_mesh_scratch", "ibgs_tsdf_mc_table",
+                "ibgs_tsdf_integrate", "ibgs_tsdf_mesh_count", "ibgs_tsdf_mesh_emit"]
+TSDF_STATE_WORDS = 8
+TSDF_ALLOCATED, TSDF_FAILED, TSDF_IGNORED, TSDF_ACTIVE, TSDF_VERTICES, TSDF_FACES, TSDF_OVERRUN, TSDF_TABLE_FULL = range(8)
+TSDF_FLAG_NO_DEDUP = 1
+
+
+class TsdfVolume(ctypes.Structure):
+    _fields_ = [("voxel_length", ctypes.c_float), ("sdf_trunc", ctypes.c_float), ("capacity", ctypes.c_int32), ("slot_bits", ctypes.c_int32),
+                ("slot_key", ctypes.c_void_p), ("slot_block", ctypes.c_void_p), ("slot_mark", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("block_key", ctypes.c_void_p), ("tsdf", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("color", ctypes.c_void_p),
+                ("state", ctypes.c_void_p)]
+
+
+class TsdfView(ctypes.Structure):
+    _fields_ = [("W", ctypes.c_int32), ("H", ctypes.c_int32), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float), ("depth_trunc", ctypes.c_float), ("world_to_camera", ctypes.c_float * 12),
+                ("camera_to_world", ctypes.c_float * 12)]
+
+
+class TsdfMeshScratch(ctypes.Structure):
+    _fields_ = [("order", ctypes.c_void_p), ("rank", ctypes.c_void_p), ("vinfo", ctypes.c_void_p), ("vcount", ctypes.c_void_p),
+                ("fcount", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -220,6 +246,23 @@ def load():
     lib.ibgs_compact_apply.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
     lib.ibgs_knn_mean_dist2.restype = ctypes.c_int32
     lib.ibgs_knn_mean_dist2.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    for name in TSDF_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    for f in (lib.ibgs_tsdf_sizeof_volume, lib.ibgs_tsdf_sizeof_view, lib.ibgs_tsdf_sizeof_mesh_scratch):
+        f.restype = ctypes.c_size_t
+        f.argtypes = []
+    lib.ibgs_tsdf_mc_table.restype = ctypes.c_int32
+    lib.ibgs_tsdf_mc_table.argtypes = [ctypes.c_void_p]
+    lib.ibgs_tsdf_integrate.restype = ctypes.c_int32
+    lib.ibgs_tsdf_integrate.argtypes = [ctypes.c_void_p, ctypes.POINTER(TsdfVolume), ctypes.POINTER(TsdfView), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+    lib.ibgs_tsdf_mesh_count.restype = ctypes.c_int32
+    lib.ibgs_tsdf_mesh_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(TsdfVolume), ctypes.POINTER(TsdfMeshScratch)]
+    lib.ibgs_tsdf_mesh_emit.restype = ctypes.c_int32
+    lib.ibgs_tsdf_mesh_emit.argtypes = [ctypes.c_void_p, ctypes.POINTER(TsdfVolume), ctypes.POINTER(TsdfMeshScratch), ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4
+    if (lib.ibgs_tsdf_sizeof_volume() != ctypes.sizeof(TsdfVolume) or lib.ibgs_tsdf_sizeof_view() != ctypes.sizeof(TsdfView)
+            or lib.ibgs_tsdf_sizeof_mesh_scratch() != ctypes.sizeof(TsdfMeshScratch)):
+        raise RasterizerLibraryError("ctypes TSDF struct layout does not match libibgs_rast.so (stale build?)")
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t
     lib.ibgs_sizeof_backward_args.restype = ctypes.c_size_t
     if (lib.ibgs_sizeof_forward_args() != ctypes.sizeof(ForwardArgs)

@@ -66,3 +66,64 @@ def load_ply(path, max_sh_degree=None):
            "scaling": np.stack([col(n) for n in sorted([n for n, _ in props if n.startswith("scale_")], key=lambda s: int(s.split("_")[-1]))], 1),
            "rotation": np.stack([col(n) for n in sorted([n for n, _ in props if n.startswith("rot")], key=lambda s: int(s.split("_")[-1]))], 1)}
     return out
+
+
+MESH_VERTEX_PROPS = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def save_mesh(path, mesh):
+    """A triangle mesh (tsdf.TriangleMesh or anything with vertices / faces / colors / normals) as Open3D's write_triangle_mesh writes it with
+    write_vertex_colors=True, write_vertex_normals=True (render.py:361-364): binary little-endian, vertex `x y z nx ny nz` (float) `red green
+    blue` (uchar, round(255 clamp(c, 0, 1)), halves rounded up), face `list uchar int vertex_indices`."""
+    v = _np(mesh.vertices).astype("<f4").reshape(-1, 3)
+    n = _np(mesh.normals).astype("<f4").reshape(-1, 3)
+    c = np.floor(255.0 * np.clip(_np(mesh.colors).astype(np.float64).reshape(-1, 3), 0.0, 1.0) + 0.5).astype("u1")
+    f = _np(mesh.faces).astype("<i4").reshape(-1, 3)
+    rec = np.empty(v.shape[0], dtype=np.dtype(MESH_VERTEX_PROPS))
+    for i, k in enumerate("xyz"):
+        rec[k] = v[:, i]; rec["n" + k] = n[:, i]
+    for i, k in enumerate(("red", "green", "blue")):
+        rec[k] = c[:, i]
+    frec = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    frec["n"] = 3
+    frec["idx"] = f
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+    header += "".join("property %s %s\n" % ("float" if t == "<f4" else "uchar", k) for k, t in MESH_VERTEX_PROPS)
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def load_mesh(path):
+    """Reads what save_mesh writes -> dict of numpy arrays: vertices (V,3) f32, normals (V,3) f32, colors (V,3) uint8, faces (F,3) int32."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or not lines[1].startswith("format binary_little_endian"):
+        raise ValueError("load_mesh reads binary little-endian PLY files")
+    V = F = 0
+    props = []
+    for ln in lines[2:]:
+        t = ln.split()
+        if t[:2] == ["element", "vertex"]:
+            V = int(t[2])
+        elif t[:2] == ["element", "face"]:
+            F = int(t[2])
+        elif t[:1] == ["property"] and t[1] != "list":
+            props.append((t[2], {"float": "<f4", "uchar": "u1"}[t[1]]))
+        elif t[:2] == ["property", "list"] and t[2:4] != ["uchar", "int"]:
+            raise ValueError("load_mesh expects `list uchar int` faces")
+    rec = np.frombuffer(raw, dtype=np.dtype(props), count=V, offset=end)
+    frec = np.frombuffer(raw, dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), count=F, offset=end + rec.nbytes)
+    if F and not np.all(frec["n"] == 3):
+        raise ValueError("load_mesh reads triangle meshes only")
+    st = lambda ks: np.stack([np.asarray(rec[k]) for k in ks], 1)
+    return {"vertices": st("xyz").astype(np.float32), "normals": st(["nx", "ny", "nz"]).astype(np.float32),
+            "colors": st(["red", "green", "blue"]).astype(np.uint8), "faces": np.asarray(frec["idx"], np.int32).reshape(-1, 3)}

@@ -1,0 +1,185 @@
+"""TSDF fusion + marching cubes on the MI355X (ibgs_amd/tsdf.py): the surface scene (tests/scenes.surface_discs) rendered at 1080p from N views,
+fused at voxel sizes where the ground square spans ~1024 and ~2048 voxels, then meshed.  Output: profiles/tsdf.txt.
+
+    python tools/bench_tsdf.py [--views 16] [--gaussians 400000] [--kstats DIR]
+
+Per voxel size: ms per view of integrate (hipEvents around the call: allocation + update), with and without the allocation's LDS dedup;
+active blocks per view; the update's bytes (20 B read + 20 B written per voxel of an active block) over its time against 8 TB/s; extract_mesh ms, V, F.
+`--kstats DIR --kstats-only [--active N]`: the per-kernel times of a `rocprofv3 --kernel-trace -d DIR -- python tools/bench_tsdf.py --spans S
+--no-ab --no-restatement` run of this script, which split the call into allocation and update (and the update's bytes per second at N active blocks).  Last, the numpy restatement (tests/tsdf_ref.py) at 160 x 120, 24 views, for context (host time)."""
+import argparse
+import csv
+import glob
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ibgs_amd import _lib, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
+from tests import scenes  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+
+
+def render_views(n, W, H, P, dev):
+    g = scenes.surface_discs(P, seed=3)
+    pc = simple_scene.SimpleGaussians(g, sh_degree=2, device=dev)
+    cams = []
+    for i in range(n):
+        el = 25.0 if i % 2 == 0 else 55.0
+        cams.append(simple_scene.SimpleCamera(syn.make_camera(W, H, azimuth_deg=360.0 * i / n, elevation_deg=el, radius=4.0), uid=i, device=dev))
+    for c in cams:
+        c.nearest_id = []
+    scene = simple_scene.SimpleScene(cams, device=dev)
+    pipe, args = simple_scene.default_pipe(), simple_scene.default_args()
+    views = []
+    with torch.no_grad():
+        for c in cams:
+            out = renderer.render(c, pc, scene, pipe, args, torch.zeros(3, device=dev), learnt_normal=True, nb_src_frames=3, buffer_length=4,
+                                  render_geo=True, return_depth_normal=False)
+            views.append((c, tsdf.depth_for_fusion(out, c, max_depth=8.0), out["render"].detach().contiguous()))
+    torch.cuda.synchronize()
+    return views
+
+
+def kernel_split(kdir):
+    """{kernel: (calls, median us)} of the tsdf_ kernels from a rocprofv3 --kernel-trace output directory (rocpd database or CSV)."""
+    durs = {}
+    for f in glob.glob(os.path.join(kdir, "**", "*.db"), recursive=True):
+        import sqlite3
+        for name, ns in sqlite3.connect(f).execute("select name, duration from kernels where name like '%tsdf_%'"):
+            durs.setdefault(name.split("(")[0].split("::")[-1].split(" ")[-1], []).append(ns / 1e3)
+    for f in glob.glob(os.path.join(kdir, "**", "*kernel_trace.csv"), recursive=True):
+        for row in csv.DictReader(open(f)):
+            if "tsdf_" in row.get("Kernel_Name", ""):
+                name = row["Kernel_Name"].split("(")[0].split("::")[-1].split(" ")[-1]
+                durs.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    return {k: (len(v), float(np.median(v))) for k, v in durs.items()}
+
+
+def print_split(kdir, active=None):
+    ks = kernel_split(kdir)
+    print("\nkernel times from %s (rocprofv3 --kernel-trace; calls, median us):" % kdir)
+    for k, (n, us) in sorted(ks.items()):
+        print("  %-26s %6d calls  %9.2f us" % (k, n, us))
+    if active and "tsdf_integrate_kernel" in ks:
+        us = ks["tsdf_integrate_kernel"][1]
+        b = active * 512 * 40
+        print("  update at %d active blocks: %.1f MB in %.1f us = %.2f TB/s = %.0f %% of 8 TB/s" % (active, b / 1e6, us, b / (us * 1e-6) / 1e12,
+                                                                                                  100 * b / (us * 1e-6) / HBM_BYTES_PER_S))
+
+
+def bench_voxel(views, span, dedup_ab=True):
+    voxel = 2 * scenes.GROUND_HALF / span
+    vol = tsdf.TSDFVolume(voxel, 4 * voxel, block_capacity=1 << 21)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def run(dedup):
+        vol.reset()
+        ms, active = [], []
+        for c, d, col in views:
+            a, b = ev(), ev()
+            a.record()
+            vol.integrate_view(c, d, color=col) if dedup else vol.integrate(d, c.Fx, c.Fy, c.Cx, c.Cy, _pose(c), color=col, dedup=False)
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+            active.append(int(vol._state[_lib.TSDF_ACTIVE].item()))
+        return ms, active
+
+    run(True)          # warm-up: code objects, allocator
+    ms, active = run(True)
+    ms_nd, _ = run(False) if dedup_ab else (None, None)
+    ms2, _ = run(True)          # the dedup run again after the A/B one: the spread of the same measurement
+    vol.check()
+    blocks = vol.num_blocks()
+    a, b = ev(), ev()
+    vol.extract_mesh()          # warm-up
+    torch.cuda.synchronize()
+    a.record()
+    mesh = vol.extract_mesh()
+    b.record()
+    b.synchronize()
+    ext = a.elapsed_time(b)
+    assert vol.mesh_overruns() == 0
+    return {"span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
+            "V": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0])}
+
+
+def _pose(c):
+    pose = np.identity(4)
+    pose[:3, :3] = np.asarray(c.R, np.float64).T
+    pose[:3, 3] = np.asarray(c.T, np.float64)
+    return pose
+
+
+def restatement_time():
+    from tests import tsdf_ref as ref
+    W, H, F = 160, 120, 140.0
+    vol = ref.RefVolume(0.02, 0.08)
+    t0 = time.perf_counter()
+    for d in ref.fibonacci_directions(24):
+        M = ref.look_at(2.0 * d)
+        dep, col = ref.sphere_view(M, W, H, F, F, 80.0, 60.0, 0.5)
+        vol.integrate(dep, F, F, 80.0, 60.0, M, color=col)
+    t1 = time.perf_counter()
+    import ctypes
+    tab = (ctypes.c_int32 * 4096)()
+    _lib.load().ibgs_tsdf_mc_table(tab)
+    v, f, _, _ = ref.marching_cubes(vol.blocks(), 0.02, np.array(tab))
+    t2 = time.perf_counter()
+    return len(vol.coords), (t1 - t0) * 1e3 / 24, (t2 - t1) * 1e3, len(v), len(f)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--views", type=int, default=16)
+    ap.add_argument("--gaussians", type=int, default=400000)
+    ap.add_argument("--spans", default="1024,2048")
+    ap.add_argument("--kstats", default=None)
+    ap.add_argument("--no-restatement", action="store_true")
+    ap.add_argument("--no-ab", action="store_true", help="skip the run without the LDS dedup (under the profiler: one allocation variant per kernel line)")
+    ap.add_argument("--kstats-only", action="store_true", help="print the kernel split of --kstats DIR and exit (no GPU needed)")
+    ap.add_argument("--active", type=int, default=None, help="with --kstats-only: active blocks per view, for the update's bytes per second")
+    a = ap.parse_args()
+    if a.kstats_only:
+        print_split(a.kstats, a.active)
+        return
+    assert torch.cuda.is_available(), "bench_tsdf.py measures on the GPU"
+    dev = torch.device("cuda")
+    W, H = 1920, 1080
+    t0 = time.perf_counter()
+    views = render_views(a.views, W, H, a.gaussians, dev)
+    print("surface scene: %d Gaussians, %d views at %dx%d (two elevations), rendered in %.1f s; valid pixels per view %.0f"
+          % (a.gaussians, a.views, W, H, time.perf_counter() - t0, np.mean([float((d > 0).sum()) for _, d, _ in views])))
+    ks = bool(a.kstats)
+    for span in [int(s) for s in a.spans.split(",")]:
+        r = bench_voxel(views, span, dedup_ab=not a.no_ab)
+        act = np.array(r["active"], np.float64)
+        med = lambda x: float(np.median(x))
+        print("\n== ground square spans %d voxels: voxel %.6f, sdf_trunc %.6f" % (span, r["voxel"], 4 * r["voxel"]))
+        print("integrate per view (alloc + update, events): median %.3f ms (repeat %.3f ms), min %.3f, max %.3f"
+              % (med(r["ms"]), med(r["ms_again"]), min(r["ms"]), max(r["ms"])))
+        if r["ms_nodedup"]:
+            print("  without the LDS dedup (every pixel's blocks to the global hash): median %.3f ms" % med(r["ms_nodedup"]))
+        print("active blocks per view: median %.0f, min %.0f, max %.0f; allocated after %d views: %d" % (med(act), act.min(), act.max(), len(act), r["blocks"]))
+        upd_bytes = med(act) * 512 * 40
+        print("update traffic per view at the median: %.1f MB (40 B per voxel of an active block)" % (upd_bytes / 1e6))
+        print("  over the whole call's median time: %.2f TB/s = %.0f %% of 8 TB/s (a lower bound for the update kernel alone)"
+              % (upd_bytes / (med(r["ms"]) * 1e-3) / 1e12, 100 * upd_bytes / (med(r["ms"]) * 1e-3) / HBM_BYTES_PER_S))
+        print("extract_mesh (sort + count + scan + read-back + emit): %.3f ms, V %d, F %d" % (r["extract_ms"], r["V"], r["F"]))
+    if ks:
+        print_split(a.kstats)
+    if not a.no_restatement:
+        nb, ms_view, ms_mc, V, F = restatement_time()
+        print("\nnumpy restatement (host), sphere 160x120, 24 views, voxel 0.02: %d blocks, %.1f ms per view, marching cubes %.1f ms (V %d, F %d)"
+              % (nb, ms_view, ms_mc, V, F))
+
+
+if __name__ == "__main__":
+    main()
