@@ -148,6 +148,18 @@ class TsdfMeshScratch(ctypes.Structure):
                 ("fcount", ctypes.c_void_p)]
 
 
+# every symbol include/ibgs_mesh.h declares (tests/test_mesh_host.py compares the two)
+MESH_EXPORTS = ["ibgs_mesh_sizeof_mesh", "ibgs_mesh_required_scratch", "ibgs_mesh_cluster", "ibgs_mesh_filter_count", "ibgs_mesh_filter_emit"]
+MESH_STATE_WORDS = 8
+MESH_BAD_FACES, MESH_CLUSTERS, MESH_VERTICES_OUT, MESH_FACES_OUT, MESH_TABLE_FULL, MESH_OVERRUN = range(6)
+MESH_KEEP_VERTICES, MESH_KEEP_DEGENERATE = 1, 2
+
+
+class Mesh(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int32), ("F", ctypes.c_int32), ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p), ("scratch", ctypes.c_void_p),
+                ("scratch_bytes", ctypes.c_size_t), ("state", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -263,6 +275,22 @@ def load():
     if (lib.ibgs_tsdf_sizeof_volume() != ctypes.sizeof(TsdfVolume) or lib.ibgs_tsdf_sizeof_view() != ctypes.sizeof(TsdfView)
             or lib.ibgs_tsdf_sizeof_mesh_scratch() != ctypes.sizeof(TsdfMeshScratch)):
         raise RasterizerLibraryError("ctypes TSDF struct layout does not match libibgs_rast.so (stale build?)")
+    for name in MESH_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_mesh_sizeof_mesh.restype = ctypes.c_size_t
+    lib.ibgs_mesh_sizeof_mesh.argtypes = []
+    lib.ibgs_mesh_required_scratch.restype = ctypes.c_size_t
+    lib.ibgs_mesh_required_scratch.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    lib.ibgs_mesh_cluster.restype = ctypes.c_int32
+    lib.ibgs_mesh_cluster.argtypes = [ctypes.c_void_p, ctypes.POINTER(Mesh)] + [ctypes.c_void_p] * 3
+    lib.ibgs_mesh_filter_count.restype = ctypes.c_int32
+    lib.ibgs_mesh_filter_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(Mesh), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32]
+    lib.ibgs_mesh_filter_emit.restype = ctypes.c_int32
+    lib.ibgs_mesh_filter_emit.argtypes = [ctypes.c_void_p, ctypes.POINTER(Mesh), ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
+    if lib.ibgs_mesh_sizeof_mesh() != ctypes.sizeof(Mesh):
+        raise RasterizerLibraryError("ctypes mesh struct layout does not match libibgs_rast.so (stale build?)")
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t
     lib.ibgs_sizeof_backward_args.restype = ctypes.c_size_t
     if (lib.ibgs_sizeof_forward_args() != ctypes.sizeof(ForwardArgs)

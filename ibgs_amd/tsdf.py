@@ -5,7 +5,9 @@
     for view in views:
         out = renderer.render(view, ...)
         volume.integrate_view(view, depth_for_fusion(out, view, max_depth, use_depth_filter, bounds), color=out["render"])
-    ply.save_mesh(path, volume.extract_mesh())
+    raw = volume.extract_mesh()
+    ply.save_mesh(path, raw)                                                   # tsdf_fusion.ply
+    ply.save_mesh(path_post, mesh.post_process_mesh(raw, num_cluster))         # tsdf_fusion_post.ply (ibgs_amd/mesh.py: the largest clusters only)
 
 The contract (block layout, per-voxel update in its f32 operation order, marching cubes) is this project's own statement of the legacy Open3D volume:
 DESIGN.md section 11 and the header of ibgs_amd/csrc/tsdf.hip; tests/tsdf_ref.py restates it in numpy.

@@ -4,9 +4,12 @@ fused at voxel sizes where the ground square spans ~1024 and ~2048 voxels, then 
     python tools/bench_tsdf.py [--views 16] [--gaussians 400000] [--kstats DIR]
 
 Per voxel size: ms per view of integrate (hipEvents around the call: allocation + update), with and without the allocation's LDS dedup;
-active blocks per view; the update's bytes (20 B read + 20 B written per voxel of an active block) over its time against 8 TB/s; extract_mesh ms, V, F.
+active blocks per view; the update's bytes (20 B read + 20 B written per voxel of an active block) over its time against 8 TB/s; extract_mesh ms, V, F;
+then, on the extracted mesh, mesh.cluster_connected_triangles and mesh.post_process_mesh (ibgs_amd/mesh.py): ms, C, V', F'.
 `--kstats DIR --kstats-only [--active N]`: the per-kernel times of a `rocprofv3 --kernel-trace -d DIR -- python tools/bench_tsdf.py --spans S
---no-ab --no-restatement` run of this script, which split the call into allocation and update (and the update's bytes per second at N active blocks).  Last, the numpy restatement (tests/tsdf_ref.py) at 160 x 120, 24 views, for context (host time)."""
+--no-ab --no-restatement` run of this script, which split the call into allocation and update (and the update's bytes per second at N active blocks; with `--faces F`
+the edge kernel's edges per second).  Last, the numpy restatement (tests/tsdf_ref.py) at 160 x 120, 24 views, and, with `--mesh-restatement`, the
+numpy + scipy restatement of the post-processing (tests/mesh_ref.py) on the first span's mesh, for context (host time)."""
 import argparse
 import csv
 import glob
@@ -20,10 +23,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _lib, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
+from ibgs_amd import _lib, mesh as meshpp, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
 from tests import scenes  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
+KERNEL_FILTER = ("tsdf_", "mesh_", "scan_chunk_kernel", "scan_add_kernel")
 
 
 def render_views(n, W, H, P, dev):
@@ -48,21 +52,24 @@ def render_views(n, W, H, P, dev):
 
 
 def kernel_split(kdir):
-    """{kernel: (calls, median us)} of the tsdf_ kernels from a rocprofv3 --kernel-trace output directory (rocpd database or CSV)."""
+    """{kernel: (calls, median us)} of the tsdf_ and mesh_ kernels (and the scans the mesh unit launches) from a rocprofv3 --kernel-trace output directory
+    (rocpd database or CSV)."""
     durs = {}
+    mine = lambda name: any(k in name for k in KERNEL_FILTER)
     for f in glob.glob(os.path.join(kdir, "**", "*.db"), recursive=True):
         import sqlite3
-        for name, ns in sqlite3.connect(f).execute("select name, duration from kernels where name like '%tsdf_%'"):
-            durs.setdefault(name.split("(")[0].split("::")[-1].split(" ")[-1], []).append(ns / 1e3)
+        for name, ns in sqlite3.connect(f).execute("select name, duration from kernels"):
+            if mine(name):
+                durs.setdefault(name.split("(")[0].split("::")[-1].split(" ")[-1], []).append(ns / 1e3)
     for f in glob.glob(os.path.join(kdir, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if "tsdf_" in row.get("Kernel_Name", ""):
+            if mine(row.get("Kernel_Name", "")):
                 name = row["Kernel_Name"].split("(")[0].split("::")[-1].split(" ")[-1]
                 durs.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     return {k: (len(v), float(np.median(v))) for k, v in durs.items()}
 
 
-def print_split(kdir, active=None):
+def print_split(kdir, active=None, faces=None):
     ks = kernel_split(kdir)
     print("\nkernel times from %s (rocprofv3 --kernel-trace; calls, median us):" % kdir)
     for k, (n, us) in sorted(ks.items()):
@@ -72,9 +79,14 @@ def print_split(kdir, active=None):
         b = active * 512 * 40
         print("  update at %d active blocks: %.1f MB in %.1f us = %.2f TB/s = %.0f %% of 8 TB/s" % (active, b / 1e6, us, b / (us * 1e-6) / 1e12,
                                                                                                   100 * b / (us * 1e-6) / HBM_BYTES_PER_S))
+    if faces and "mesh_edge_union_kernel" in ks:
+        us = ks["mesh_edge_union_kernel"][1]
+        print("  edge table at %d faces: %.1f M edges (a load, a CAS for an edge's first arrival, an atomicMin, a union for the later ones) = %.2f G edges/s; each a random"
+              " 16-byte slot, one 64-byte line in and out = %.2f TB/s = %.0f %% of 8 TB/s" % (faces, 3 * faces / 1e6, 3 * faces / (us * 1e-6) / 1e9, 3 * faces * 128 / (us * 1e-6) / 1e12,
+                                                                                             100 * 3 * faces * 128 / (us * 1e-6) / HBM_BYTES_PER_S))
 
 
-def bench_voxel(views, span, dedup_ab=True):
+def bench_voxel(views, span, dedup_ab=True, keep_mesh=None):
     voxel = 2 * scenes.GROUND_HALF / span
     vol = tsdf.TSDFVolume(voxel, 4 * voxel, block_capacity=1 << 21)
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -107,7 +119,27 @@ def bench_voxel(views, span, dedup_ab=True):
     b.synchronize()
     ext = a.elapsed_time(b)
     assert vol.mesh_overruns() == 0
-    return {"span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
+
+    def timed(fn, reps=3):
+        out = fn()          # warm-up: code objects, allocator
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            a, b = ev(), ev()
+            a.record()
+            out = fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), out
+
+    cl_ms, cl = timed(lambda: meshpp.cluster_connected_triangles(mesh))
+    pp_ms, post = timed(lambda: meshpp.post_process_mesh(mesh, 1))
+    pp = {"cluster_ms": cl_ms, "post_ms": pp_ms, "C": int(cl.cluster_n_triangles.shape[0]), "largest": int(cl.cluster_n_triangles.max()),
+          "V2": int(post.vertices.shape[0]), "F2": int(post.faces.shape[0]), "scratch": _lib.load().ibgs_mesh_required_scratch(mesh.vertices.shape[0], mesh.faces.shape[0])}
+    if keep_mesh is not None:
+        keep_mesh.append((mesh, cl, post))
+    return {"pp": pp, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
             "V": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0])}
 
 
@@ -136,6 +168,20 @@ def restatement_time():
     return len(vol.coords), (t1 - t0) * 1e3 / 24, (t2 - t1) * 1e3, len(v), len(f)
 
 
+def mesh_restatement_time(mesh, cl, post):
+    """The host restatement of the post-processing (numpy + scipy, not Open3D) on a device mesh; its results must be the kernels'."""
+    from tests import mesh_ref
+    v, f = mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy()
+    t0 = time.perf_counter()
+    lab, counts, _ = mesh_ref.cluster(v, f)
+    t1 = time.perf_counter()
+    rows, fo = mesh_ref.post_process(f, len(v), lab, counts, 1)
+    t2 = time.perf_counter()
+    same = bool(np.array_equal(lab, cl.triangle_clusters.cpu().numpy()) and np.array_equal(fo, post.faces.cpu().numpy())
+                and v[rows].tobytes() == post.vertices.cpu().numpy().tobytes())
+    return t1 - t0, t2 - t1, same
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--views", type=int, default=16)
@@ -146,9 +192,11 @@ def main():
     ap.add_argument("--no-ab", action="store_true", help="skip the run without the LDS dedup (under the profiler: one allocation variant per kernel line)")
     ap.add_argument("--kstats-only", action="store_true", help="print the kernel split of --kstats DIR and exit (no GPU needed)")
     ap.add_argument("--active", type=int, default=None, help="with --kstats-only: active blocks per view, for the update's bytes per second")
+    ap.add_argument("--faces", type=int, default=None, help="with --kstats-only: faces of the mesh, for the edge kernel's edges per second")
+    ap.add_argument("--mesh-restatement", action="store_true", help="time tests/mesh_ref.py (numpy + scipy, host) on the first span's mesh and compare the results")
     a = ap.parse_args()
     if a.kstats_only:
-        print_split(a.kstats, a.active)
+        print_split(a.kstats, a.active, a.faces)
         return
     assert torch.cuda.is_available(), "bench_tsdf.py measures on the GPU"
     dev = torch.device("cuda")
@@ -158,8 +206,9 @@ def main():
     print("surface scene: %d Gaussians, %d views at %dx%d (two elevations), rendered in %.1f s; valid pixels per view %.0f"
           % (a.gaussians, a.views, W, H, time.perf_counter() - t0, np.mean([float((d > 0).sum()) for _, d, _ in views])))
     ks = bool(a.kstats)
+    first_mesh = []
     for span in [int(s) for s in a.spans.split(",")]:
-        r = bench_voxel(views, span, dedup_ab=not a.no_ab)
+        r = bench_voxel(views, span, dedup_ab=not a.no_ab, keep_mesh=first_mesh if a.mesh_restatement and not first_mesh else None)
         act = np.array(r["active"], np.float64)
         med = lambda x: float(np.median(x))
         print("\n== ground square spans %d voxels: voxel %.6f, sdf_trunc %.6f" % (span, r["voxel"], 4 * r["voxel"]))
@@ -173,8 +222,17 @@ def main():
         print("  over the whole call's median time: %.2f TB/s = %.0f %% of 8 TB/s (a lower bound for the update kernel alone)"
               % (upd_bytes / (med(r["ms"]) * 1e-3) / 1e12, 100 * upd_bytes / (med(r["ms"]) * 1e-3) / HBM_BYTES_PER_S))
         print("extract_mesh (sort + count + scan + read-back + emit): %.3f ms, V %d, F %d" % (r["extract_ms"], r["V"], r["F"]))
+        p = r["pp"]
+        print("cluster_connected_triangles (memsets + 4 kernels + scan + read-back): %.3f ms = %.2f x extract_mesh; C %d, largest cluster %d faces; scratch %.0f MB"
+              % (p["cluster_ms"], p["cluster_ms"] / r["extract_ms"], p["C"], p["largest"], p["scratch"] / 1e6))
+        print("post_process_mesh(mesh, 1) (clustering + top-k + mark + 2 scans + read-back + emit + read-back): %.3f ms = %.2f x extract_mesh; V' %d, F' %d"
+              % (p["post_ms"], p["post_ms"] / r["extract_ms"], p["V2"], p["F2"]))
     if ks:
         print_split(a.kstats)
+    if first_mesh:
+        t_cl, t_pp, same = mesh_restatement_time(*first_mesh[0])
+        print("\nnumpy + scipy restatement of the post-processing (host; not Open3D) on the %d-face mesh: clustering %.2f s, filter %.2f s; results equal to the kernels': %s"
+              % (first_mesh[0][0].faces.shape[0], t_cl, t_pp, same))
     if not a.no_restatement:
         nb, ms_view, ms_mc, V, F = restatement_time()
         print("\nnumpy restatement (host), sphere 160x120, 24 views, voxel 0.02: %d blocks, %.1f ms per view, marching cubes %.1f ms (V %d, F %d)"
