@@ -160,6 +160,16 @@ class Mesh(ctypes.Structure):
                 ("scratch_bytes", ctypes.c_size_t), ("state", ctypes.c_void_p)]
 
 
+# every symbol include/ibgs_mesh_eval.h declares (tests/test_mesh_eval_host.py compares the two)
+MESH_EVAL_EXPORTS = ["ibgs_meval_required_sample_scratch", "ibgs_meval_sample_count", "ibgs_meval_sample_emit", "ibgs_meval_keys", "ibgs_meval_required_tree",
+                     "ibgs_meval_build", "ibgs_meval_thin_rounds", "ibgs_meval_nearest", "ibgs_meval_reduce"]
+MEVAL_STATE_WORDS = 8
+MEVAL_BAD_FACES, MEVAL_SAMPLE_OVERFLOW, MEVAL_BAD_POINTS, MEVAL_OVERRUN, MEVAL_UNDECIDED = range(5)
+MEVAL_MAX_SIDE = 32768
+MEVAL_LEAF = 8
+MEVAL_THIN_UNDECIDED, MEVAL_THIN_KEPT, MEVAL_THIN_REMOVED = 0, 1, 2
+
+
 _lib = None
 
 
@@ -291,6 +301,22 @@ def load():
                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
     if lib.ibgs_mesh_sizeof_mesh() != ctypes.sizeof(Mesh):
         raise RasterizerLibraryError("ctypes mesh struct layout does not match libibgs_rast.so (stale build?)")
+    for name in MESH_EVAL_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    vp, i32, i64, f32, f64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+    for f in (lib.ibgs_meval_required_sample_scratch, lib.ibgs_meval_required_tree):
+        f.restype = sz
+        f.argtypes = [i64]
+    for f, args in ((lib.ibgs_meval_sample_count, [vp, i32, i32, vp, vp, f64, vp, sz, vp, vp]),
+                    (lib.ibgs_meval_sample_emit, [vp, i32, i32, vp, vp, f64, vp, sz, i64, vp, vp]),
+                    (lib.ibgs_meval_keys, [vp, i32, vp, vp, vp, vp]),
+                    (lib.ibgs_meval_build, [vp, i32, vp, vp, vp, vp, sz, vp]),
+                    (lib.ibgs_meval_thin_rounds, [vp, i32, vp, sz, f32, vp, i32, vp]),
+                    (lib.ibgs_meval_nearest, [vp, i32, vp, vp, i32, vp, sz, f32, vp, vp, vp]),
+                    (lib.ibgs_meval_reduce, [vp, i32, vp, f32, vp, vp])):
+        f.restype = i32
+        f.argtypes = args
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t
     lib.ibgs_sizeof_backward_args.restype = ctypes.c_size_t
     if (lib.ibgs_sizeof_forward_args() != ctypes.sizeof(ForwardArgs)

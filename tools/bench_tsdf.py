@@ -9,7 +9,11 @@ then, on the extracted mesh, mesh.cluster_connected_triangles and mesh.post_proc
 `--kstats DIR --kstats-only [--active N]`: the per-kernel times of a `rocprofv3 --kernel-trace -d DIR -- python tools/bench_tsdf.py --spans S
 --no-ab --no-restatement` run of this script, which split the call into allocation and update (and the update's bytes per second at N active blocks; with `--faces F`
 the edge kernel's edges per second).  Last, the numpy restatement (tests/tsdf_ref.py) at 160 x 120, 24 views, and, with `--mesh-restatement`, the
-numpy + scipy restatement of the post-processing (tests/mesh_ref.py) on the first span's mesh, for context (host time)."""
+numpy + scipy restatement of the post-processing (tests/mesh_ref.py) on the first span's mesh, for context (host time).
+`--mesh-eval`: every stage of ibgs_amd/mesh_eval.py on each span's post-processed mesh (density = a third of the voxel, so that the triangles are sampled,
+not only their vertices; max_dist = 100 densities, DTU's ratio; the
+ground truth is the thinned sampling of the raw mesh at 1.5 densities), and sklearn's kd-tree (the reference's engine, n_jobs = 16) on `--mesh-eval-host`
+points of the same clouds, a size the host finishes."""
 import argparse
 import csv
 import glob
@@ -23,11 +27,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _lib, mesh as meshpp, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
+from ibgs_amd import _lib, mesh as meshpp, mesh_eval, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
 from tests import scenes  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-KERNEL_FILTER = ("tsdf_", "mesh_", "scan_chunk_kernel", "scan_add_kernel")
+KERNEL_FILTER = ("tsdf_", "mesh_", "meval_", "scan_chunk_kernel", "scan_add_kernel")
 
 
 def render_views(n, W, H, P, dev):
@@ -86,7 +90,87 @@ def print_split(kdir, active=None, faces=None):
                                                                                              100 * 3 * faces * 128 / (us * 1e-6) / HBM_BYTES_PER_S))
 
 
-def bench_voxel(views, span, dedup_ab=True, keep_mesh=None):
+def bench_mesh_eval(raw, post, voxel, host_points):
+    """Stage times (hipEvents around the Python calls, median of 3 after a warm-up, read-backs included) and the host engine's on a subsample."""
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps=3):
+        out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            a, b = ev(), ev()
+            a.record()
+            out = fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), out
+
+    density = voxel / 3
+    max_dist = 100 * density
+    gt_cloud = mesh_eval.sample_surface(raw, 1.5 * density)
+    gt = gt_cloud[mesh_eval.downsample(gt_cloud, 1.5 * density)]
+    del gt_cloud
+    r = {"density": density, "F": int(post.faces.shape[0]), "gt": int(gt.shape[0])}
+    r["sample_ms"], cloud = timed(lambda: mesh_eval.sample_surface(post, density))
+    order = torch.randperm(cloud.shape[0], device=cloud.device)
+    r["thin_ms"], keep = timed(lambda: mesh_eval.downsample(cloud, density, order=order))
+    thinned = cloud[keep]
+    r["sampled"], r["thinned"] = int(cloud.shape[0]), int(thinned.shape[0])
+    state = torch.zeros(_lib.MEVAL_STATE_WORDS, dtype=torch.int32, device=cloud.device)
+    r["build_ms"], index = timed(lambda: mesh_eval._Index(gt, state))
+    r["d2s_ms"], _ = timed(lambda: index.query(thinned, max_dist))
+    r["nearest_s2d_ms"], _ = timed(lambda: mesh_eval.nearest(gt, thinned, max_dist))
+    r["chamfer_ms"], c = timed(lambda: mesh_eval.chamfer(thinned, gt, max_dist))
+    r["fscore_ms"], f = timed(lambda: mesh_eval.fscore(thinned, gt, 2 * density))
+    r["evaluate_ms"], e = timed(lambda: mesh_eval.evaluate_mesh(post, gt, density=density, max_dist=max_dist))
+    r["chamfer"], r["fscore"], r["evaluate"] = c, f, e
+    if host_points:
+        import sklearn.neighbors as skln
+        n = min(host_points, cloud.shape[0], gt.shape[0])
+        hc, hg = cloud[order[:n]].cpu().numpy().astype(np.float64), gt[:n].cpu().numpy().astype(np.float64)
+        t0 = time.perf_counter()
+        eng = skln.NearestNeighbors(n_neighbors=1, radius=density, algorithm="kd_tree", n_jobs=16).fit(hc)
+        lists = eng.radius_neighbors(hc, radius=density, return_distance=False)
+        t1 = time.perf_counter()
+        mask = np.ones(n, bool)
+        for i, near in enumerate(lists):
+            if mask[i]:
+                mask[near] = False
+                mask[i] = True
+        t2 = time.perf_counter()
+        eng.fit(hg)
+        eng.kneighbors(hc[mask], n_neighbors=1, return_distance=True)
+        t3 = time.perf_counter()
+        dev_thin, dkeep = timed(lambda: mesh_eval.downsample(cloud[order[:n]].contiguous(), density))
+        sub, gsub = cloud[order[:n]][dkeep].contiguous(), gt[:n].contiguous()
+        dev_nn, _ = timed(lambda: mesh_eval.nearest(sub, gsub, max_dist))
+        r["host"] = {"n": n, "radius_lists_s": t1 - t0, "loop_s": t2 - t1, "kneighbors_s": t3 - t2, "kept": int(mask.sum()), "dev_thin_ms": dev_thin,
+                     "dev_nearest_ms": dev_nn, "mask_diff": int((mask != dkeep.cpu().numpy()).sum())}
+    return r
+
+
+def print_mesh_eval(r):
+    print("mesh_eval on the post-processed mesh (F %d), density %.6f, max_dist = 100 densities, gt %d points:" % (r["F"], r["density"], r["gt"]))
+    print("  sample_surface (count + 64-bit scan + read-back + emit + read-back): %.3f ms -> %d points" % (r["sample_ms"], r["sampled"]))
+    print("  downsample, shuffled order (keys + torch.sort + hierarchy + rounds, one read-back per batch): %.3f ms -> %d kept" % (r["thin_ms"], r["thinned"]))
+    print("  hierarchy over gt (keys + torch.sort + gather + boxes): %.3f ms; pred -> gt queries on it (keys + torch.sort + walk): %.3f ms"
+          % (r["build_ms"], r["d2s_ms"]))
+    print("  nearest(gt, pred) (hierarchy + queries + read-back): %.3f ms" % r["nearest_s2d_ms"])
+    print("  chamfer (both directions + sums + one read-back): %.3f ms; fscore at 2 densities: %.3f ms" % (r["chamfer_ms"], r["fscore_ms"]))
+    print("  evaluate_mesh (all of the above from the mesh): %.3f ms" % r["evaluate_ms"])
+    c, f = r["chamfer"], r["fscore"]
+    print("  mean_d2s %.6g (%d) mean_s2d %.6g (%d) overall %.6g; precision %.4f recall %.4f F %.4f" % (c.mean_d2s, c.n_d2s, c.mean_s2d, c.n_s2d, c.overall,
+                                                                                                        f.precision, f.recall, f.fscore))
+    h = r.get("host")
+    if h:
+        print("  host, sklearn kd_tree with n_jobs = 16 on %d of the sampled points: radius lists %.2f s + the thinning loop %.2f s (%d kept; %d entries differ from the"
+              " device's mask, which decides in f32), kneighbors of the kept against %d gt points %.2f s; the device on the same inputs: downsample %.3f ms, nearest %.3f ms"
+              % (h["n"], h["radius_lists_s"], h["loop_s"], h["kept"], h["mask_diff"], h["n"], h["kneighbors_s"], h["dev_thin_ms"], h["dev_nearest_ms"]))
+
+
+def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None):
     voxel = 2 * scenes.GROUND_HALF / span
     vol = tsdf.TSDFVolume(voxel, 4 * voxel, block_capacity=1 << 21)
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -139,7 +223,8 @@ def bench_voxel(views, span, dedup_ab=True, keep_mesh=None):
           "V2": int(post.vertices.shape[0]), "F2": int(post.faces.shape[0]), "scratch": _lib.load().ibgs_mesh_required_scratch(mesh.vertices.shape[0], mesh.faces.shape[0])}
     if keep_mesh is not None:
         keep_mesh.append((mesh, cl, post))
-    return {"pp": pp, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
+    me = bench_mesh_eval(mesh, post, voxel, mesh_eval_host) if mesh_eval_host is not None else None
+    return {"pp": pp, "mesh_eval": me, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
             "V": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0])}
 
 
@@ -194,6 +279,8 @@ def main():
     ap.add_argument("--active", type=int, default=None, help="with --kstats-only: active blocks per view, for the update's bytes per second")
     ap.add_argument("--faces", type=int, default=None, help="with --kstats-only: faces of the mesh, for the edge kernel's edges per second")
     ap.add_argument("--mesh-restatement", action="store_true", help="time tests/mesh_ref.py (numpy + scipy, host) on the first span's mesh and compare the results")
+    ap.add_argument("--mesh-eval", action="store_true", help="time every stage of ibgs_amd/mesh_eval.py on each span's post-processed mesh")
+    ap.add_argument("--mesh-eval-host", type=int, default=300000, help="with --mesh-eval: points handed to sklearn's kd-tree on the host (0: skip)")
     a = ap.parse_args()
     if a.kstats_only:
         print_split(a.kstats, a.active, a.faces)
@@ -208,7 +295,8 @@ def main():
     ks = bool(a.kstats)
     first_mesh = []
     for span in [int(s) for s in a.spans.split(",")]:
-        r = bench_voxel(views, span, dedup_ab=not a.no_ab, keep_mesh=first_mesh if a.mesh_restatement and not first_mesh else None)
+        r = bench_voxel(views, span, dedup_ab=not a.no_ab, keep_mesh=first_mesh if a.mesh_restatement and not first_mesh else None,
+                        mesh_eval_host=a.mesh_eval_host if a.mesh_eval else None)
         act = np.array(r["active"], np.float64)
         med = lambda x: float(np.median(x))
         print("\n== ground square spans %d voxels: voxel %.6f, sdf_trunc %.6f" % (span, r["voxel"], 4 * r["voxel"]))
@@ -227,6 +315,8 @@ def main():
               % (p["cluster_ms"], p["cluster_ms"] / r["extract_ms"], p["C"], p["largest"], p["scratch"] / 1e6))
         print("post_process_mesh(mesh, 1) (clustering + top-k + mark + 2 scans + read-back + emit + read-back): %.3f ms = %.2f x extract_mesh; V' %d, F' %d"
               % (p["post_ms"], p["post_ms"] / r["extract_ms"], p["V2"], p["F2"]))
+        if r["mesh_eval"]:
+            print_mesh_eval(r["mesh_eval"])
     if ks:
         print_split(a.kstats)
     if first_mesh:
