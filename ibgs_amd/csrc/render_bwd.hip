@@ -181,7 +181,15 @@ __device__ __forceinline__ bool tile_is_risky(const uint32_t* __restrict__ tile_
 __device__ unsigned long long g_lanes_bwd[4];
 #endif
 constexpr int BWD_CHUNK = 16;          // 16 records per round: 0.75 KB + 4 KB of per-pixel constants <= 5 KB per wave = 8 waves per SIMD, every tile of a 1080p frame resident at once
-template <int PPL, bool ABS = true, bool RISK = false>          // ABS = false (IBGS_FLAG_NO_ABS_GRAD): the |.| moments of dL/dmean2D are not accumulated; RISK: the tile's list holds near-singular conics (see above)
+// LDSRED (the two tile-wave kernels): on a black background with float-atomic accumulation the fourth float of every s_gpix entry is dead (it is
+// -T_final (bg . g) = 0 and the BG0 forms never read it), so such a wave lays the 4 KB block out anew: dL/dC in 3 KB -- planes r, g, b per quadrant,
+// [q][channel][lane], read by ds_read2st64_b32 + ds_read_b32 off the byte offset 4 lane that the reducer's stores use as well: 6 LDS cycles per pixel,
+// conflict-free (the ds_read_b96 that the black-background loops narrow the float4 read to takes 8), no value live across quadrants -- and the last
+// 1 KB is the transposition buffer of wave_lds_reduce12 (wave_reduce.h), which sums the twelve moments in 22 VALU instructions instead of the butterfly's
+// 31 with nine 8-cycle swaps.  ((r, g) as one ds_read_b64 + b as a ds_read_b32 is 4 LDS cycles, but its offset 8 lane is one address register more than
+// the kernel has: 12 bytes per lane of scratch, reloaded per entry.)  The wave decides (bg is known to it, not to the host); any other background, and
+// the deterministic mode, whose bits the tests pin for both backgrounds alike, keep the float4 layout and the butterfly.
+template <int PPL, bool ABS = true, bool RISK = false, bool LDSRED = false>          // ABS = false (IBGS_FLAG_NO_ABS_GRAD): the |.| moments of dL/dmean2D are not accumulated; RISK: the tile's list holds near-singular conics (see above)
 __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const int tile, const int sub, float4 (&s_rec)[3][BWD_CHUNK],
                                                       float4 (*s_gpix)[WAVE] /* PPL rows: dL/dC (rgb), -T_final * (bg . dL/dC) */)
 {
@@ -190,8 +198,15 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
     constexpr int CHUNK = BWD_CHUNK;
 
     const int lane = threadIdx.x;
-    int col = reduce12_column(lane);
+    static_assert(!LDSRED || (PPL == 4 && !RISK), "the LDS reducer's buffer is the fourth float of four quadrants");
+    const bool bg0 = p.cam.bg[0] == 0.f && p.cam.bg[1] == 0.f && p.cam.bg[2] == 0.f;      // wave-uniform (scalar loads)
+    const bool lds_red = LDSRED && bg0 && p.slab == nullptr;                              // wave-uniform
+    float* const s_gpl = reinterpret_cast<float*>(&s_gpix[0][0]);                         // lds_red: [4][3][WAVE] planes r, g, b per quadrant, 3 KB
+    float* const s_red = s_gpl + 4 * 3 * WAVE;                                            //          the reducer's 1 KB
+    static_assert(!LDSRED || 4 * 3 * WAVE * sizeof(float) + LDS_REDUCE12_BYTES <= 4 * WAVE * sizeof(float4), "dL/dC and the reduce buffer share s_gpix's 4 KB");
+    int col = lds_red ? lds_reduce12_column(lane) : reduce12_column(lane);
     if (col >= 11) col = -1;
+    float* const acc_col = (p.slab ? p.slab : p.gacc) + col;          // the lane's column of whichever accumulator this launch writes: ONE pointer held across the loops (dereferenced where col >= 0 only)
     constexpr int IPT = 4 / PPL;
     const int quad0 = sub * PPL;
     const int W = p.cam.W, H = p.cam.H;
@@ -199,7 +214,6 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
     const size_t HW = (size_t)W * H;
 
     float T[PPL], S[PPL];
-    const bool bg0 = p.cam.bg[0] == 0.f && p.cam.bg[1] == 0.f && p.cam.bg[2] == 0.f;      // wave-uniform (scalar loads)
     uint32_t ncontrib[PPL];
     uint32_t nmax = 0;
     const float pxf0 = (float)(tx0 + (quad0 & 1) * 8 + (lane & 7)), pyf0 = (float)(ty0 + (quad0 >> 1) * 8 + (lane >> 3));
@@ -219,7 +233,8 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
         g.y = (inside && p.dL_dcolor) ? p.dL_dcolor[HW + pix] : 0.f;
         g.z = (inside && p.dL_dcolor) ? p.dL_dcolor[2 * HW + pix] : 0.f;
         g.w = -T_final * (p.cam.bg[0] * g.x + p.cam.bg[1] * g.y + p.cam.bg[2] * g.z);
-        s_gpix[q][lane] = g;
+        if (lds_red) { s_gpl[(q * 3 + 0) * WAVE + lane] = g.x; s_gpl[(q * 3 + 1) * WAVE + lane] = g.y; s_gpl[(q * 3 + 2) * WAVE + lane] = g.z; }
+        else s_gpix[q][lane] = g;
     }
     nmax = wave_max_u32(nmax);
     const uint32_t r0 = p.ranges[2 * tile], r1 = p.ranges[2 * tile + 1];
@@ -252,9 +267,11 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
             stable = stable && (ncm[q] == __builtin_amdgcn_ballot_w64((uint32_t)(top - 1) < ncontrib[q]));
         }
         __syncthreads();
-        auto chunk = [&](auto stable_tag, auto bg0_tag) {
+        auto chunk = [&](auto stable_tag, auto bg0_tag, auto lds_tag) {
             constexpr bool STABLE = decltype(stable_tag)::value;
             constexpr bool BG0 = decltype(bg0_tag)::value;          // black background: the -T_final (bg . g) / (1 - alpha) term is zero
+            constexpr bool LR = decltype(lds_tag)::value;           // lds_red: dL/dC in the plane layout, the moments summed through LDS
+            static_assert(!LR || (BG0 && LDSRED), "the plane layout has no room for the background term");
             for (int j = 0; j < count; j++) {
                 const uint32_t k = (uint32_t)(top - 1 - j);          // 0-based position in the tile list
                 const float4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j];
@@ -324,8 +341,8 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                             float v[12] = {rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rR, rG, rB, 0.f};
                             const float tot = wave_transpose_reduce12(v, lane);
                             if (col >= 0) {
-                                if (p.slab) p.slab[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS + col] = tot;
-                                else atomicAdd(p.gacc + (size_t)gid * GACC_FLOATS + col, tot);
+                                if (p.slab) acc_col[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS] = tot;
+                                else atomicAdd(acc_col + (size_t)gid * GACC_FLOATS, tot);
                             }
                         }
                         continue;
@@ -352,7 +369,9 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         const float rinv = __builtin_amdgcn_rcpf(1.f - alpha);
                         T[q] = T[q] * rinv;
                         const float w = alpha * T[q];
-                        const float4 gp = s_gpix[q][lane];
+                        float4 gp;
+                        if constexpr (LR) gp = make_float4(s_gpl[(q * 3 + 0) * WAVE + lane], s_gpl[(q * 3 + 1) * WAVE + lane], s_gpl[(q * 3 + 2) * WAVE + lane], 0.f);
+                        else gp = s_gpix[q][lane];
                         // S = (colour behind this Gaussian) . (pixel gradient): scalar form of the reference's per-channel
                         // accum_rec / last_color / last_alpha recurrence (backward.cu:665-669), folded into one fma:
                         // behind_k = alpha_k c_k + (1 - alpha_k) behind_{k+1} = behind_{k+1} + alpha_k (c_k - behind_{k+1})
@@ -387,17 +406,24 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                     }
                     v[2] = aX; v[3] = aY;          // (conic * d was formed with the scaled conic: preprocess_bwd multiplies these two sums by EXP2_UNSCALE)
                     v[8] = vR; v[9] = vG; v[10] = vB; v[11] = 0.f;
-                    const float tot = wave_transpose_reduce12(v, lane);
+                    float tot;
+                    if constexpr (LR) tot = wave_lds_reduce12(v, lane, s_red);
+                    else tot = wave_transpose_reduce12(v, lane);
                     const uint32_t id = __float_as_uint(q0.w);
                     if (col >= 0) {
-                        if (p.slab) p.slab[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS + col] = tot;      // wave-uniform choice
-                        else atomicAdd(p.gacc + (size_t)id * GACC_FLOATS + col, tot);
+                        if (!LR && p.slab) acc_col[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS] = tot;      // wave-uniform choice
+                        else atomicAdd(acc_col + (size_t)id * GACC_FLOATS, tot);
                     }
                 }
             }
         };
-        if (bg0) { if (stable) chunk(std::true_type{}, std::true_type{}); else chunk(std::false_type{}, std::true_type{}); }
-        else { if (stable) chunk(std::true_type{}, std::false_type{}); else chunk(std::false_type{}, std::false_type{}); }
+        if constexpr (LDSRED) {
+            if (lds_red) { if (stable) chunk(std::true_type{}, std::true_type{}, std::true_type{}); else chunk(std::false_type{}, std::true_type{}, std::true_type{}); }
+        }
+        if (!lds_red) {
+            if (bg0) { if (stable) chunk(std::true_type{}, std::true_type{}, std::false_type{}); else chunk(std::false_type{}, std::true_type{}, std::false_type{}); }
+            else { if (stable) chunk(std::true_type{}, std::false_type{}, std::false_type{}); else chunk(std::false_type{}, std::false_type{}, std::false_type{}); }
+        }
         __syncthreads();
         top -= count;
     }
@@ -818,8 +844,8 @@ __global__ void __launch_bounds__(64, 8) render_bwd_color_kernel(BwdParams p)
     if (p.order) { const uint32_t t = p.order[blockIdx.x]; tile = (int)(t & ~ORDER_SPLIT_BIT); have = t != 0xFFFFFFFFu; }
     else have = tile_map_item(p.tmap, blockIdx.x, p.cam.gx, p.cam.gy, 1, tile, sub);
     __shared__ float4 s_rec[3][BWD_CHUNK];
-    __shared__ float4 s_gpix[4][WAVE];
-    if (have && !tile_is_risky(p.tile_risky, tile)) render_bwd_color_body<4>(p, tile, sub, s_rec, s_gpix);
+    __shared__ __align__(16) unsigned char s_pix[4 * WAVE * sizeof(float4)];          // per-pixel constants; on a black background also the reduce buffer (render_bwd_color_body, LDSRED)
+    if (have && !tile_is_risky(p.tile_risky, tile)) render_bwd_color_body<4, true, false, true>(p, tile, sub, s_rec, reinterpret_cast<float4 (*)[WAVE]>(s_pix));
     IBGS_TRACE_END(g_trace_bwd);
 }
 __global__ void __launch_bounds__(64, 8) render_bwd_color_noabs_kernel(BwdParams p)          // IBGS_FLAG_NO_ABS_GRAD
@@ -829,8 +855,8 @@ __global__ void __launch_bounds__(64, 8) render_bwd_color_noabs_kernel(BwdParams
     if (p.order) { const uint32_t t = p.order[blockIdx.x]; tile = (int)(t & ~ORDER_SPLIT_BIT); have = t != 0xFFFFFFFFu; }
     else have = tile_map_item(p.tmap, blockIdx.x, p.cam.gx, p.cam.gy, 1, tile, sub);
     __shared__ float4 s_rec[3][BWD_CHUNK];
-    __shared__ float4 s_gpix[4][WAVE];
-    if (have && !tile_is_risky(p.tile_risky, tile)) render_bwd_color_body<4, false>(p, tile, sub, s_rec, s_gpix);
+    __shared__ __align__(16) unsigned char s_pix[4 * WAVE * sizeof(float4)];
+    if (have && !tile_is_risky(p.tile_risky, tile)) render_bwd_color_body<4, false, false, true>(p, tile, sub, s_rec, reinterpret_cast<float4 (*)[WAVE]>(s_pix));
 }
 // The flagged tiles (their list holds a near-singular conic), one wave per tile whatever the frame's size, in the order of the kernel it is launched beside
 // (p.order) or in tile order; every other workgroup leaves at once.  128 VGPRs: the reference-arithmetic block spills nothing.

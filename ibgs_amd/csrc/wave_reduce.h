@@ -1,4 +1,4 @@
-// wave64 butterfly transpose-reduce (shared by render_bwd.hip and tests/csrc/test_wave_reduce.hip)
+// wave64 transpose-reduces: the butterflies and the 12-value sum through LDS (shared by render_bwd.hip and tests/csrc/test_wave_reduce.hip, test_wave_lds_reduce.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +75,58 @@ __device__ __forceinline__ float wave_transpose_reduce12(float (&v)[12], int lan
     const float t1 = v[1] + IBGS_DPP(0.f, v[1], 0x128, 0xF);
     float A = (lane & 8) ? t1 : t0;
     float B = v[2] + IBGS_DPP(0.f, v[2], 0x128, 0xF);
+    // lane bits 2..0: 8 lanes -> 1
+    A += IBGS_DPP(0.f, A, 0x141 /* row_half_mirror */, 0xF); B += IBGS_DPP(0.f, B, 0x141, 0xF);
+    A += IBGS_DPP(0.f, A, 0xB1 /* quad_perm [1,0,3,2] */, 0xF); B += IBGS_DPP(0.f, B, 0xB1, 0xF);
+    A += IBGS_DPP(0.f, A, 0x4E /* quad_perm [2,3,0,1] */, 0xF); B += IBGS_DPP(0.f, B, 0x4E, 0xF);
+    return (lane & 15) == 1 ? B : A;
+}
+
+// ---- 12 values through LDS (colour backward on a black background) ------------------------------
+// The same sum with the transposition done by the LDS instead of the nine v_permlane swaps (8 cycles each).  `buf` is 1 KB of
+// LDS that belongs to this wave alone (the workgroup is one wave: no s_barrier anywhere).  Three rounds of four values:
+//   * every lane stores v[4r + c] to buf[c][lane], c = 0..3: four ds_write_b32 off one address register, each a contiguous
+//     256 B row -- conflict-free;
+//   * lane L reads buf[L >> 4][4 (L & 15) .. + 3] = the float4 at byte 16 L: ONE ds_read_b128 over a contiguous 1 KB --
+//     conflict-free in its four 16-lane groups -- and adds the four: each 16-lane row now holds column 4r + row in 16 partial sums.
+// A wave's DS operations execute in issue order, so round r + 1's stores cannot overtake round r's read and the three rounds
+// go out back to back: the wave waits for one LDS round trip, not three (counted lgkmcnt, placed by the compiler).  The fences
+// keep the compiler from moving a read over the stores around it; at wavefront scope they emit no instruction.
+// The three partial sums per lane are then folded over the row's 16 lanes as the butterfly's tail folds its three values.
+// 21 VALU instructions (the read offset, 9 adds, 9 DPP adds, 2 selects), 12 ds_write_b32 (hipcc pairs them: 6 ds_write2st64_b32), 3 ds_read_b128.
+// In: v[0..11] per lane.  Out: in the lanes where lds_reduce12_column(lane) = c >= 0, the sum over all 64 lanes of v[c].
+// The sum is associated differently from wave_transpose_reduce12's: equal up to rounding, not to the bit.
+constexpr int LDS_REDUCE12_BYTES = 1024;
+__device__ __forceinline__ int lds_reduce12_column(int lane)
+{
+    const int row = lane >> 4, l = lane & 15;
+    return l == 0 ? row : (l == 8 ? 4 + row : (l == 1 ? 8 + row : -1));
+}
+__device__ __forceinline__ float wave_lds_reduce12(const float (&v)[12], int lane, float* buf /* LDS, 16-byte aligned, LDS_REDUCE12_BYTES */)
+{
+    // The read's byte offset 16 L is formed here, once per call, and hidden from the optimiser: hoisted out of the caller's loop it is one more
+    // VGPR held beside 4 L (the stores' offset), and the colour kernels have none to spare (64 of 64: it was spilled, and reloaded per entry).
+    int rd;
+    asm volatile("v_lshlrev_b32 %0, 4, %1" : "=v"(rd) : "v"(lane));
+    float p[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) buf[c * 64 + lane] = v[4 * r + c];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const float4 t = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(buf) + rd);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        p[r] = (t.x + t.y) + (t.z + t.w);
+    }
+    // lane bit 3: lanes 0-7 of a row then carry column `row`, lanes 8-15 column 4 + row, all 16 column 8 + row
+    const float t0 = p[0] + IBGS_DPP(0.f, p[0], 0x128 /* row_ror:8 */, 0xF);
+    const float t1 = p[1] + IBGS_DPP(0.f, p[1], 0x128, 0xF);
+    float A = (lane & 8) ? t1 : t0;
+    float B = p[2] + IBGS_DPP(0.f, p[2], 0x128, 0xF);
     // lane bits 2..0: 8 lanes -> 1
     A += IBGS_DPP(0.f, A, 0x141 /* row_half_mirror */, 0xF); B += IBGS_DPP(0.f, B, 0x141, 0xF);
     A += IBGS_DPP(0.f, A, 0xB1 /* quad_perm [1,0,3,2] */, 0xF); B += IBGS_DPP(0.f, B, 0xB1, 0xF);

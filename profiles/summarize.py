@@ -8,6 +8,7 @@ Commands that produced the inputs (on the MI355X box, `cd /tmp && export TMPDIR=
   rocprofv3 --kernel-trace --pmc WRITE_SIZE  ... (own pass)
   rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE ...
   rocprofv3 --kernel-trace --pmc TCC_EA0_ATOMIC_sum TCC_HIT_sum TCC_MISS_sum ...
+  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VALU ... -d <out>/r08_lds   (round 8: counters only, no tracing in the run)
 HBM traffic follows MI355X_MICROARCH.md "HBM": FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE
 reports half the bytes of wide (16 B/lane) coalesced reads, so both the raw and the doubled figure are kept.
 """
@@ -57,7 +58,7 @@ def main():
             if "render_fwd" in r["Name"]:
                 out["render_fwd_avg_us_rocprof"] = float(r["AverageNs"]) / 1e3
     per_kernel = collections.defaultdict(lambda: collections.defaultdict(list))
-    for d in ("_fetch", "_write", "_sq", "_tcc", "_mfma"):
+    for d in ("_fetch", "_write", "_sq", "_tcc", "_mfma", "_lds"):
         cc = find(tag + d, "counter_collection.csv")
         if not cc:
             continue
