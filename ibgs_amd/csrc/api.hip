@@ -315,6 +315,23 @@ void ibgs_last_forward_stats(int64_t* out)
 void ibgs_debug_set_lookback_spins(uint32_t v) { radix_set_lookback_spins(v); }
 // tests only: whether a hinted forward's SH colours ride in the depth sort's launches (1, the default) or run in front of it (0)
 void ibgs_debug_set_sh_ride(int32_t on) { radix_set_sh_ride(on != 0); }
+// tests only (tests/test_gpu_scan_sort.py): the device-wide scan and radix sort of scan_sort.hip on the caller's own buffers, as every subsystem calls them --
+// the sort checks its own look-back flag (no err_dev), zeroes its scratch itself and carries no SH ride; set_onesweep: -1 = passes chosen by size (the
+// default), 0 = hist + scan + scatter passes, 1 = single-launch passes, returns the previous mode
+size_t ibgs_debug_scan_scratch_elems(size_t n) { return scan_scratch_elems(n); }
+int32_t ibgs_debug_scan_u32(void* stream, const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, size_t scratch_elems, int32_t with_total)
+{
+    return exclusive_scan_u32(reinterpret_cast<hipStream_t>(stream), in, out, n, scratch, scratch_elems, with_total != 0);
+}
+size_t ibgs_debug_sort_scratch_elems(size_t n) { return radix_hist_elems(n); }
+int32_t ibgs_debug_sort_pairs(void* stream, uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uint32_t* vals1, size_t n, int32_t nbits,
+                              uint32_t* scratch, size_t scratch_elems, uint32_t* kept_dev, uint32_t* result_alt)
+{
+    uint32_t* keys[2] = {keys0, keys1};
+    uint32_t* vals[2] = {vals0, vals1};
+    return radix_sort_pairs(reinterpret_cast<hipStream_t>(stream), keys, vals, n, nbits, scratch, scratch_elems, nullptr, kept_dev, false, result_alt, nullptr);
+}
+int32_t ibgs_debug_set_onesweep(int32_t mode) { return radix_set_onesweep(mode); }
 int32_t ibgs_check_async(void* stream, int32_t wait)
 {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

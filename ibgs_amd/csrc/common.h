@@ -454,7 +454,7 @@ size_t radix_zero_elems(size_t n, int nbits);      // leading words of `hist` th
 int exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch,
                        size_t scratch_elems, bool with_total);
 size_t scan_scratch_elems(size_t n);
-void radix_set_onesweep(bool on);       // default on; off = hist + scan + scatter launches per pass
+int radix_set_onesweep(int mode);       // -1 (default) = by size, 0 = hist + scan + scatter launches per pass, 1 = single-launch passes; returns the previous mode
 void radix_set_lookback_spins(uint32_t v);      // tests: how often a look-back sleeps on an unpublished word before its pass gives up (default 2^26)
 
 // per-tile lists + tile ranges from the depth-ordered Gaussians (two-level binning, binning.hip); `cap` = capacity of point_list

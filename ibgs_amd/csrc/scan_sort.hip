@@ -100,8 +100,8 @@ size_t scan_scratch_elems(size_t n)
     return total + 64;
 }
 
-int exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch,
-                       size_t scratch_elems, bool with_total)
+static int scan_level(hipStream_t s, const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch,
+                      size_t scratch_elems, bool with_total)
 {
     if (n == 0) {
         if (with_total) IBGS_HIP(hipMemsetAsync(out, 0, sizeof(uint32_t), s));
@@ -118,19 +118,29 @@ int exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out, size_t 
     hipLaunchKernelGGL(scan_chunk_kernel, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, s, in, out, n, sums, 0);
     IBGS_HIP(hipGetLastError());
     const size_t used = nblocks + 1 + 32;
-    int rc = exclusive_scan_u32(s, sums, sums, nblocks, scratch + used, scratch_elems > used ? scratch_elems - used : 0, true);
+    int rc = scan_level(s, sums, sums, nblocks, scratch + used, scratch_elems > used ? scratch_elems - used : 0, true);
     if (rc) return rc;
     hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, s, out, n, sums, nblocks, with_total ? 1 : 0);
     IBGS_HIP(hipGetLastError());
     return 0;
 }
 
+int exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch,
+                       size_t scratch_elems, bool with_total)
+{
+    // the whole recursion's scratch is checked HERE, against what scan_scratch_elems promises, before the first launch: a level that found its share
+    // too small would fail the call with `out` already half written
+    if (n > (size_t)SCAN_CHUNK && (!scratch || scratch_elems < scan_scratch_elems(n))) { set_error("scan scratch too small"); return -IBGS_ERR_ALLOC; }
+    return scan_level(s, in, out, n, scratch, scratch_elems, with_total);
+}
+
 // ------------------------------------------------------------------------------------------------
 // radix pass
 // ------------------------------------------------------------------------------------------------
 // (The classic hist + scan + scatter passes below stay generic over the key width and accept a device-side element count `n_dev`: round 1's
-// R-sized tile sort used both; since the two-level binning of round 2 only the depth sort of more than 2 M Gaussians, the knn codes and
-// the deterministic backward's ids come through here, all with 32-bit keys and a host-side count.)
+// R-sized tile sort used both; since the two-level binning of round 2 every caller passes 32-bit keys and a host-side count, and only sorts of
+// more than OS_AUTO_MAX_CHUNKS = 4096 chunks (16.7 M pairs) come through here: the deterministic backward's id sort at full-size frames
+// (R x ipt rows, 20-bit ids = three 7-bit passes), a depth sort or a knn cloud of that many points -- and whatever IBGS_RADIX_ONESWEEP=0 sends.)
 // Rank of an element among the elements of its wave that carry the same digit, in lane order (what makes the pass
 // stable), plus the running per-wave digit counter.  The set of lanes with the same digit ("match-any") comes from
 // the LDS: every lane ORs its lane bit into the digit's 64-bit slot, then reads the slot back -- LDS operations of
@@ -570,7 +580,7 @@ static int g_sh_ride = [] {
     return 1;
 }();
 void radix_set_sh_ride(bool on) { g_sh_ride = on ? 1 : 0; }
-void radix_set_onesweep(bool on) { g_use_onesweep = on ? 1 : 0; }
+int radix_set_onesweep(int mode) { const int prev = g_use_onesweep; g_use_onesweep = mode < 0 ? -1 : (mode ? 1 : 0); return prev; }
 void radix_set_lookback_spins(uint32_t v) { g_lookback_spins = v; }
 constexpr size_t OS_AUTO_MAX_CHUNKS = 4096;          // (round 1: 512 -- with 256-thread chunks the look-back of ~3000 workgroups lost against hist + scan + scatter; with 512-thread chunks and
                                                      // eight predecessors per look-back round trip the single-launch passes win up to at least 5 M keys: 0.178 vs 0.296 ms)

@@ -51,12 +51,16 @@ def _ref_cat(opt, ext):
     return out
 
 
-@pytest.mark.parametrize("N,n_app,keep_frac", [(5003, 700, 0.8), (4096, 0, 0.5), (777, 300, 1.0), (1000, 64, 0.0), (300001, 50000, 0.93)])
+# (2047 / 2048 / 2049 rows: the keep mask is scanned in chunks of 2048, one more scan level per factor of 2048 -- one chunk short of full, exactly full, the
+# first row of a second chunk; 2048 x 2048 + 1 rows: the first count that needs a third level, with a few narrow tensors -- the row offsets are what it tests)
+@pytest.mark.parametrize("N,n_app,keep_frac", [(5003, 700, 0.8), (4096, 0, 0.5), (777, 300, 1.0), (1000, 64, 0.0), (300001, 50000, 0.93),
+                                               (2047, 5, 0.5), (2048, 5, 0.5), (2049, 0, 0.5), (4194305, 3, 0.9)])
 def test_compact_append_is_boolean_indexing_plus_cat(N, n_app, keep_frac):
     g = torch.Generator(device="cuda").manual_seed(N)
-    ts = [torch.randn((N,) + s, device="cuda", generator=g) for s in SHAPES.values()] + [torch.randint(0, 1000, (N,), device="cuda", dtype=torch.int32, generator=g)]
+    shapes = list(SHAPES.values()) if N <= 1 << 20 else [(3,), (1,), (4,)]
+    ts = [torch.randn((N,) + s, device="cuda", generator=g) for s in shapes] + [torch.randint(0, 1000, (N,), device="cuda", dtype=torch.int32, generator=g)]
     mask = torch.rand(N, device="cuda", generator=g) < keep_frac
-    apps = [torch.randn((n_app,) + s, device="cuda", generator=g) for s in SHAPES.values()] + [None]
+    apps = [torch.randn((n_app,) + s, device="cuda", generator=g) for s in shapes] + [None]
     got = densify.compact_append(ts, mask, apps if n_app else None)
     for t, a, o in zip(ts, apps, got):
         kept = t[mask]

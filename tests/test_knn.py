@@ -36,6 +36,27 @@ def test_hip_distcuda2_matches_oracle():
     assert distCUDA2(torch.zeros(0, 3, device="cuda")).shape == (0,)
 
 
+def edge_clouds():
+    """Sizes around the code's units -- fewer points than neighbours, the 64-point wave, the 256-point box -- and a cloud whose Morton codes collapse."""
+    rng = np.random.default_rng(11)
+    out = {"%d points" % n: rng.uniform(-1.3, 1.3, (n, 3)).astype(np.float32) for n in (1, 2, 3, 4, 63, 64, 65, 255, 256, 257)}
+    # far from the origin, which the bounds include: every code falls into one or two cells, the Morton sort moves nothing, the pruning must stay exact
+    out["far cluster"] = (1000.0 + rng.uniform(-0.05, 0.05, (3000, 3))).astype(np.float32)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(edge_clouds()))
+def test_hip_distcuda2_edge_clouds_match_oracle(name):
+    from simple_knn._C import distCUDA2
+    pts = edge_clouds()[name]
+    got = distCUDA2(torch.as_tensor(pts, device="cuda")).cpu().numpy()
+    want = oracle.knn_mean_dist2(pts)
+    if len(pts) < 4:          # fewer than three neighbours: the missing ones count with the FLT_MAX sentinel, as in the oracle (and the reference's updateKBest)
+        assert not np.any(want < 1e37)
+    np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-12, err_msg=name)
+
+
 @pytest.mark.gpu
 def test_hip_distcuda2_large_cloud_against_kdtree():
     from scipy.spatial import cKDTree
