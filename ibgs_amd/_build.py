@@ -4,7 +4,8 @@ No torch.utils.cpp_extension here: under ROCm it would hipify the sources, and t
 torch types in its ABI anyway.  One hipcc invocation per translation unit (parallel), then a link.
 preprocess.hip is compiled with -ffp-contract=off so its integer outputs are bit-identical to the
 C oracle (see the header of that file); so is scan_sort.hip, whose depth sort launches also run the SH
-colours (sh_color.h); so is tsdf.hip, whose f32 operation order is part of the TSDF contract (its header, tests/tsdf_ref.py), and mesh.hip (the f64 triangle areas), and mesh_eval.hip (f64 sample positions, f32 squared distances).
+colours (sh_color.h); so is tsdf.hip, whose f32 operation order is part of the TSDF contract (its header, tests/tsdf_ref.py), and mesh.hip (the f64 triangle areas), and mesh_eval.hip (f64 sample positions, f32 squared distances),
+and registration.hip (the f64 transform, crop, voxel index and moment terms).
 """
 import os
 import subprocess
@@ -15,13 +16,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
     "tsdf": ["-ffp-contract=off"],                 # the update / marching-cubes operation order is the contract (tests/tsdf_ref.py restates it)
     "mesh": ["-ffp-contract=off"],                 # a triangle's f64 area is the restatement's to the bit (tests/mesh_ref.py); the rest is integers
     "mesh_eval": ["-ffp-contract=off"],            # the f64 sample positions and the f32 squared distances are the restatement's to the bit (tests/mesh_eval_ref.py)
+    "registration": ["-ffp-contract=off"],         # the f64 transform, crop crossings, voxel indices and moment terms are the restatement's to the bit (tests/registration_ref.py)
     # no SLP packing: v_pk_*_f32 is not faster than two scalar VALU ops on gfx950 and costs v_mov / s_nop glue
     "render_fwd": ["-fno-slp-vectorize"],
     "render_bwd": ["-fno-slp-vectorize", "-fno-signed-zeros"],
@@ -29,7 +31,8 @@ EXTRA = {
 ARCH = "gfx950"
 # headers that only one unit includes: hashed into that unit's profile stamp alone (tu_shas), rebuild triggers like the others
 UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "mesh": [os.path.join(HERE, "..", "include", "ibgs_mesh.h")],
-                "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")]}
+                "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")],
+                "registration": [os.path.join(HERE, "..", "include", "ibgs_registration.h")]}
 
 
 def _hipcc():
@@ -71,7 +74,7 @@ def csrc_sha():
 # which translation unit a kernel of the step lives in (substring of its name -> TU): profile-derived numbers of a kernel stay valid while ITS
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning)
-KERNEL_TU = (("meval_", "mesh_eval"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+KERNEL_TU = (("meval_", "mesh_eval"), ("pcreg_", "registration"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"))

@@ -169,6 +169,16 @@ MEVAL_MAX_SIDE = 32768
 MEVAL_LEAF = 8
 MEVAL_THIN_UNDECIDED, MEVAL_THIN_KEPT, MEVAL_THIN_REMOVED = 0, 1, 2
 
+# every symbol include/ibgs_registration.h declares (tests/test_registration_host.py compares the two)
+PCREG_EXPORTS = ["ibgs_pcreg_required_scratch", "ibgs_pcreg_bounds", "ibgs_pcreg_transform", "ibgs_pcreg_crop", "ibgs_pcreg_voxel_keys",
+                 "ibgs_pcreg_voxel_count", "ibgs_pcreg_voxel_emit", "ibgs_pcreg_moments"]
+PCREG_STATE_WORDS = 8
+PCREG_BAD_POINTS, PCREG_KEY_OVERFLOW, PCREG_BAD_INDEX, PCREG_OVERRUN = range(4)
+PCREG_MAX_POLYGON = 1024
+PCREG_MAX_INDEX = (1 << 21) - 1
+PCREG_LONG_SEGMENT = 64
+PCREG_MOMENTS = 18
+
 
 _lib = None
 
@@ -315,6 +325,20 @@ def load():
                     (lib.ibgs_meval_thin_rounds, [vp, i32, vp, sz, f32, vp, i32, vp]),
                     (lib.ibgs_meval_nearest, [vp, i32, vp, vp, i32, vp, sz, f32, vp, vp, vp]),
                     (lib.ibgs_meval_reduce, [vp, i32, vp, f32, vp, vp])):
+        f.restype = i32
+        f.argtypes = args
+    for name in PCREG_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_pcreg_required_scratch.restype = sz
+    lib.ibgs_pcreg_required_scratch.argtypes = [i64]
+    for f, args in ((lib.ibgs_pcreg_bounds, [vp, i32, vp, vp, sz, vp, vp]),
+                    (lib.ibgs_pcreg_transform, [vp, i32, vp, vp, vp, vp]),
+                    (lib.ibgs_pcreg_crop, [vp, i32, vp, vp, i32, f64, f64, i32, vp, vp, vp]),
+                    (lib.ibgs_pcreg_voxel_keys, [vp, i32, vp, vp, f64, vp, vp]),
+                    (lib.ibgs_pcreg_voxel_count, [vp, i32, vp, vp, sz, vp, vp]),
+                    (lib.ibgs_pcreg_voxel_emit, [vp, i32, vp, vp, vp, vp, sz, i32, vp, vp, vp]),
+                    (lib.ibgs_pcreg_moments, [vp, i32, vp, vp, i32, vp, vp, vp, sz, vp, vp])):
         f.restype = i32
         f.argtypes = args
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t

@@ -13,7 +13,10 @@ numpy + scipy restatement of the post-processing (tests/mesh_ref.py) on the firs
 `--mesh-eval`: every stage of ibgs_amd/mesh_eval.py on each span's post-processed mesh (density = a third of the voxel, so that the triangles are sampled,
 not only their vertices; max_dist = 100 densities, DTU's ratio; the
 ground truth is the thinned sampling of the raw mesh at 1.5 densities), and sklearn's kd-tree (the reference's engine, n_jobs = 16) on `--mesh-eval-host`
-points of the same clouds, a size the host finishes."""
+points of the same clouds, a size the host finishes.
+`--tnt`: ibgs_amd/registration.py on each span's post-processed mesh: its vertices, moved by the inverse of a planted similarity, against the thinned
+sampling of the raw mesh inside a polygon volume that cuts off one corner (tau = two thirds of the voxel): every stage's time, the time of one ICP
+iteration, the whole evaluate_tnt, and the numpy restatement (tests/registration_ref.py) on `--mesh-eval-host` points of the same clouds."""
 import argparse
 import csv
 import glob
@@ -27,11 +30,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _lib, mesh as meshpp, mesh_eval, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
+from ibgs_amd import _lib, mesh as meshpp, mesh_eval, registration, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
 from tests import scenes  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-KERNEL_FILTER = ("tsdf_", "mesh_", "meval_", "scan_chunk_kernel", "scan_add_kernel")
+KERNEL_FILTER = ("tsdf_", "mesh_", "meval_", "pcreg_", "scan_chunk_kernel", "scan_add_kernel")
 
 
 def render_views(n, W, H, P, dev):
@@ -170,7 +173,101 @@ def print_mesh_eval(r):
               % (h["n"], h["radius_lists_s"], h["loop_s"], h["kept"], h["mask_diff"], h["n"], h["kneighbors_s"], h["dev_thin_ms"], h["dev_nearest_ms"]))
 
 
-def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None):
+def bench_tnt(raw, post, voxel, host_points):
+    """Stage times of ibgs_amd/registration.py (hipEvents around the Python calls, median of 3 after a warm-up, read-backs included)."""
+    from tests import registration_ref as ref
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps=3):
+        out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            a, b = ev(), ev()
+            a.record()
+            out = fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), out
+
+    density = voxel / 3
+    tau = 2 * density
+    gt_cloud = mesh_eval.sample_surface(raw, 1.5 * density)
+    gt = gt_cloud[mesh_eval.downsample(gt_cloud, 1.5 * density)]
+    del gt_cloud
+    planted = ref.similarity(1.01, 1.0, (0.3, -0.5, 0.8), (3 * tau, -2 * tau, 2.5 * tau))
+    pred = registration.transform(post.vertices, np.linalg.inv(planted))          # evaluate_tnt has to find `planted`
+    lo, hi = gt.amin(0).cpu().numpy().astype(np.float64), gt.amax(0).cpu().numpy().astype(np.float64)
+    ext = hi - lo
+    x0, y0, x1, y1 = lo[0] - 0.01 * ext[0], lo[1] - 0.01 * ext[1], hi[0] + 0.01 * ext[0], hi[1] + 0.01 * ext[1]
+    poly = np.array([[x0, y0, 0], [x1, y0, 0], [x1, y0 + 0.7 * (y1 - y0), 0], [x0 + 0.7 * (x1 - x0), y1, 0], [x0, y1, 0]])
+    vol = registration.CropVolume("Z", lo[2] - 0.01 * ext[2], hi[2] + 0.01 * ext[2], poly)
+    r = {"tau": tau, "pred": int(pred.shape[0]), "gt": int(gt.shape[0])}
+    r["transform_ms"], moved = timed(lambda: registration.transform(pred, planted))
+    r["crop_ms"], m_gt = timed(lambda: registration.crop(gt, vol))
+    r["crop_T_ms"], m_pred = timed(lambda: registration.crop(pred, vol, planted))
+    gt_c, pred_c = gt[m_gt], moved[m_pred]
+    r["gt_cropped"], r["pred_cropped"] = int(gt_c.shape[0]), int(pred_c.shape[0])
+    r["voxel_tau_ms"], t1 = timed(lambda: registration.voxel_down_sample(gt_c, tau))
+    r["voxel_half_ms"], t2 = timed(lambda: registration.voxel_down_sample(gt_c, tau / 2))
+    r["gt_at_tau"], r["gt_at_half"] = int(t1.shape[0]), int(t2.shape[0])
+    s1 = registration.voxel_down_sample(pred_c, tau)
+    r["moments_ms"], _ = timed(lambda: registration.moments(s1, t1, 20 * tau))
+    icp1, _ = timed(lambda: registration.icp(s1, t1, 20 * tau, max_iter=1))
+    icp5, r5 = timed(lambda: registration.icp(s1, t1, 20 * tau, max_iter=5, rel_fitness=0.0, rel_rmse=0.0))
+    r["icp_iteration_ms"], r["icp_setup_ms"], r["icp_points"] = (icp5 - icp1) / 4, icp1 - (icp5 - icp1) / 4 * 2, (int(s1.shape[0]), int(t1.shape[0]))
+    r["evaluate_ms"], e = timed(lambda: registration.evaluate_tnt(pred, gt, np.identity(4), vol, tau))
+    r["evaluate"] = e
+    r["planted_err"] = float(np.abs(e["transformation"] - planted).max())
+    if host_points:
+        from tests import mesh_eval_ref
+        n = min(host_points, pred.shape[0], gt.shape[0])
+        g = torch.Generator(device="cpu")
+        g.manual_seed(0)
+        hp = pred[torch.randperm(pred.shape[0], generator=g)[:n].to(pred.device)].cpu().numpy()
+        hg = gt[torch.randperm(gt.shape[0], generator=g)[:n].to(gt.device)].cpu().numpy()
+        volume = (vol.axis, vol.axis_min, vol.axis_max, vol.polygon)
+        t0 = time.perf_counter()
+        q = ref.transform(hp, planted)
+        t1_ = time.perf_counter()
+        mask = ref.crop(hg, *volume)
+        t2_ = time.perf_counter()
+        thin = ref.voxel_down_sample(hg[mask], tau)[0].astype(np.float32)
+        t3_ = time.perf_counter()
+        _, idx = mesh_eval_ref.nearest(q, thin, 20 * tau)
+        t4_ = time.perf_counter()
+        ref.moments(q, thin, idx, ref.pivot_of(thin))
+        t5_ = time.perf_counter()
+        dq, dg = torch.as_tensor(hp, device=pred.device), torch.as_tensor(hg, device=pred.device)
+        dthin = registration.voxel_down_sample(dg[registration.crop(dg, vol)], tau)
+        dev_vox, _ = timed(lambda: registration.voxel_down_sample(dg, tau))
+        dev_mom, _ = timed(lambda: registration.moments(dq, dthin, 20 * tau, planted))
+        r["host"] = {"n": n, "transform_s": t1_ - t0, "crop_s": t2_ - t1_, "voxel_s": t3_ - t2_, "nearest_s": t4_ - t3_, "moments_s": t5_ - t4_,
+                     "dev_voxel_ms": dev_vox, "dev_moments_ms": dev_mom}
+    return r
+
+
+def print_tnt(r):
+    e = r["evaluate"]
+    print("registration on the post-processed mesh's %d vertices against %d gt points, tau %.6f (two thirds of the voxel), a 5-vertex volume:" % (r["pred"], r["gt"], r["tau"]))
+    print("  transform: %.3f ms; crop of gt: %.3f ms -> %d; crop of pred through the fused T: %.3f ms -> %d" % (r["transform_ms"], r["crop_ms"], r["gt_cropped"],
+                                                                                                      r["crop_T_ms"], r["pred_cropped"]))
+    print("  voxel_down_sample of the cropped gt (bounds + keys + torch.sort + heads + scan + read-back + means): at tau %.3f ms -> %d, at tau / 2 %.3f ms -> %d"
+          % (r["voxel_tau_ms"], r["gt_at_tau"], r["voxel_half_ms"], r["gt_at_half"]))
+    print("  one ICP evaluation from scratch (hierarchy + bounds read-back + transform + nearest + moments + read-back), %d -> %d points: %.3f ms" % (r["icp_points"] + (r["moments_ms"],)))
+    print("  one ICP iteration (transform + nearest + moments + read-back + 3 x 3 SVD on the host; from icp at 5 and at 1 updates): %.3f ms; the rest of an icp call: %.3f ms"
+          % (r["icp_iteration_ms"], r["icp_setup_ms"]))
+    print("  evaluate_tnt (three rounds + the final thinning + fscore): %.3f ms; iterations %s; precision %.4f recall %.4f F %.4f on %d / %d points; |T - planted| %.3g"
+          % (r["evaluate_ms"], [x.iterations for x in e["rounds"]], e["precision"], e["recall"], e["fscore"], e["n_pred"], e["n_gt"], r["planted_err"]))
+    h = r.get("host")
+    if h:
+        print("  numpy restatement (host) on %d points of each cloud: transform %.3f s, crop %.3f s, voxel_down_sample %.3f s, nearest (scipy kd-tree) %.3f s, moments %.3f s; "
+              "the device on the same inputs: voxel_down_sample %.3f ms, one ICP evaluation %.3f ms"
+              % (h["n"], h["transform_s"], h["crop_s"], h["voxel_s"], h["nearest_s"], h["moments_s"], h["dev_voxel_ms"], h["dev_moments_ms"]))
+
+
+def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None, tnt_host=None):
     voxel = 2 * scenes.GROUND_HALF / span
     vol = tsdf.TSDFVolume(voxel, 4 * voxel, block_capacity=1 << 21)
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -224,7 +321,8 @@ def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None)
     if keep_mesh is not None:
         keep_mesh.append((mesh, cl, post))
     me = bench_mesh_eval(mesh, post, voxel, mesh_eval_host) if mesh_eval_host is not None else None
-    return {"pp": pp, "mesh_eval": me, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
+    tnt = bench_tnt(mesh, post, voxel, tnt_host) if tnt_host is not None else None
+    return {"pp": pp, "mesh_eval": me, "tnt": tnt, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
             "V": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0])}
 
 
@@ -280,7 +378,8 @@ def main():
     ap.add_argument("--faces", type=int, default=None, help="with --kstats-only: faces of the mesh, for the edge kernel's edges per second")
     ap.add_argument("--mesh-restatement", action="store_true", help="time tests/mesh_ref.py (numpy + scipy, host) on the first span's mesh and compare the results")
     ap.add_argument("--mesh-eval", action="store_true", help="time every stage of ibgs_amd/mesh_eval.py on each span's post-processed mesh")
-    ap.add_argument("--mesh-eval-host", type=int, default=300000, help="with --mesh-eval: points handed to sklearn's kd-tree on the host (0: skip)")
+    ap.add_argument("--mesh-eval-host", type=int, default=300000, help="with --mesh-eval / --tnt: points handed to the host engine (sklearn's kd-tree / the numpy restatement; 0: skip)")
+    ap.add_argument("--tnt", action="store_true", help="time every stage of ibgs_amd/registration.py (evaluate_tnt) on each span's post-processed mesh")
     a = ap.parse_args()
     if a.kstats_only:
         print_split(a.kstats, a.active, a.faces)
@@ -296,7 +395,7 @@ def main():
     first_mesh = []
     for span in [int(s) for s in a.spans.split(",")]:
         r = bench_voxel(views, span, dedup_ab=not a.no_ab, keep_mesh=first_mesh if a.mesh_restatement and not first_mesh else None,
-                        mesh_eval_host=a.mesh_eval_host if a.mesh_eval else None)
+                        mesh_eval_host=a.mesh_eval_host if a.mesh_eval else None, tnt_host=a.mesh_eval_host if a.tnt else None)
         act = np.array(r["active"], np.float64)
         med = lambda x: float(np.median(x))
         print("\n== ground square spans %d voxels: voxel %.6f, sdf_trunc %.6f" % (span, r["voxel"], 4 * r["voxel"]))
@@ -317,6 +416,8 @@ def main():
               % (p["post_ms"], p["post_ms"] / r["extract_ms"], p["V2"], p["F2"]))
         if r["mesh_eval"]:
             print_mesh_eval(r["mesh_eval"])
+        if r["tnt"]:
+            print_tnt(r["tnt"])
     if ks:
         print_split(a.kstats)
     if first_mesh:
