@@ -62,18 +62,20 @@ class FusedAdam(torch.optim.Adam):
         if not (m3.is_cuda and m3.dtype == torch.float32 and m3.is_contiguous() and tuple(m3.shape) == (P, 3)):
             raise RuntimeError("FusedAdam.step: means3D must be the contiguous fp32 (P, 3) positions on the MI355X")
         group_of = {id(p): g for g in self.param_groups for p in g["params"]}
-        ds, k0s, Ks, k0 = [], [], [], 0
-        for p in params:
+        for p in params:          # every check before any state moves: a rejected step leaves the optimiser as it was
             if p.grad is not None:
                 raise RuntimeError("FusedAdam.step: an SH tensor has a dense .grad beside the factors (a loss term outside the rasterizer?): step without sh_factors")
             if id(p) not in group_of:
                 raise ValueError("FusedAdam.step: sh_params must be parameters of this optimiser")
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.dim() == 3 and int(p.shape[0]) == P and int(p.shape[2]) == 3):
                 raise RuntimeError("FusedAdam: SH tensors must be contiguous fp32 (P, K, 3) tensors on the MI355X")
+        ds, k0s, Ks, k0, stepped = [], [], [], 0, []
+        for p in params:
             group = group_of[id(p)]
             b1, b2 = group["betas"]
             st = self._state_of(p)
             st["step"] += 1
+            stepped.append(st)
             t = float(st["step"])
             m, v = st["exp_avg"], st["exp_avg_sq"]
             if not (m.is_contiguous() and v.is_contiguous()):
@@ -91,6 +93,8 @@ class FusedAdam(torch.optim.Adam):
             rc = lib.ibgs_adam_step_sh(torch.cuda.current_stream(dev).cuda_stream, P, degree, len(items), m3.data_ptr(), cams.data_ptr(), dcolor.data_ptr(), 3 * P,
                                        len(ds), ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(a0, ctypes.c_void_p), ctypes.cast(aK, ctypes.c_void_p))
         if rc < 0:
+            for st in stepped:          # nothing was launched
+                st["step"] -= 1
             raise RuntimeError("ibgs_adam_step_sh failed (%d): %s" % (rc, _lib.last_error()))
         return set(id(p) for p in params)
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from ibgs_amd.optim import FusedAdam
+from tests import adam_ref
 
 pytestmark = pytest.mark.gpu
 SHAPES = {"xyz": (5003, 3), "f_dc": (5003, 1, 3), "f_rest": (5003, 15, 3), "opacity": (5003, 1), "scaling": (5003, 3),
@@ -45,9 +46,16 @@ def test_survives_densification_style_state_surgery():
     """cat_tensors_to_optimizer / _prune_optimizer of the reference replace parameters and state tensors in place."""
     b = _groups(3)
     fus = FusedAdam(b, lr=0.0, eps=1e-15)
+    step = lambda st, g, t, lr: adam_ref.adam_step(st[0], np.full_like(st[0], g), st[1], st[2], t, lr, (0.9, 0.999), 1e-15, np.float32)
+    mirror = []                                                  # tests/adam_ref.py carried through the same surgery: [param, exp_avg, exp_avg_sq] per group
     for g in b:
+        p0 = g["params"][0].detach().cpu().numpy()
+        mirror.append(list(step([p0, np.zeros_like(p0), np.zeros_like(p0)], 1.0, 1, g["lr"])))
         g["params"][0].grad = torch.ones_like(g["params"][0])
     fus.step()
+    for st in mirror:
+        ext = np.zeros((100,) + st[0].shape[1:], np.float32)
+        st[:] = [np.ascontiguousarray(np.concatenate([a, ext], 0)[::3]) for a in st]
     for g in b:                                                  # append 100 rows (zeros state), then prune every third row
         old = g["params"][0]
         st = fus.state.pop(old)
@@ -63,6 +71,11 @@ def test_survives_densification_style_state_surgery():
         p = g["params"][0]
         assert torch.isfinite(p).all() and (p != p0).any() and float(fus.state[p]["step"]) == 2.0
         assert fus.state[p]["exp_avg"].is_contiguous() and fus.state[p]["exp_avg"].shape == p.shape
+    for g, st in zip(b, mirror):
+        p = g["params"][0]
+        for name, got, want in zip(("param", "exp_avg", "exp_avg_sq"), (p, fus.state[p]["exp_avg"], fus.state[p]["exp_avg_sq"]), step(st, 0.5, 2, g["lr"])):
+            got = got.detach().cpu().numpy()
+            assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32)), (g["name"], name, float(np.abs(got - want).max()))
 
 
 def test_rejects_what_it_does_not_cover():
