@@ -6,6 +6,8 @@ preprocess.hip is compiled with -ffp-contract=off so its integer outputs are bit
 C oracle (see the header of that file); so is scan_sort.hip, whose depth sort launches also run the SH
 colours (sh_color.h); so is tsdf.hip, whose f32 operation order is part of the TSDF contract (its header, tests/tsdf_ref.py), and mesh.hip (the f64 triangle areas), and mesh_eval.hip (f64 sample positions, f32 squared distances),
 and registration.hip (the f64 transform, crop, voxel index and moment terms).
+csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval and registration (no multiply-add in them: the flag above does not
+bear on them); ibgs_amd/_device.py is the Python side those five units share.
 """
 import os
 import subprocess

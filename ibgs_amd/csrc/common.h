@@ -242,6 +242,18 @@ void set_error(const char* fmt, ...);
         }                                                                                 \
     } while (0)
 
+// ---- a caller-owned arena (what a Carver carves) before anything is launched into it: not null, 128-byte aligned, `need` bytes long --------------
+// who: the entry point, what: the arena's name in the message ("scratch", "hierarchy").  need: the `total` of a carve from p (a carve only computes addresses).
+inline bool arena_ok(const char* who, const char* what, const void* p, size_t bytes, size_t need)
+{
+    if (!p) { set_error("%s: null %s", who, what); return false; }
+    if (reinterpret_cast<uintptr_t>(p) & 127) { set_error("%s: %s is not 128-byte aligned", who, what); return false; }
+    if (bytes < need) { set_error("%s: %s of %zu bytes, %zu needed", who, what, bytes, need); return false; }
+    return true;
+}
+// workgroups of `threads` that cover n items
+inline unsigned grid_for(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
 // ---- optional stage timing (api.hip; include/ibgs_rast.h: ibgs_timing_enable) ---------------------------------------------------
 struct StageTimer {   // RAII: records an event pair around one stage (or one kernel of it) when that stage is selected
     hipStream_t s; hipEvent_t a = nullptr, b = nullptr; int stage; bool on;

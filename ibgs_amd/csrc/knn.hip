@@ -7,6 +7,7 @@
 // and a surviving box is staged once into LDS (coalesced, from a Morton-sorted copy of the points) and consumed by all
 // 64 lanes as broadcast reads.  No host read-back (the reference copies min / max to the host, simple_knn.cu:195-198).
 #include "common.h"
+#include "block_ops.h"
 #include <cfloat>
 
 namespace ibgs {
@@ -36,19 +37,6 @@ struct KnnState {
     }
 };
 
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-
 // order-preserving float <-> uint map so that min / max can use integer atomics
 __device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
@@ -61,7 +49,7 @@ __global__ void __launch_bounds__(256) knn_bounds_kernel(uint32_t P, const float
         for (int a = 0; a < 3; a++) { const float v = pts[3 * i + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const float lo = wave_min(mn[a]), hi = wave_max(mx[a]);
+        const float lo = wave_reduce(mn[a], op_min()), hi = wave_reduce(mx[a], op_max());
         if ((threadIdx.x & 63) == 0) { atomicMin(&ob[a], f2ord(lo)); atomicMax(&ob[3 + a], f2ord(hi)); }
     }
 }
@@ -101,7 +89,7 @@ __global__ void __launch_bounds__(KNN_BOX) knn_boxes_kernel(uint32_t P, const fl
     if (valid) { const uint32_t id = order[i]; p[0] = pts[3 * id]; p[1] = pts[3 * id + 1]; p[2] = pts[3 * id + 2]; sorted[i] = make_float4(p[0], p[1], p[2], 0.f); }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const float lo = wave_min(valid ? p[a] : FLT_MAX), hi = wave_max(valid ? p[a] : -FLT_MAX);
+        const float lo = wave_reduce(valid ? p[a] : FLT_MAX, op_min()), hi = wave_reduce(valid ? p[a] : -FLT_MAX, op_max());
         if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6][a] = lo; s_mx[threadIdx.x >> 6][a] = hi; }
     }
     __syncthreads();
@@ -187,16 +175,16 @@ int32_t ibgs_knn_mean_dist2(void* stream, int32_t P, const float* points, float*
     uint32_t* ob = reinterpret_cast<uint32_t*>(k.bounds);
     const uint32_t zero_ord[6] = {0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u};
     IBGS_HIP(hipMemcpyAsync(ob, zero_ord, sizeof(zero_ord), hipMemcpyHostToDevice, s));
-    const unsigned nb = (unsigned)((P + 255) / 256);
+    const unsigned nb = grid_for((size_t)P, 256);
     hipLaunchKernelGGL(knn_bounds_kernel, dim3(nb < 1024u ? nb : 1024u), dim3(256), 0, s, (uint32_t)P, points, ob);
     hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, s, (uint32_t)P, points, ob, k.codes[0], k.idx[0]);
     IBGS_HIP(hipGetLastError());
     int rc = radix_sort_pairs(s, k.codes, k.idx, (size_t)P, 30, k.hist, k.hist_elems);
     if (rc) return rc;
-    const unsigned nboxes = (unsigned)((P + KNN_BOX - 1) / KNN_BOX);
+    const unsigned nboxes = grid_for((size_t)P, KNN_BOX);
     hipLaunchKernelGGL(knn_boxes_kernel, dim3(nboxes), dim3(KNN_BOX), 0, s, (uint32_t)P, points, k.idx[0],
                        reinterpret_cast<float4*>(k.sorted), reinterpret_cast<float4*>(k.boxes));
-    hipLaunchKernelGGL(knn_search_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, s, (uint32_t)P,
+    hipLaunchKernelGGL(knn_search_kernel, dim3(grid_for((size_t)P, 64)), dim3(64), 0, s, (uint32_t)P,
                        reinterpret_cast<const float4*>(k.sorted), reinterpret_cast<const float4*>(k.boxes), k.idx[0], out);
     IBGS_HIP(hipGetLastError());
     return 0;

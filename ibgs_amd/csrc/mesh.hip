@@ -30,6 +30,7 @@
 //   mesh_emit_faces_kernel / mesh_emit_vertices_kernel (one thread per float)
 // A face index outside [0, V) is never dereferenced: such triangles are counted in state[IBGS_MESH_BAD_FACES] and the caller fails the call.
 #include "common.h"
+#include "block_ops.h"
 #include "../../include/ibgs_mesh.h"
 
 namespace ibgs {
@@ -151,7 +152,7 @@ constexpr int LABEL_K = 16;          // chunks of 64 consecutive triangles per w
 // counts[lab] += n, areas[lab] += the wave's sum of a (one lane adds)
 __device__ __forceinline__ void mesh_label_add(int32_t* counts, double* areas, uint32_t lab, int n, double a)
 {
-    for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d, WAVE);
+    a = wave_reduce(a, op_add());
     if ((threadIdx.x & 63) == 0 && n > 0) { atomicAdd(counts + lab, n); atomicAdd(areas + lab, a); }
 }
 
@@ -264,13 +265,9 @@ static bool mesh_ok(const ibgs_mesh* m, const char* who, MeshScratch* sc)
     if (m->V < 0 || m->F < 0 || m->F >= (1 << 30)) { set_error("%s: V %d / F %d out of range (0 <= V < 2^31, 0 <= F < 2^30)", who, m->V, m->F); return false; }
     if ((m->V > 0 && !m->vertices) || (m->F > 0 && !m->faces) || !m->state || !m->scratch) { set_error("%s: null mesh array", who); return false; }
     size_t need = 0;
-    if (reinterpret_cast<uintptr_t>(m->scratch) & 127) { set_error("%s: scratch is not 128-byte aligned", who); return false; }
     *sc = MeshScratch::carve(static_cast<char*>(m->scratch), m->V, m->F, &need);
-    if (m->scratch_bytes < need) { set_error("%s: scratch of %zu bytes, %zu needed", who, m->scratch_bytes, need); return false; }
-    return true;
+    return arena_ok(who, "scratch", m->scratch, m->scratch_bytes, need);
 }
-
-static inline unsigned mesh_grid(size_t n) { return (unsigned)((n + MT - 1) / MT); }
 
 }  // namespace ibgs
 
@@ -301,7 +298,7 @@ int32_t ibgs_mesh_cluster(void* stream, const ibgs_mesh* mesh, int32_t* triangle
     if (!triangle_clusters || !cluster_n_triangles || !cluster_area) { set_error("mesh_cluster: null output"); return -IBGS_ERR_INVALID; }
     IBGS_HIP(hipMemsetAsync(cluster_n_triangles, 0, (size_t)F * sizeof(int32_t), s));
     IBGS_HIP(hipMemsetAsync(cluster_area, 0, (size_t)F * sizeof(double), s));
-    const unsigned g = mesh_grid(F);
+    const unsigned g = grid_for(F, MT);
     IBGS_HIP(hipMemsetAsync(sc.slots, 0xFF, sc.nslots * sizeof(MeshSlot), s));
     hipLaunchKernelGGL(mesh_init_kernel, dim3(g), dim3(MT), 0, s, sc.parent, F);
     IBGS_HIP(hipGetLastError());
@@ -311,7 +308,7 @@ int32_t ibgs_mesh_cluster(void* stream, const ibgs_mesh* mesh, int32_t* triangle
     IBGS_HIP(hipGetLastError());
     int rc = exclusive_scan_u32(s, sc.rootpos, sc.rootpos, F, sc.scan, sc.scan_elems, true);
     if (rc) return rc;
-    hipLaunchKernelGGL(mesh_label_kernel, dim3(mesh_grid(((size_t)F + LABEL_K - 1) / LABEL_K)), dim3(MT), 0, s, mesh->vertices, mesh->faces, V, F, sc.parent, sc.rootpos, triangle_clusters,
+    hipLaunchKernelGGL(mesh_label_kernel, dim3(grid_for(((size_t)F + LABEL_K - 1) / LABEL_K, MT)), dim3(MT), 0, s, mesh->vertices, mesh->faces, V, F, sc.parent, sc.rootpos, triangle_clusters,
                        cluster_n_triangles, cluster_area, mesh->state);
     IBGS_HIP(hipGetLastError());
     return 0;
@@ -327,7 +324,7 @@ int32_t ibgs_mesh_filter_count(void* stream, const ibgs_mesh* mesh, const int32_
     if (!(flags & IBGS_MESH_KEEP_VERTICES)) IBGS_HIP(hipMemsetAsync(sc.vpos, 0, ((size_t)V + 1) * sizeof(uint32_t), s));
     IBGS_HIP(hipMemsetAsync(sc.fpos + F, 0, sizeof(uint32_t), s));
     if (F > 0) {
-        hipLaunchKernelGGL(mesh_filter_mark_kernel, dim3(mesh_grid(F)), dim3(MT), 0, s, mesh->faces, V, F, triangle_clusters, keep_cluster, (uint32_t)C, flags,
+        hipLaunchKernelGGL(mesh_filter_mark_kernel, dim3(grid_for(F, MT)), dim3(MT), 0, s, mesh->faces, V, F, triangle_clusters, keep_cluster, (uint32_t)C, flags,
                            sc.vpos, sc.fpos, mesh->state);
         IBGS_HIP(hipGetLastError());
     }
@@ -362,12 +359,12 @@ int32_t ibgs_mesh_filter_emit(void* stream, const ibgs_mesh* mesh, uint32_t flag
         at.out[j] = reinterpret_cast<uint32_t*>(host_attr_out[j]);
     }
     if (F > 0 && F_out > 0) {
-        hipLaunchKernelGGL(mesh_emit_faces_kernel, dim3(mesh_grid(F)), dim3(MT), 0, s, mesh->faces, V, F, sc.vpos, sc.fpos, flags, (uint32_t)V_out, (uint32_t)F_out,
+        hipLaunchKernelGGL(mesh_emit_faces_kernel, dim3(grid_for(F, MT)), dim3(MT), 0, s, mesh->faces, V, F, sc.vpos, sc.fpos, flags, (uint32_t)V_out, (uint32_t)F_out,
                            faces_out, mesh->state);
         IBGS_HIP(hipGetLastError());
     }
     if (!keep_v && n_attr > 0 && V > 0 && V_out > 0) {
-        hipLaunchKernelGGL(mesh_emit_vertices_kernel, dim3(mesh_grid((size_t)V * 3)), dim3(MT), 0, s, at, V, sc.vpos, (uint32_t)V_out, mesh->state);
+        hipLaunchKernelGGL(mesh_emit_vertices_kernel, dim3(grid_for((size_t)V * 3, MT)), dim3(MT), 0, s, at, V, sc.vpos, (uint32_t)V_out, mesh->state);
         IBGS_HIP(hipGetLastError());
     }
     return 0;

@@ -38,6 +38,7 @@
 //   meval_reduce_kernel
 // Face indices outside [0, V) are never dereferenced; out-of-range conditions are counted in the state words and the caller fails the call.
 #include "common.h"
+#include "block_ops.h"
 #include "../../include/ibgs_mesh_eval.h"
 
 namespace ibgs {
@@ -185,23 +186,6 @@ __device__ __forceinline__ uint32_t tri_walk_wave(const TriSetup& s, uint64_t ro
     return n;
 }
 
-// exclusive scan of v over the workgroup's ET threads (64-bit); *total = the workgroup's sum
-__device__ __forceinline__ uint64_t meval_block_scan(uint64_t v, uint64_t* total, uint64_t* lds /* ET / 64 */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(inc, d, WAVE);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int k = 0; k < ET / 64; ++k) { const uint64_t x = lds[k]; if (k < wave) before += x; all += x; }
-    *total = all;
-    return before + inc - v;
-}
-
 template <bool EMIT>
 __device__ __forceinline__ void meval_sample_body(const float* __restrict__ vert, const int32_t* __restrict__ faces, uint32_t V, uint32_t F, double density,
                                                   uint32_t* __restrict__ counts, uint64_t* __restrict__ blocksum, uint64_t n_out, float* __restrict__ out,
@@ -218,7 +202,7 @@ __device__ __forceinline__ void meval_sample_body(const float* __restrict__ vert
     uint64_t row0 = 0;
     if (EMIT) {
         uint64_t total;
-        row0 = blocksum[blockIdx.x] + meval_block_scan(valid ? counts[t] : 0u, &total, lds);
+        row0 = blocksum[blockIdx.x] + block_exclusive_scan<ET>((uint64_t)(valid ? counts[t] : 0u), &total, lds);
     }
     uint32_t n = 0;
     if (s.n1 != 0 && !big) n = tri_walk_serial<EMIT>(s, row0, n_out, out, state);
@@ -234,7 +218,7 @@ __device__ __forceinline__ void meval_sample_body(const float* __restrict__ vert
     if (!EMIT) {
         if (valid) counts[t] = n;
         uint64_t total;
-        meval_block_scan(n, &total, lds);
+        block_exclusive_scan<ET>((uint64_t)n, &total, lds);
         if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
     }
 }
@@ -418,21 +402,16 @@ __global__ void __launch_bounds__(ET) meval_nearest_kernel(const float* __restri
 
 __global__ void __launch_bounds__(ET) meval_reduce_kernel(const float* __restrict__ dist, uint32_t Q, float threshold, double* sum, unsigned long long* count)
 {
-    __shared__ double s_sum[ET / 64];
-    __shared__ unsigned long long s_cnt[ET / 64];
     double a = 0.0;
     unsigned long long n = 0;
     for (size_t i = (size_t)blockIdx.x * ET + threadIdx.x; i < Q; i += (size_t)gridDim.x * ET) {
         const float d = dist[i];
         if (d < threshold) { a += (double)d; ++n; }
     }
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, WAVE); n += __shfl_xor(n, d, WAVE); }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = a; s_cnt[threadIdx.x >> 6] = n; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < ET / 64; ++w) { a += s_sum[w]; n += s_cnt[w]; }
-        if (n) { atomicAdd(sum, a); atomicAdd(count, n); }
-    }
+    double an[2] = {a, (double)n};          // (a workgroup's count is below 2^31: exact in f64, whatever the order)
+    const double v = block_reduce<ET, 2>(an, op_add());
+    if (threadIdx.x == 0 && v != 0.0) atomicAdd(sum, v);          // (a sum of 0 leaves *sum as it is: no count, or distances of 0 alone)
+    if (threadIdx.x == 1 && v != 0.0) atomicAdd(count, (unsigned long long)v);
 }
 
 struct SampleScratch {
@@ -441,7 +420,7 @@ struct SampleScratch {
     {
         SampleScratch s;
         Carver c(base);
-        s.nblocks = (uint32_t)(((size_t)F + ET - 1) / ET);
+        s.nblocks = grid_for((size_t)F, ET);
         s.counts = c.take<uint32_t>((size_t)F);
         s.blocksum = c.take<uint64_t>((size_t)s.nblocks + 1);
         if (total) *total = c.cur - reinterpret_cast<uintptr_t>(base) + 128;
@@ -449,30 +428,23 @@ struct SampleScratch {
     }
 };
 
-static inline unsigned meval_grid(size_t n) { return (unsigned)((n + ET - 1) / ET); }
-
 static bool sample_ok(const char* who, int32_t V, int32_t F, const float* vertices, const int32_t* faces, double density, const void* scratch, size_t scratch_bytes,
                       uint32_t* state, SampleScratch* sc)
 {
     if (V < 0 || F < 0 || F >= (1 << 30)) { set_error("%s: V %d / F %d out of range (0 <= V < 2^31, 0 <= F < 2^30)", who, V, F); return false; }
     if (!(density > 0.0) || !(density < 1e300)) { set_error("%s: density must be positive and finite", who); return false; }
     if ((V > 0 && !vertices) || (F > 0 && !faces) || !state || !scratch) { set_error("%s: null array", who); return false; }
-    if (reinterpret_cast<uintptr_t>(scratch) & 127) { set_error("%s: scratch is not 128-byte aligned", who); return false; }
     size_t need = 0;
     *sc = SampleScratch::carve(static_cast<char*>(const_cast<void*>(scratch)), F, &need);
-    if (scratch_bytes < need) { set_error("%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, need); return false; }
-    return true;
+    return arena_ok(who, "scratch", scratch, scratch_bytes, need);
 }
 
 static bool tree_ok(const char* who, int32_t N, const void* tree, size_t tree_bytes, MevalTree* t)
 {
     if (N <= 0) { set_error("%s: N %d out of range (0 < N < 2^31)", who, N); return false; }
-    if (!tree) { set_error("%s: null hierarchy", who); return false; }
-    if (reinterpret_cast<uintptr_t>(tree) & 127) { set_error("%s: hierarchy is not 128-byte aligned", who); return false; }
     size_t need = 0;
     *t = meval_tree_carve(static_cast<char*>(const_cast<void*>(tree)), N, &need);
-    if (tree_bytes < need) { set_error("%s: hierarchy of %zu bytes, %zu needed", who, tree_bytes, need); return false; }
-    return true;
+    return arena_ok(who, "hierarchy", tree, tree_bytes, need);
 }
 
 }  // namespace ibgs
@@ -523,7 +495,7 @@ int32_t ibgs_meval_keys(void* stream, int32_t N, const float* points, const floa
     if (N < 0) { set_error("meval_keys: N %d out of range", N); return -IBGS_ERR_INVALID; }
     if (N == 0) return 0;
     if (!points || !bounds || !keys || !state) { set_error("meval_keys: null array"); return -IBGS_ERR_INVALID; }
-    hipLaunchKernelGGL(meval_keys_kernel, dim3(meval_grid((size_t)N)), dim3(ET), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, bounds, keys, state);
+    hipLaunchKernelGGL(meval_keys_kernel, dim3(grid_for((size_t)N, ET)), dim3(ET), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, bounds, keys, state);
     IBGS_HIP(hipGetLastError());
     return 0;
 }
@@ -542,12 +514,12 @@ int32_t ibgs_meval_build(void* stream, int32_t N, const float* points, const int
     if (!tree_ok("meval_build", N, tree, tree_bytes, &t)) return -IBGS_ERR_INVALID;
     if (!points || !order || !state) { set_error("meval_build: null array"); return -IBGS_ERR_INVALID; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(meval_gather_kernel, dim3(meval_grid((size_t)N)), dim3(ET), 0, s, points, (uint32_t)N, order, tag, const_cast<float4*>(t.pts), state);
+    hipLaunchKernelGGL(meval_gather_kernel, dim3(grid_for((size_t)N, ET)), dim3(ET), 0, s, points, (uint32_t)N, order, tag, const_cast<float4*>(t.pts), state);
     IBGS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(meval_leaf_box_kernel, dim3(meval_grid(t.n[0])), dim3(ET), 0, s, t.pts, t.N, const_cast<float4*>(t.box[0]), t.n[0]);
+    hipLaunchKernelGGL(meval_leaf_box_kernel, dim3(grid_for(t.n[0], ET)), dim3(ET), 0, s, t.pts, t.N, const_cast<float4*>(t.box[0]), t.n[0]);
     IBGS_HIP(hipGetLastError());
     for (int l = 1; l < t.L; ++l) {
-        hipLaunchKernelGGL(meval_box_kernel, dim3(meval_grid(t.n[l])), dim3(ET), 0, s, t.box[l - 1], t.n[l - 1], const_cast<float4*>(t.box[l]), t.n[l]);
+        hipLaunchKernelGGL(meval_box_kernel, dim3(grid_for(t.n[l], ET)), dim3(ET), 0, s, t.box[l - 1], t.n[l - 1], const_cast<float4*>(t.box[l]), t.n[l]);
         IBGS_HIP(hipGetLastError());
     }
     return 0;
@@ -562,7 +534,7 @@ int32_t ibgs_meval_thin_rounds(void* stream, int32_t N, const void* tree, size_t
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     IBGS_HIP(hipMemsetAsync(state + IBGS_MEVAL_UNDECIDED, 0, sizeof(uint32_t), s));
     for (int r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(meval_thin_round_kernel, dim3(meval_grid((size_t)N)), dim3(ET), 0, s, t, radius, status,
+        hipLaunchKernelGGL(meval_thin_round_kernel, dim3(grid_for((size_t)N, ET)), dim3(ET), 0, s, t, radius, status,
                            r == rounds - 1 ? state + IBGS_MEVAL_UNDECIDED : nullptr);
         IBGS_HIP(hipGetLastError());
     }
@@ -578,7 +550,7 @@ int32_t ibgs_meval_nearest(void* stream, int32_t Q, const float* query, const in
     if (!(max_dist >= 0.0f) || !(max_dist < 1e18f)) { set_error("meval_nearest: max_dist must be finite and >= 0"); return -IBGS_ERR_INVALID; }
     if (Q == 0) return 0;
     if (!query || !dist || !index || !state) { set_error("meval_nearest: null array"); return -IBGS_ERR_INVALID; }
-    hipLaunchKernelGGL(meval_nearest_kernel, dim3(meval_grid((size_t)Q)), dim3(ET), 0, reinterpret_cast<hipStream_t>(stream), query, (uint32_t)Q, qorder, t, max_dist,
+    hipLaunchKernelGGL(meval_nearest_kernel, dim3(grid_for((size_t)Q, ET)), dim3(ET), 0, reinterpret_cast<hipStream_t>(stream), query, (uint32_t)Q, qorder, t, max_dist,
                        dist, index, state);
     IBGS_HIP(hipGetLastError());
     return 0;
@@ -589,7 +561,7 @@ int32_t ibgs_meval_reduce(void* stream, int32_t Q, const float* dist, float thre
     if (Q < 0) { set_error("meval_reduce: Q %d out of range", Q); return -IBGS_ERR_INVALID; }
     if (Q == 0) return 0;
     if (!dist || !sum || !count) { set_error("meval_reduce: null array"); return -IBGS_ERR_INVALID; }
-    const unsigned g = meval_grid((size_t)Q);
+    const unsigned g = grid_for((size_t)Q, ET);
     hipLaunchKernelGGL(meval_reduce_kernel, dim3(g < 2048u ? g : 2048u), dim3(ET), 0, reinterpret_cast<hipStream_t>(stream), dist, (uint32_t)Q, threshold, sum,
                        reinterpret_cast<unsigned long long*>(count));
     IBGS_HIP(hipGetLastError());

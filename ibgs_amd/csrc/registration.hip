@@ -17,7 +17,7 @@
 //              order; so do the kernels for voxels of up to 64 members (the sort is stable); larger voxels are summed by a wave in a fixed tree order.
 //   moments    over the queries with a correspondence, s = f32 query, t = its f32 target, pivot c (f64): n, sum(s - c), sum(t - c), sum (s - c)(t - c)^T,
 //              sum |s - c|^2 with |.|^2 = (x x + y y) + z z, sum d^2 with d = s - t widened, d^2 = (dx dx + dy dy) + dz dz.  Per-workgroup partials, then one
-//              workgroup; no atomics: 18 words that are the same bits on every run.
+//              workgroup (block_reduce: block_ops.h states the order of the additions); no atomics: 18 words that are the same bits on every run.
 //
 // KERNELS
 //   pcreg_bounds_kernel / pcreg_bounds_final_kernel      per-axis min / max: workgroup partials, then one workgroup
@@ -30,6 +30,7 @@
 //   pcreg_moments_kernel / pcreg_moments_final_kernel
 // Indices outside their range are never dereferenced; out-of-range conditions are counted in the state words and the caller fails the call.
 #include "common.h"
+#include "block_ops.h"
 #include "../../include/ibgs_registration.h"
 
 namespace ibgs {
@@ -73,42 +74,31 @@ __device__ __forceinline__ void pcreg_apply(const PcregT& T, float& x, float& y,
 }
 
 // ---- bounds --------------------------------------------------------------------------------------------------------------------------------------
-// the workgroup's min / max of (lo[3], hi[3]) to dst[0..6)
-__device__ __forceinline__ void pcreg_block_minmax(float* lo, float* hi, float* dst)
-{
-    __shared__ float s_mm[RT / 64][6];
-    for (int d = 32; d >= 1; d >>= 1)
-        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], d, WAVE)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d, WAVE)); }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 3; ++k) { s_mm[threadIdx.x >> 6][k] = lo[k]; s_mm[threadIdx.x >> 6][3 + k] = hi[k]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = s_mm[0][threadIdx.x];
-        for (int w = 1; w < RT / 64; ++w) v = threadIdx.x < 3 ? fminf(v, s_mm[w][threadIdx.x]) : fmaxf(v, s_mm[w][threadIdx.x]);
-        dst[threadIdx.x] = v;
-    }
-}
+// per-axis min (components 0..2) and max (3..5): the op of block_reduce
+struct PcregMinMax { __device__ __forceinline__ float operator()(float x, float y, int k) const { return k < 3 ? fminf(x, y) : fmaxf(x, y); } };
 
 __global__ void __launch_bounds__(RT) pcreg_bounds_kernel(const float* __restrict__ pts, uint32_t N, float* __restrict__ part, uint32_t* state)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    const float inf = __builtin_inff();
+    float b[6] = {inf, inf, inf, -inf, -inf, -inf};
     uint32_t bad = 0;
     for (size_t i = (size_t)blockIdx.x * RT + threadIdx.x; i < N; i += (size_t)gridDim.x * RT) {
         const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
         if (!(isfinite(x) && isfinite(y) && isfinite(z))) { ++bad; continue; }
-        lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
-        hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
+        b[0] = fminf(b[0], x); b[1] = fminf(b[1], y); b[2] = fminf(b[2], z);
+        b[3] = fmaxf(b[3], x); b[4] = fmaxf(b[4], y); b[5] = fmaxf(b[5], z);
     }
     if (bad) atomicAdd(state + IBGS_PCREG_BAD_POINTS, bad);
-    pcreg_block_minmax(lo, hi, part + (size_t)blockIdx.x * 6);
+    block_reduce<RT, 6>(b, part + (size_t)blockIdx.x * 6, PcregMinMax());
 }
 
 __global__ void __launch_bounds__(RT) pcreg_bounds_final_kernel(const float* __restrict__ part, uint32_t nparts, float* __restrict__ bounds)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (uint32_t b = threadIdx.x; b < nparts; b += RT)
-        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], part[(size_t)b * 6 + k]); hi[k] = fmaxf(hi[k], part[(size_t)b * 6 + 3 + k]); }
-    pcreg_block_minmax(lo, hi, bounds);
+    const float inf = __builtin_inff();
+    float b[6] = {inf, inf, inf, -inf, -inf, -inf};
+    for (uint32_t p = threadIdx.x; p < nparts; p += RT)
+        for (int k = 0; k < 6; ++k) b[k] = PcregMinMax()(b[k], part[(size_t)p * 6 + k], k);
+    block_reduce<RT, 6>(b, bounds, PcregMinMax());
 }
 
 // ---- transform and crop --------------------------------------------------------------------------------------------------------------------------
@@ -229,30 +219,13 @@ __global__ void __launch_bounds__(RT) pcreg_voxel_mean_kernel(const float* __res
             if (lane < first) pcreg_add_member(a, pts, order, N, (uint32_t)k, state);
             if (stop) break;
         }
-        for (int d = 32; d >= 1; d >>= 1) {          // a fixed tree: the same bits on every run
-            a.x += __shfl_xor(a.x, d, WAVE); a.y += __shfl_xor(a.y, d, WAVE); a.z += __shfl_xor(a.z, d, WAVE); a.n += __shfl_xor(a.n, d, WAVE);
-        }
+        a.x = wave_reduce(a.x, op_add()); a.y = wave_reduce(a.y, op_add()); a.z = wave_reduce(a.z, op_add());          // a fixed tree: the same bits on every run
+        a.n = wave_reduce(a.n, op_add());
         if (lane == 0 && a.n) pcreg_write_mean(a, sg, M, keys[start], out, out_keys, state);
     }
 }
 
 // ---- moments -------------------------------------------------------------------------------------------------------------------------------------
-// the workgroup's sum of a[0..18) to dst[0..18): xor tree inside a wave, then the waves in order
-__device__ __forceinline__ void pcreg_block_sum(double* a, double* dst)
-{
-    __shared__ double s_sum[RT / 64][NM];
-    for (int d = 32; d >= 1; d >>= 1)
-        for (int k = 0; k < NM; ++k) a[k] += __shfl_xor(a[k], d, WAVE);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < NM; ++k) s_sum[threadIdx.x >> 6][k] = a[k];
-    __syncthreads();
-    if (threadIdx.x < NM) {
-        double v = s_sum[0][threadIdx.x];
-        for (int w = 1; w < RT / 64; ++w) v += s_sum[w][threadIdx.x];
-        dst[threadIdx.x] = v;
-    }
-}
-
 __global__ void __launch_bounds__(RT) pcreg_moments_kernel(const float* __restrict__ query, const int32_t* __restrict__ index, uint32_t Q,
                                                            const float* __restrict__ target, uint32_t N, double cx, double cy, double cz,
                                                            double* __restrict__ part, uint32_t* state)
@@ -276,7 +249,7 @@ __global__ void __launch_bounds__(RT) pcreg_moments_kernel(const float* __restri
         a[16] += (sc[0] * sc[0] + sc[1] * sc[1]) + sc[2] * sc[2];
         a[17] += (dx * dx + dy * dy) + dz * dz;
     }
-    pcreg_block_sum(a, part + (size_t)blockIdx.x * NM);
+    block_reduce<RT, NM>(a, part + (size_t)blockIdx.x * NM, op_add());          // (block_ops.h states the order of this sum)
 }
 
 __global__ void __launch_bounds__(RT) pcreg_moments_final_kernel(const double* __restrict__ part, uint32_t nparts, double* __restrict__ out)
@@ -285,20 +258,16 @@ __global__ void __launch_bounds__(RT) pcreg_moments_final_kernel(const double* _
     for (int k = 0; k < NM; ++k) a[k] = 0.0;
     for (uint32_t b = threadIdx.x; b < nparts; b += RT)
         for (int k = 0; k < NM; ++k) a[k] += part[(size_t)b * NM + k];
-    pcreg_block_sum(a, out);
+    block_reduce<RT, NM>(a, out, op_add());
 }
 
-static inline unsigned pcreg_grid(size_t n) { return (unsigned)((n + RT - 1) / RT); }
-static inline unsigned pcreg_parts(size_t n) { const unsigned g = pcreg_grid(n); return g < (unsigned)PCREG_PARTS ? g : (unsigned)PCREG_PARTS; }
+static inline unsigned pcreg_parts(size_t n) { const unsigned g = grid_for(n, RT); return g < (unsigned)PCREG_PARTS ? g : (unsigned)PCREG_PARTS; }
 
 static bool scratch_ok(const char* who, int32_t N, const void* scratch, size_t scratch_bytes, PcregScratch* sc)
 {
-    if (!scratch) { set_error("%s: null scratch", who); return false; }
-    if (reinterpret_cast<uintptr_t>(scratch) & 127) { set_error("%s: scratch is not 128-byte aligned", who); return false; }
     size_t need = 0;
     *sc = PcregScratch::carve(static_cast<char*>(const_cast<void*>(scratch)), N, &need);
-    if (scratch_bytes < need) { set_error("%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, need); return false; }
-    return true;
+    return arena_ok(who, "scratch", scratch, scratch_bytes, need);
 }
 
 static bool transform_ok(const char* who, const double* host_T, PcregT* T)
@@ -347,7 +316,7 @@ int32_t ibgs_pcreg_transform(void* stream, int32_t N, const float* points, const
     if (!transform_ok("pcreg_transform", host_T, &T)) return -IBGS_ERR_INVALID;
     if (N == 0) return 0;
     if (!points || !out || !state) { set_error("pcreg_transform: null array"); return -IBGS_ERR_INVALID; }
-    hipLaunchKernelGGL(pcreg_transform_kernel, dim3(pcreg_grid((size_t)N)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, T, out, state);
+    hipLaunchKernelGGL(pcreg_transform_kernel, dim3(grid_for((size_t)N, RT)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, T, out, state);
     IBGS_HIP(hipGetLastError());
     return 0;
 }
@@ -364,7 +333,7 @@ int32_t ibgs_pcreg_crop(void* stream, int32_t N, const float* points, const doub
     if (N == 0) return 0;
     if (!points || !polygon || !mask || !state) { set_error("pcreg_crop: null array"); return -IBGS_ERR_INVALID; }
     const int u = axis == 0 ? 1 : 0, v = axis == 2 ? 1 : 2;
-    hipLaunchKernelGGL(pcreg_crop_kernel, dim3(pcreg_grid((size_t)N)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, T, host_T ? 1 : 0,
+    hipLaunchKernelGGL(pcreg_crop_kernel, dim3(grid_for((size_t)N, RT)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, T, host_T ? 1 : 0,
                        (int)axis, u, v, axis_min, axis_max, polygon, (int)n_poly, mask, state);
     IBGS_HIP(hipGetLastError());
     return 0;
@@ -376,7 +345,7 @@ int32_t ibgs_pcreg_voxel_keys(void* stream, int32_t N, const float* points, cons
     if (!(voxel > 0.0) || !(voxel < 1e300)) { set_error("pcreg_voxel_keys: voxel must be positive and finite"); return -IBGS_ERR_INVALID; }
     if (N == 0) return 0;
     if (!points || !bounds || !keys || !state) { set_error("pcreg_voxel_keys: null array"); return -IBGS_ERR_INVALID; }
-    hipLaunchKernelGGL(pcreg_voxel_keys_kernel, dim3(pcreg_grid((size_t)N)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, bounds, voxel,
+    hipLaunchKernelGGL(pcreg_voxel_keys_kernel, dim3(grid_for((size_t)N, RT)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, bounds, voxel,
                        keys, state);
     IBGS_HIP(hipGetLastError());
     return 0;
@@ -389,7 +358,7 @@ int32_t ibgs_pcreg_voxel_count(void* stream, int32_t N, const int64_t* sorted_ke
     if (!sorted_keys || !total || !state) { set_error("pcreg_voxel_count: null array"); return -IBGS_ERR_INVALID; }
     if (!scratch_ok("pcreg_voxel_count", N, scratch, scratch_bytes, &sc)) return -IBGS_ERR_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pcreg_voxel_heads_kernel, dim3(pcreg_grid((size_t)N)), dim3(RT), 0, s, sorted_keys, (uint32_t)N, sc.flag);
+    hipLaunchKernelGGL(pcreg_voxel_heads_kernel, dim3(grid_for((size_t)N, RT)), dim3(RT), 0, s, sorted_keys, (uint32_t)N, sc.flag);
     IBGS_HIP(hipGetLastError());
     const int rc = exclusive_scan_u32(s, sc.flag, sc.pos, (size_t)N, sc.scan, sc.scan_elems, true);
     if (rc) return rc;
@@ -405,7 +374,7 @@ int32_t ibgs_pcreg_voxel_emit(void* stream, int32_t N, const float* points, cons
     if (!points || !order || !sorted_keys || !state || (M > 0 && !out)) { set_error("pcreg_voxel_emit: null array"); return -IBGS_ERR_INVALID; }
     if (!scratch_ok("pcreg_voxel_emit", N, scratch, scratch_bytes, &sc)) return -IBGS_ERR_INVALID;
     if (M == 0) return 0;
-    hipLaunchKernelGGL(pcreg_voxel_mean_kernel, dim3(pcreg_grid((size_t)N)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, order, sorted_keys,
+    hipLaunchKernelGGL(pcreg_voxel_mean_kernel, dim3(grid_for((size_t)N, RT)), dim3(RT), 0, reinterpret_cast<hipStream_t>(stream), points, (uint32_t)N, order, sorted_keys,
                        sc.flag, sc.pos, (uint32_t)M, out, out_keys, state);
     IBGS_HIP(hipGetLastError());
     return 0;

@@ -41,6 +41,7 @@
 // integrate never waits for the device; extract reads back the totals once (ibgs_amd/tsdf.py).
 #include <cmath>
 #include "common.h"
+#include "block_ops.h"
 #include "../../include/ibgs_tsdf.h"
 
 namespace ibgs {
@@ -503,7 +504,7 @@ struct McLds {
     float c[3][NB3];
     uint8_t ok[NB3];          // weight > 0
     int nb[27];               // block index of neighbour (ox + 1) + 3 (oy + 1) + 9 (oz + 1), -1 = none
-    int wsum[2][TVOX / 64];
+    int wsum[2][TVOX / 64];          // two rows: a vertex scan and a face scan (block_exclusive_scan) are in flight together
 };
 
 // the 27 blocks around block `id` and its 10^3 voxels (colours too when `with_color`) into LDS; ends with a barrier
@@ -566,23 +567,6 @@ __device__ int mc_edge_mask(const McLds& L, int px, int py, int pz)
     return mask;
 }
 
-// exclusive prefix over the 512 threads (and the total) of x; `slot` picks the LDS row, so two scans may be in flight
-__device__ int wg_scan(McLds& L, int slot, int x, int& total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    if (lane == 63) L.wsum[slot][w] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int q = 0; q < TVOX / 64; ++q) { const int s = L.wsum[slot][q]; off += q < w ? s : 0; tot += s; }
-    total = tot;
-    return off + inc - x;
-}
-
 struct McGeom { int gx, gy, gz; float vl; };          // global voxel coordinates of LDS voxel (0, 0, 0), voxel length
 
 // vertex of the cell-edge `e` of the cell with min corner m (LDS coordinates): position and interpolation parameter
@@ -616,8 +600,8 @@ __global__ void __launch_bounds__(TVOX) tsdf_mc_count_kernel(ibgs_tsdf_volume vo
         const int emask = mc_edge_mask(L, px, py, pz);
         const int cs = mc_case(L, px, py, pz);
         int vtot, ftot;
-        const int vex = wg_scan(L, 0, __popc(emask), vtot);
-        (void)wg_scan(L, 1, cs >= 0 ? tsdf_tri_count(cs) : 0, ftot);
+        const int vex = block_exclusive_scan<TVOX>((int)__popc(emask), &vtot, L.wsum[0]);
+        (void)block_exclusive_scan<TVOX>(cs >= 0 ? tsdf_tri_count(cs) : 0, &ftot, L.wsum[1]);
         sc.vinfo[(size_t)id * TVOX + tid] = (uint16_t)(emask | (vex << 3));
         if (tid == 0) { sc.vcount[r] = vtot; sc.fcount[r] = ftot; }
         __syncthreads();          // LDS reused by the next block
@@ -640,7 +624,7 @@ __global__ void __launch_bounds__(TVOX) tsdf_mc_scan_kernel(ibgs_tsdf_volume vol
             sv += v[q]; sf += f[q];
         }
         int tv, tf;
-        int ov = wg_scan(L, 0, sv, tv) + carry_v, of = wg_scan(L, 1, sf, tf) + carry_f;
+        int ov = block_exclusive_scan<TVOX>(sv, &tv, L.wsum[0]) + carry_v, of = block_exclusive_scan<TVOX>(sf, &tf, L.wsum[1]) + carry_f;
         for (int q = 0; q < SC_PER; ++q) {
             const uint32_t r = base + tid * SC_PER + q;
             if (r < N) { sc.vcount[r] = ov; sc.fcount[r] = of; }
@@ -671,8 +655,8 @@ __global__ void __launch_bounds__(TVOX) tsdf_mc_emit_kernel(ibgs_tsdf_volume vol
         const int cs = mc_case(L, px, py, pz);
         const int nf = cs >= 0 ? tsdf_tri_count(cs) : 0;
         int vtot, ftot;
-        int vi = sc.vcount[r] + wg_scan(L, 0, __popc(emask), vtot);
-        int fi = sc.fcount[r] + wg_scan(L, 1, nf, ftot);
+        int vi = sc.vcount[r] + block_exclusive_scan<TVOX>((int)__popc(emask), &vtot, L.wsum[0]);
+        int fi = sc.fcount[r] + block_exclusive_scan<TVOX>(nf, &ftot, L.wsum[1]);
         for (int a = 0; a < 3; ++a) {
             if (!(emask >> a & 1)) continue;
             const int e = 4 * a;          // the edge owned by p is edge 4 a of the cell whose min corner is p

@@ -3,7 +3,7 @@ used once by GaussianModel.create_from_pcd to initialise the scales (reference s
 submodules/simple-knn/spatial.cu:15-26)."""
 import torch
 
-from . import _lib
+from . import _device, _lib
 
 
 def distCUDA2(points):
@@ -17,10 +17,6 @@ def distCUDA2(points):
     pts = points.detach().float().contiguous()
     out = torch.zeros(P, dtype=torch.float32, device=dev)
     if P:
-        with torch.cuda.device(dev):
-            scratch = torch.empty(lib.ibgs_required_knn(P), dtype=torch.uint8, device=dev)
-            rc = lib.ibgs_knn_mean_dist2(torch.cuda.current_stream(dev).cuda_stream, P, pts.data_ptr(), out.data_ptr(),
-                                         scratch.data_ptr(), scratch.numel())
-            if rc < 0:
-                raise RuntimeError("ibgs_knn_mean_dist2 failed (%d): %s" % (rc, _lib.last_error()))
+        scratch = _device.scratch(dev, lib.ibgs_required_knn(P))
+        _device.call(dev, "ibgs_knn_mean_dist2", P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel())
     return out

@@ -18,7 +18,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _device, _lib
 from .tsdf import TriangleMesh
 
 MAX_FACES = (1 << 30) - 1
@@ -55,8 +55,7 @@ def _check(mesh):
     if F > MAX_FACES or V > MAX_VERTICES:
         raise ValueError("mesh too large: V %d, F %d (limits: V < 2^31, F < 2^30)" % (V, F))
     for name, t in (("vertices", v), ("faces", f), ("colors", c), ("normals", n)):
-        if not t.is_cuda:
-            raise RuntimeError("ibgs_amd.mesh runs on the MI355X only (mesh.%s is a CPU tensor; there is no CPU path)" % name)
+        _device.refuse_cpu("mesh", "mesh." + name, t)
     if any(t.device != v.device for t in (f, c, n)):
         raise ValueError("the mesh's tensors are on different devices")
     return V, F, v.device
@@ -72,22 +71,14 @@ class _Run:
         nbytes = self.lib.ibgs_mesh_required_scratch(V, F)
         if nbytes == 0:
             raise ValueError("mesh too large: V %d, F %d" % (V, F))
-        with torch.cuda.device(dev):
-            self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.state = torch.zeros(_lib.MESH_STATE_WORDS, dtype=torch.int32, device=dev)
+        self.scratch, self.state = _device.scratch(dev, nbytes), _device.zeros_state(dev, _lib.MESH_STATE_WORDS)
         m = _lib.Mesh()
         m.V, m.F, m.vertices, m.faces = V, F, self.vertices.data_ptr(), self.faces.data_ptr()
         m.scratch, m.scratch_bytes, m.state = self.scratch.data_ptr(), nbytes, self.state.data_ptr()
         self.c = m
 
-    def stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
-
     def call(self, name, *args):
-        with torch.cuda.device(self.dev):
-            rc = getattr(self.lib, name)(self.stream(), ctypes.byref(self.c), *args)
-        if rc < 0:
-            raise RuntimeError("%s failed (%d): %s" % (name, rc, _lib.last_error()))
+        _device.call(self.dev, name, ctypes.byref(self.c), *args)
 
     def counters(self):
         s = self.state.cpu().tolist()          # (waits for the stream)

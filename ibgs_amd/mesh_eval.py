@@ -12,15 +12,13 @@ from run to run); the f64 means are summed with atomics and may differ in their 
 HIP only (C ABI include/ibgs_mesh_eval.h): CPU tensors are refused, every argument is checked before any GPU work, every kernel runs on torch's current
 stream, inputs are never written.  The two orderings (Morton keys of the points, for the search hierarchy) are torch.sort calls; everything else is the
 library's kernels.  Each call reads a few words back (it waits for the stream): the docstrings say which."""
-import math
 from typing import NamedTuple
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _device, _lib
+from ._device import MAX_POINTS
 
-MAX_POINTS = (1 << 31) - 1
 MAX_FACES = (1 << 30) - 1
 THIN_FIRST_BATCH = 8          # rounds issued before the first read-back of the undecided count; every further batch is twice as long, up to
 THIN_MAX_BATCH = 1024
@@ -55,37 +53,6 @@ class MeshEvalError(RuntimeError):
     pass
 
 
-def _check_points(name, p):
-    if not torch.is_tensor(p):
-        raise TypeError("%s must be a tensor, got %s" % (name, type(p).__name__))
-    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("%s must be (N, 3) float32, got %s %s" % (name, tuple(p.shape), p.dtype))
-    if p.shape[0] > MAX_POINTS:
-        raise ValueError("%s holds %d points (limit: N < 2^31)" % (name, p.shape[0]))
-    return p
-
-
-def _check_cuda(*named):
-    """After every shape and value check: (name, tensor) pairs must be device tensors on one device.  -> the tensors, contiguous."""
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError("ibgs_amd.mesh_eval runs on the MI355X only (%s is a CPU tensor; there is no CPU path)" % name)
-    for name, t in named[1:]:
-        if t.device != named[0][1].device:
-            raise ValueError("%s is on %s, %s on %s" % (named[0][0], named[0][1].device, name, t.device))
-    return [t.contiguous() for _, t in named]
-
-
-def _check_positive(name, x, allow_zero=False):
-    try:
-        x = float(x)
-    except (TypeError, ValueError):
-        raise TypeError("%s must be a number, got %s" % (name, type(x).__name__)) from None
-    if not math.isfinite(x) or x < 0 or (x == 0 and not allow_zero) or float(np.float32(x)) > 1e18:
-        raise ValueError("%s must be a finite %s number, got %r" % (name, "non-negative" if allow_zero else "positive", x))
-    return x
-
-
 def _check_mask(name, m, n):
     if m is None:
         return None
@@ -96,22 +63,11 @@ def _check_mask(name, m, n):
     return m
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+def new_state(dev):
+    return _device.zeros_state(dev, _lib.MEVAL_STATE_WORDS)
 
 
-def _call(dev, name, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), name)(_stream(dev), *args)
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (name, rc, _lib.last_error()))
-
-
-def _new_state(dev):
-    return torch.zeros(_lib.MEVAL_STATE_WORDS, dtype=torch.int32, device=dev)
-
-
-def _raise_on(s, what):
+def raise_on(s, what):
     """s: the state words on the host."""
     if s[_lib.MEVAL_BAD_FACES]:
         raise MeshEvalError("%s: mesh.faces holds %d triangle(s) with a vertex index out of range" % (what, s[_lib.MEVAL_BAD_FACES]))
@@ -151,24 +107,23 @@ def sample_surface(mesh, density, include_vertices=True, max_points=None):
     One host read-back sizes the output: the 64-bit total and the state words.  `max_points` (default: what fits in 90 % of the device's free memory) is
     enforced on that total BEFORE anything is allocated: ValueError with the count.  A second read-back of the state follows the emit."""
     v, f = _check_mesh(mesh)
-    density = _check_positive("density", density)
+    density = _device.check_positive("density", density)
     if max_points is not None:
         max_points = int(max_points)
         if max_points < 0:
             raise ValueError("max_points must be >= 0, got %d" % max_points)
-    v, f = _check_cuda(("mesh.vertices", v), ("mesh.faces", f))
+    v, f = _device.check_cuda("mesh_eval", ("mesh.vertices", v), ("mesh.faces", f))
     V, F, dev = int(v.shape[0]), int(f.shape[0]), v.device
     lib = _lib.load()
     nbytes = lib.ibgs_meval_required_sample_scratch(F)
     if nbytes == 0:
         raise ValueError("mesh too large: F %d" % F)
+    scratch, state = _device.scratch(dev, nbytes), new_state(dev)
     with torch.cuda.device(dev):
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        state = _new_state(dev)
         total = torch.zeros(1, dtype=torch.int64, device=dev)
-    _call(dev, "ibgs_meval_sample_count", V, F, v.data_ptr(), f.data_ptr(), density, scratch.data_ptr(), nbytes, total.data_ptr(), state.data_ptr())
+    _device.call(dev, "ibgs_meval_sample_count", V, F, v.data_ptr(), f.data_ptr(), density, scratch.data_ptr(), nbytes, total.data_ptr(), state.data_ptr())
     back = torch.cat([total, state.to(torch.int64)]).cpu().tolist()          # (waits for the stream)
-    _raise_on(back[1:], "sample_surface")
+    raise_on(back[1:], "sample_surface")
     n_samples = back[0]
     n = n_samples + (V if include_vertices else 0)
     if max_points is not None and n > max_points:
@@ -186,31 +141,32 @@ def sample_surface(mesh, density, include_vertices=True, max_points=None):
         out[:V].copy_(v)
         first = V
     if n_samples:
-        _call(dev, "ibgs_meval_sample_emit", V, F, v.data_ptr(), f.data_ptr(), density, scratch.data_ptr(), nbytes, n_samples,
-              out.data_ptr() + first * 12, state.data_ptr())
-        _raise_on(state.cpu().tolist(), "sample_surface")
+        _device.call(dev, "ibgs_meval_sample_emit", V, F, v.data_ptr(), f.data_ptr(), density, scratch.data_ptr(), nbytes, n_samples,
+                     out.data_ptr() + first * 12, state.data_ptr())
+        raise_on(state.cpu().tolist(), "sample_surface")
     return out
 
 
 # ---- the search hierarchy ----------------------------------------------------------------------------------------------------------------------------
-class _Index:
-    """Hierarchy of boxes over a point set (N > 0), its scratch owned here.  `tag`: the int32 that travels with every point (default: its index)."""
+class Index:
+    """Hierarchy of boxes over a point set (N > 0), its scratch owned here; `points` stays referenced (registration's moments read the targets through it).
+    `tag`: the int32 that travels with every point (default: its index)."""
 
     def __init__(self, points, state, tag=None):
-        self.N, self.dev, self.state = int(points.shape[0]), points.device, state
+        self.points, self.N, self.dev, self.state = points, int(points.shape[0]), points.device, state
         lib = _lib.load()
         self.nbytes = lib.ibgs_meval_required_tree(self.N)
         with torch.cuda.device(self.dev):
             self.bounds = torch.cat([points.amin(0), points.amax(0)])
             self.order = torch.sort(self.keys(points), stable=True).indices
-            self.tree = torch.empty(self.nbytes, dtype=torch.uint8, device=self.dev)
-        _call(self.dev, "ibgs_meval_build", self.N, points.data_ptr(), self.order.data_ptr(), tag.data_ptr() if tag is not None else None,
-              self.tree.data_ptr(), self.nbytes, state.data_ptr())
+        self.tree = _device.scratch(self.dev, self.nbytes)
+        _device.call(self.dev, "ibgs_meval_build", self.N, points.data_ptr(), self.order.data_ptr(), tag.data_ptr() if tag is not None else None,
+                     self.tree.data_ptr(), self.nbytes, state.data_ptr())
 
     def keys(self, points):
         with torch.cuda.device(self.dev):
             k = torch.empty(points.shape[0], dtype=torch.int64, device=self.dev)
-        _call(self.dev, "ibgs_meval_keys", int(points.shape[0]), points.data_ptr(), self.bounds.data_ptr(), k.data_ptr(), self.state.data_ptr())
+        _device.call(self.dev, "ibgs_meval_keys", int(points.shape[0]), points.data_ptr(), self.bounds.data_ptr(), k.data_ptr(), self.state.data_ptr())
         return k
 
     def query(self, q, max_dist):
@@ -222,9 +178,12 @@ class _Index:
             if Q == 0:
                 return dist, index
             qorder = torch.sort(self.keys(q)).indices          # neighbouring lanes walk neighbouring boxes
-        _call(self.dev, "ibgs_meval_nearest", Q, q.data_ptr(), qorder.data_ptr(), self.N, self.tree.data_ptr(), self.nbytes, max_dist, dist.data_ptr(),
-              index.data_ptr(), self.state.data_ptr())
+        _device.call(self.dev, "ibgs_meval_nearest", Q, q.data_ptr(), qorder.data_ptr(), self.N, self.tree.data_ptr(), self.nbytes, max_dist, dist.data_ptr(),
+                     index.data_ptr(), self.state.data_ptr())
         return dist, index
+
+
+_Index = Index          # (the name tests/test_gpu_mesh_eval.py and tools/bench_tsdf.py know it by)
 
 
 def _no_match(Q, dev):
@@ -235,7 +194,7 @@ def _no_match(Q, dev):
 def _nearest_async(query, target, max_dist, state):
     if target.shape[0] == 0:
         return _no_match(int(query.shape[0]), query.device)
-    return _Index(target, state).query(query, max_dist)
+    return Index(target, state).query(query, max_dist)
 
 
 def nearest(query, target, max_dist):
@@ -245,12 +204,12 @@ def nearest(query, target, max_dist):
 
     A query with nothing within max_dist costs a few dozen box tests, whatever max_dist is in units of the point spacing.
     One host read-back, at the end: the state words (a non-finite coordinate raises ValueError).  Nothing before it waits for the device."""
-    query, target = _check_points("query", query), _check_points("target", target)
-    max_dist = _check_positive("max_dist", max_dist, allow_zero=True)
-    query, target = _check_cuda(("query", query), ("target", target))
-    state = _new_state(query.device)
+    query, target = _device.check_points("query", query), _device.check_points("target", target)
+    max_dist = _device.check_positive("max_dist", max_dist, allow_zero=True)
+    query, target = _device.check_cuda("mesh_eval", ("query", query), ("target", target))
+    state = new_state(query.device)
     dist, index = _nearest_async(query, target, max_dist, state)
-    _raise_on(state.cpu().tolist(), "nearest")          # (waits for the stream)
+    raise_on(state.cpu().tolist(), "nearest")          # (waits for the stream)
     return NearestResult(dist, index)
 
 
@@ -264,34 +223,34 @@ def downsample(points, radius, order=None):
     THIN_FIRST_BATCH = 8, 16, 32, ... up to THIN_MAX_BATCH = 1024 rounds, with ONE read-back per batch (the undecided count and the state words).  A
     shuffled cloud needs about 10 rounds (one batch or two); the worst case is a chain of points visited along its length, each within `radius` of
     the one before, which needs on the order of one round per point: n points cost about log2(n / 8) + n / 1024 read-backs."""
-    points = _check_points("points", points)
-    radius = _check_positive("radius", radius, allow_zero=True)
+    points = _device.check_points("points", points)
+    radius = _device.check_positive("radius", radius, allow_zero=True)
     N = int(points.shape[0])
     if order is not None:
         if not torch.is_tensor(order):
             raise TypeError("order must be a tensor, got %s" % type(order).__name__)
         if order.dtype != torch.int64 or order.dim() != 1 or order.shape[0] != N:
             raise ValueError("order must be (%d,) int64, got %s %s" % (N, tuple(order.shape), order.dtype))
-        points, order = _check_cuda(("points", points), ("order", order))
+        points, order = _device.check_cuda("mesh_eval", ("points", points), ("order", order))
     else:
-        points, = _check_cuda(("points", points))
+        points, = _device.check_cuda("mesh_eval", ("points", points))
     dev = points.device
     with torch.cuda.device(dev):
         keep = torch.zeros(N, dtype=torch.bool, device=dev)
         if N == 0:
             return keep
-        state = _new_state(dev)
+        state = new_state(dev)
         if order is None:
             rank = torch.arange(N, dtype=torch.int32, device=dev)
         else:          # rank[order[k]] = k; whether `order` is a permutation is settled by the counts read back with the first batch
             rank = torch.full((N,), -1, dtype=torch.int32, device=dev)
             rank[order.clamp(0, N - 1)] = torch.arange(N, dtype=torch.int32, device=dev)
             unranked = ((rank < 0).sum() + ((order < 0) | (order >= N)).sum()).to(torch.int32)          # (0 iff `order` is a permutation)
-        index = _Index(points, state, tag=rank)
+        index = Index(points, state, tag=rank)
         status = torch.zeros(N, dtype=torch.int32, device=dev)
     batch, first = THIN_FIRST_BATCH, True
     while True:
-        _call(dev, "ibgs_meval_thin_rounds", N, index.tree.data_ptr(), index.nbytes, radius, status.data_ptr(), batch, state.data_ptr())
+        _device.call(dev, "ibgs_meval_thin_rounds", N, index.tree.data_ptr(), index.nbytes, radius, status.data_ptr(), batch, state.data_ptr())
         if first and order is not None:
             s = torch.cat([state, unranked.reshape(1)]).cpu().tolist()          # (waits for the stream)
             if s[-1]:
@@ -299,7 +258,7 @@ def downsample(points, radius, order=None):
         else:
             s = state.cpu().tolist()
         first = False
-        _raise_on(s, "downsample")
+        raise_on(s, "downsample")
         if s[_lib.MEVAL_UNDECIDED] == 0:
             break
         batch = min(2 * batch, THIN_MAX_BATCH)
@@ -319,13 +278,13 @@ class _Sums:
             self.count = torch.zeros(n, dtype=torch.int64, device=dev)
 
     def add(self, slot, dist, threshold):
-        _call(self.dev, "ibgs_meval_reduce", int(dist.shape[0]), dist.data_ptr(), threshold, self.sum.data_ptr() + 8 * slot, self.count.data_ptr() + 8 * slot)
+        _device.call(self.dev, "ibgs_meval_reduce", int(dist.shape[0]), dist.data_ptr(), threshold, self.sum.data_ptr() + 8 * slot, self.count.data_ptr() + 8 * slot)
 
     def read(self, what):
         with torch.cuda.device(self.dev):
             back = torch.cat([self.sum.view(torch.int64), self.count, self.state.to(torch.int64)]).cpu()          # (waits for the stream)
         n = self.sum.shape[0]
-        _raise_on(back[2 * n:].tolist(), what)
+        raise_on(back[2 * n:].tolist(), what)
         return back[:n].view(torch.float64).tolist(), back[n:2 * n].tolist()
 
 
@@ -340,14 +299,14 @@ def chamfer(pred, gt, max_dist, pred_query_mask=None, gt_query_mask=None):
     f64.  An empty selection gives NaN means and zero counts.  -> ChamferResult.
 
     One host read-back, at the end: the two sums, the two counts and the state words."""
-    pred, gt = _check_points("pred", pred), _check_points("gt", gt)
-    max_dist = _check_positive("max_dist", max_dist, allow_zero=True)
+    pred, gt = _device.check_points("pred", pred), _device.check_points("gt", gt)
+    max_dist = _device.check_positive("max_dist", max_dist, allow_zero=True)
     pm = _check_mask("pred_query_mask", pred_query_mask, pred.shape[0])
     gm = _check_mask("gt_query_mask", gt_query_mask, gt.shape[0])
-    pred, gt = _check_cuda(("pred", pred), ("gt", gt))
-    _check_cuda(*([("pred", pred)] + [(n, m) for n, m in (("pred_query_mask", pm), ("gt_query_mask", gm)) if m is not None]))
+    pred, gt = _device.check_cuda("mesh_eval", ("pred", pred), ("gt", gt))
+    _device.check_cuda("mesh_eval", *([("pred", pred)] + [(n, m) for n, m in (("pred_query_mask", pm), ("gt_query_mask", gm)) if m is not None]))
     dev = pred.device
-    state = _new_state(dev)
+    state = new_state(dev)
     sums = _Sums(dev, state, 2)
     with torch.cuda.device(dev):
         pq = pred if pm is None else pred[pm]          # (an element-wise selection; torch sizes it with a read-back of its own)
@@ -375,13 +334,13 @@ def fscore(pred, gt, tau):
     The nearest search is cut off at 2 tau and the comparison is dist < tau in f32.  An empty set gives 0, as the reference does.  -> FScoreResult.
 
     One host read-back, at the end: the two counts and the state words."""
-    pred, gt = _check_points("pred", pred), _check_points("gt", gt)
-    tau = _check_positive("tau", tau)
-    pred, gt = _check_cuda(("pred", pred), ("gt", gt))
+    pred, gt = _device.check_points("pred", pred), _device.check_points("gt", gt)
+    tau = _device.check_positive("tau", tau)
+    pred, gt = _device.check_cuda("mesh_eval", ("pred", pred), ("gt", gt))
     n_pred, n_gt = int(pred.shape[0]), int(gt.shape[0])
     if n_pred == 0 or n_gt == 0:
         return _fscore_from(0, n_pred, 0, n_gt)
-    state = _new_state(pred.device)
+    state = new_state(pred.device)
     sums = _Sums(pred.device, state, 2)
     sums.add(0, _nearest_async(pred, gt, 2 * tau, state)[0], tau)
     sums.add(1, _nearest_async(gt, pred, 2 * tau, state)[0], tau)
@@ -401,14 +360,14 @@ def evaluate_mesh(mesh, gt_points, density=0.2, max_dist=20.0, tau=None, seed=0,
 
     -> dict: mean_d2s, mean_s2d, overall, n_d2s, n_s2d, n_sampled, n_thinned, and with tau: precision, recall, fscore.
     Host read-backs: those of sample_surface, downsample, chamfer and fscore."""
-    gt_points = _check_points("gt_points", gt_points)
-    max_dist = _check_positive("max_dist", max_dist, allow_zero=True)
+    gt_points = _device.check_points("gt_points", gt_points)
+    max_dist = _device.check_positive("max_dist", max_dist, allow_zero=True)
     if tau is not None:
-        tau = _check_positive("tau", tau)
+        tau = _device.check_positive("tau", tau)
     _check_mask("gt_query_mask", gt_query_mask, gt_points.shape[0])
     v, f = _check_mesh(mesh)
-    _check_positive("density", density)
-    _check_cuda(("gt_points", gt_points), ("mesh.vertices", v), ("mesh.faces", f))
+    _device.check_positive("density", density)
+    _device.check_cuda("mesh_eval", ("gt_points", gt_points), ("mesh.vertices", v), ("mesh.faces", f))
     cloud = sample_surface(mesh, density, include_vertices=include_vertices, max_points=max_points)
     dev = cloud.device
     with torch.cuda.device(dev):

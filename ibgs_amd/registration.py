@@ -21,8 +21,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib, mesh_eval
-from .mesh_eval import _check_points, _check_positive
+from . import _device, _lib, mesh_eval
 
 _AXES = {"X": 0, "Y": 1, "Z": 2}
 
@@ -62,17 +61,6 @@ def _check_T(name, T):
     return np.ascontiguousarray(T)
 
 
-def _check_cuda(*named):
-    """After every shape and value check: (name, tensor) pairs must be device tensors on one device.  -> the tensors, contiguous."""
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError("ibgs_amd.registration runs on the MI355X only (%s is a CPU tensor; there is no CPU path)" % name)
-    for name, t in named[1:]:
-        if t.device != named[0][1].device:
-            raise ValueError("%s is on %s, %s on %s" % (named[0][0], named[0][1].device, name, t.device))
-    return [t.contiguous() for _, t in named]
-
-
 def _check_volume(vol):
     """-> (w, axis_min, axis_max, (n, 2) f64 {u, v})."""
     try:
@@ -109,23 +97,15 @@ def _c16(T):
     return (ctypes.c_double * 16)(*T.reshape(-1).tolist())
 
 
-def _call(dev, name, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), name)(torch.cuda.current_stream(dev).cuda_stream, *args)
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (name, rc, _lib.last_error()))
-
-
 def _new_state(dev):
-    return torch.zeros(_lib.PCREG_STATE_WORDS, dtype=torch.int32, device=dev)
+    return _device.zeros_state(dev, _lib.PCREG_STATE_WORDS)
 
 
 def _scratch(dev, n):
     nbytes = _lib.load().ibgs_pcreg_required_scratch(n)
     if nbytes == 0:
         raise ValueError("cloud too large: N %d" % n)
-    with torch.cuda.device(dev):
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _device.scratch(dev, nbytes), nbytes
 
 
 def _raise_on(s, what, voxel=None):
@@ -141,15 +121,15 @@ def _raise_on(s, what, voxel=None):
 
 # ---- transform and crop --------------------------------------------------------------------------------------------------------------------------------
 def _transform_into(points, T, out, state):
-    _call(points.device, "ibgs_pcreg_transform", int(points.shape[0]), points.data_ptr(), _c16(T), out.data_ptr(), state.data_ptr())
+    _device.call(points.device, "ibgs_pcreg_transform", int(points.shape[0]), points.data_ptr(), _c16(T), out.data_ptr(), state.data_ptr())
 
 
 def transform(points, T):
     """T (4 x 4 f64 on the host, last row 0 0 0 1) applied to every point: x' = ((T00 x + T01 y) + T02 z) + T03 in f64 from the f32 coordinates, rounded once to
     f32.  -> (N, 3) f32 on the device.  One host read-back, at the end: the state words (a non-finite coordinate raises ValueError)."""
-    points = _check_points("points", points)
+    points = _device.check_points("points", points)
     T = _check_T("T", T)
-    points, = _check_cuda(("points", points))
+    points, = _device.check_cuda("registration", ("points", points))
     dev = points.device
     with torch.cuda.device(dev):
         out = torch.empty_like(points)
@@ -165,8 +145,8 @@ def _crop_async(points, vol, T, state):
     with torch.cuda.device(dev):
         mask = torch.zeros(int(points.shape[0]), dtype=torch.uint8, device=dev)
         poly = torch.from_numpy(uv).to(dev)
-    _call(dev, "ibgs_pcreg_crop", int(points.shape[0]), points.data_ptr(), _c16(T) if T is not None else None, w, lo, hi, int(uv.shape[0]), poly.data_ptr(),
-          mask.data_ptr(), state.data_ptr())
+    _device.call(dev, "ibgs_pcreg_crop", int(points.shape[0]), points.data_ptr(), _c16(T) if T is not None else None, w, lo, hi, int(uv.shape[0]), poly.data_ptr(),
+                 mask.data_ptr(), state.data_ptr())
     return mask.view(torch.bool)
 
 
@@ -175,11 +155,11 @@ def crop(points, volume, T=None):
     v-coordinate to the left of it (the half-open rule of the header of registration.hip), all in f64.  With T the point is transformed first exactly as
     transform() does: crop(points, vol, T) equals crop(transform(points, T), vol) bit for bit.  -> (N,) bool on the device.
     One host read-back, at the end: the state words."""
-    points = _check_points("points", points)
+    points = _device.check_points("points", points)
     vol = _check_volume(volume)
     if T is not None:
         T = _check_T("T", T)
-    points, = _check_cuda(("points", points))
+    points, = _device.check_cuda("registration", ("points", points))
     state = _new_state(points.device)
     mask = _crop_async(points, vol, T, state)
     _raise_on(state.cpu().tolist(), "crop")          # (waits for the stream)
@@ -194,9 +174,9 @@ def voxel_down_sample(points, voxel_size, return_keys=False):
 
     A voxel index above 2^21 - 1 raises ValueError (the voxel size is too small for the cloud's extent).  One host read-back sizes the output: M and the
     state words."""
-    points = _check_points("points", points)
-    voxel_size = _check_positive("voxel_size", voxel_size)
-    points, = _check_cuda(("points", points))
+    points = _device.check_points("points", points)
+    voxel_size = _device.check_positive("voxel_size", voxel_size)
+    points, = _device.check_cuda("registration", ("points", points))
     N, dev = int(points.shape[0]), points.device
     if N == 0:
         with torch.cuda.device(dev):
@@ -208,19 +188,19 @@ def voxel_down_sample(points, voxel_size, return_keys=False):
         bounds = torch.empty(6, dtype=torch.float32, device=dev)
         keys = torch.empty(N, dtype=torch.int64, device=dev)
         total = torch.zeros(1, dtype=torch.int32, device=dev)
-    _call(dev, "ibgs_pcreg_bounds", N, points.data_ptr(), scratch.data_ptr(), nbytes, bounds.data_ptr(), state.data_ptr())
-    _call(dev, "ibgs_pcreg_voxel_keys", N, points.data_ptr(), bounds.data_ptr(), voxel_size, keys.data_ptr(), state.data_ptr())
+    _device.call(dev, "ibgs_pcreg_bounds", N, points.data_ptr(), scratch.data_ptr(), nbytes, bounds.data_ptr(), state.data_ptr())
+    _device.call(dev, "ibgs_pcreg_voxel_keys", N, points.data_ptr(), bounds.data_ptr(), voxel_size, keys.data_ptr(), state.data_ptr())
     with torch.cuda.device(dev):
         skeys, order = torch.sort(keys, stable=True)          # equal keys stay in index order: a voxel's sum is made in that order
-    _call(dev, "ibgs_pcreg_voxel_count", N, skeys.data_ptr(), scratch.data_ptr(), nbytes, total.data_ptr(), state.data_ptr())
+    _device.call(dev, "ibgs_pcreg_voxel_count", N, skeys.data_ptr(), scratch.data_ptr(), nbytes, total.data_ptr(), state.data_ptr())
     back = torch.cat([total, state]).cpu().tolist()          # (waits for the stream)
     _raise_on(back[1:], "voxel_down_sample", voxel_size)
     M = back[0]
     with torch.cuda.device(dev):
         out = torch.empty(M, 3, dtype=torch.float32, device=dev)
         okeys = torch.empty(M, dtype=torch.int64, device=dev) if return_keys else None
-    _call(dev, "ibgs_pcreg_voxel_emit", N, points.data_ptr(), order.data_ptr(), skeys.data_ptr(), scratch.data_ptr(), nbytes, M, out.data_ptr(),
-          okeys.data_ptr() if return_keys else None, state.data_ptr())
+    _device.call(dev, "ibgs_pcreg_voxel_emit", N, points.data_ptr(), order.data_ptr(), skeys.data_ptr(), scratch.data_ptr(), nbytes, M, out.data_ptr(),
+                 okeys.data_ptr() if return_keys else None, state.data_ptr())
     return (out, okeys) if return_keys else out
 
 
@@ -274,10 +254,10 @@ def _icp_step(source, index, T, max_dist, qorder, q, out, pivot, scratch, mstate
     with torch.cuda.device(dev):
         dist = torch.empty(Q, dtype=torch.float32, device=dev)
         idx = torch.empty(Q, dtype=torch.int32, device=dev)
-    mesh_eval._call(dev, "ibgs_meval_nearest", Q, q.data_ptr(), qorder.data_ptr() if qorder is not None else None, index.N, index.tree.data_ptr(), index.nbytes,
-                    max_dist, dist.data_ptr(), idx.data_ptr(), mstate.data_ptr())
-    _call(dev, "ibgs_pcreg_moments", Q, q.data_ptr(), idx.data_ptr(), index.N, index.points.data_ptr(), (ctypes.c_double * 3)(*pivot.tolist()), scratch[0].data_ptr(),
-          scratch[1], out.data_ptr(), pstate.data_ptr())
+    _device.call(dev, "ibgs_meval_nearest", Q, q.data_ptr(), qorder.data_ptr() if qorder is not None else None, index.N, index.tree.data_ptr(), index.nbytes,
+                 max_dist, dist.data_ptr(), idx.data_ptr(), mstate.data_ptr())
+    _device.call(dev, "ibgs_pcreg_moments", Q, q.data_ptr(), idx.data_ptr(), index.N, index.points.data_ptr(), (ctypes.c_double * 3)(*pivot.tolist()), scratch[0].data_ptr(),
+                 scratch[1], out.data_ptr(), pstate.data_ptr())
     return idx
 
 
@@ -285,15 +265,14 @@ def _read_step(out, mstate, pstate, what):
     """The one read-back of an ICP iteration: the 18 doubles and both units' state words.  -> the moments (numpy f64)."""
     with torch.cuda.device(out.device):
         back = torch.cat([out.view(torch.int64), mstate.to(torch.int64), pstate.to(torch.int64)]).cpu()          # (waits for the stream)
-    mesh_eval._raise_on(back[_lib.PCREG_MOMENTS:_lib.PCREG_MOMENTS + _lib.MEVAL_STATE_WORDS].tolist(), what)
+    mesh_eval.raise_on(back[_lib.PCREG_MOMENTS:_lib.PCREG_MOMENTS + _lib.MEVAL_STATE_WORDS].tolist(), what)
     _raise_on(back[_lib.PCREG_MOMENTS + _lib.MEVAL_STATE_WORDS:].tolist(), what)
     return back[:_lib.PCREG_MOMENTS].view(torch.float64).numpy().copy()
 
 
 def _target_index(target, mstate, what):
     """The hierarchy over the target and the pivot of the moments, the centre of its bounding box (one read-back: the bounds)."""
-    index = mesh_eval._Index(target, mstate)
-    index.points = target
+    index = mesh_eval.Index(target, mstate)
     b = index.bounds.cpu().numpy().astype(np.float64)          # (waits for the stream)
     if not np.all(np.isfinite(b)):
         raise ValueError("%s: target holds a non-finite coordinate" % what)
@@ -304,14 +283,14 @@ def moments(source, target, max_dist, T=None):
     """One ICP evaluation: the 18 moments of the pairs (T source[i], its nearest target within max_dist) about the centre of the target's bounding box.
     -> (moments (18,) f64 numpy: n, sum(s - c), sum(t - c), sum (s - c)(t - c)^T row-major, sum |s - c|^2, sum d^2; pivot (3,) f64; index (Q,) int32 on the
     device, -1 where there is no pair).  Two host read-backs: the target's bounds, then the moments with the state words."""
-    source, target = _check_points("source", source), _check_points("target", target)
-    max_dist = _check_positive("max_dist", max_dist)
+    source, target = _device.check_points("source", source), _device.check_points("target", target)
+    max_dist = _device.check_positive("max_dist", max_dist)
     T = _check_T("T", np.identity(4) if T is None else T)
-    source, target = _check_cuda(("source", source), ("target", target))
+    source, target = _device.check_cuda("registration", ("source", source), ("target", target))
     dev = source.device
     if source.shape[0] == 0 or target.shape[0] == 0:
         raise RegistrationError("moments: source %d, target %d points: both must hold points" % (source.shape[0], target.shape[0]))
-    mstate, pstate = mesh_eval._new_state(dev), _new_state(dev)
+    mstate, pstate = mesh_eval.new_state(dev), _new_state(dev)
     index, pivot = _target_index(target, mstate, "moments")
     with torch.cuda.device(dev):
         q = torch.empty_like(source)
@@ -329,18 +308,18 @@ def icp(source, target, max_dist, init=None, max_iter=20, rel_fitness=1e-6, rel_
 
     The hierarchy over `target` and the queries' walk order are built once.  Host read-backs: the target's bounds once, then the 18 doubles and the state
     words once per iteration.  Fewer than 3 correspondences raise RegistrationError with the iteration."""
-    source, target = _check_points("source", source), _check_points("target", target)
-    max_dist = _check_positive("max_dist", max_dist)
+    source, target = _device.check_points("source", source), _device.check_points("target", target)
+    max_dist = _device.check_positive("max_dist", max_dist)
     T = _check_T("init", np.identity(4) if init is None else init)
     max_iter = int(max_iter)
     if max_iter < 0:
         raise ValueError("max_iter must be >= 0, got %d" % max_iter)
-    rel_fitness, rel_rmse = _check_positive("rel_fitness", rel_fitness, allow_zero=True), _check_positive("rel_rmse", rel_rmse, allow_zero=True)
-    source, target = _check_cuda(("source", source), ("target", target))
+    rel_fitness, rel_rmse = _device.check_positive("rel_fitness", rel_fitness, allow_zero=True), _device.check_positive("rel_rmse", rel_rmse, allow_zero=True)
+    source, target = _device.check_cuda("registration", ("source", source), ("target", target))
     dev, Q = source.device, int(source.shape[0])
     if Q == 0 or target.shape[0] == 0:
         raise RegistrationError("icp: iteration 0: 0 correspondence(s) (source %d, target %d points), at least 3 are needed" % (Q, target.shape[0]))
-    mstate, pstate = mesh_eval._new_state(dev), _new_state(dev)
+    mstate, pstate = mesh_eval.new_state(dev), _new_state(dev)
     index, pivot = _target_index(target, mstate, "icp")
     scratch = _scratch(dev, 0)
     with torch.cuda.device(dev):
@@ -382,20 +361,20 @@ def evaluate_tnt(pred_points, gt_points, init_trans, volume, tau, voxel_rounds=(
 
     -> dict: precision, recall, fscore, n_precision, n_pred, n_recall, n_gt, n_pred_cropped, n_gt_cropped, transformation (4 x 4 f64), rounds (ICPResults).
     Host read-backs: those of crop, voxel_down_sample, icp and fscore, and one per boolean selection (torch sizes it)."""
-    pred_points, gt_points = _check_points("pred_points", pred_points), _check_points("gt_points", gt_points)
+    pred_points, gt_points = _device.check_points("pred_points", pred_points), _device.check_points("gt_points", gt_points)
     T = _check_T("init_trans", init_trans)
     _check_volume(volume)
-    tau = _check_positive("tau", tau)
+    tau = _device.check_positive("tau", tau)
     rounds = []
     for r in voxel_rounds:
         a, b = r
-        rounds.append((_check_positive("voxel_rounds voxel factor", a), _check_positive("voxel_rounds threshold factor", b)))
+        rounds.append((_device.check_positive("voxel_rounds voxel factor", a), _device.check_positive("voxel_rounds threshold factor", b)))
     if uniform_round is not None:
-        uniform_round = _check_positive("uniform_round", uniform_round)
+        uniform_round = _device.check_positive("uniform_round", uniform_round)
     max_points = int(max_points)
     if max_points < 1:
         raise ValueError("max_points must be >= 1, got %d" % max_points)
-    pred_points, gt_points = _check_cuda(("pred_points", pred_points), ("gt_points", gt_points))
+    pred_points, gt_points = _device.check_cuda("registration", ("pred_points", pred_points), ("gt_points", gt_points))
     dev = pred_points.device
     eye = np.identity(4)
 

@@ -21,7 +21,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _device, _lib
 
 BLOCK = 8
 VOXELS = BLOCK ** 3
@@ -112,9 +112,6 @@ class TSDFVolume:
         self.reset()
 
     # -- plumbing ---------------------------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _vol(self):
         v = _lib.TsdfVolume()
         v.voxel_length, v.sdf_trunc, v.capacity, v.slot_bits = self.voxel_length, self.sdf_trunc, self.capacity, self.slot_bits
@@ -186,11 +183,8 @@ class TSDFVolume:
         view.camera_to_world[:] = [float(x) for x in c2w[:3].reshape(-1)]
         d = depth.contiguous()
         c = None if color is None else color.contiguous()
-        with torch.cuda.device(self.device):
-            rc = self._lib.ibgs_tsdf_integrate(self._stream(), ctypes.byref(self._vol()), ctypes.byref(view), d.data_ptr(),
-                                               None if c is None else c.data_ptr(), 0 if dedup else _lib.TSDF_FLAG_NO_DEDUP)
-        if rc < 0:
-            raise RuntimeError("ibgs_tsdf_integrate failed (%d): %s" % (rc, _lib.last_error()))
+        _device.call(self.device, "ibgs_tsdf_integrate", ctypes.byref(self._vol()), ctypes.byref(view), d.data_ptr(), None if c is None else c.data_ptr(),
+                     0 if dedup else _lib.TSDF_FLAG_NO_DEDUP)
 
     def integrate_view(self, camera, depth, color=None, depth_trunc=math.inf):
         """integrate() with the intrinsics Fx, Fy, Cx, Cy of a reference `Camera` (or simple_scene.SimpleCamera) and the pose render.py:275-277
@@ -223,9 +217,7 @@ class TSDFVolume:
             sc.order, sc.rank, sc.vinfo, sc.vcount, sc.fcount = (order.data_ptr(), mc["rank"].data_ptr(), mc["vinfo"].data_ptr(),
                                                                  mc["vcount"].data_ptr(), mc["fcount"].data_ptr())
             vol = self._vol()
-            rc = self._lib.ibgs_tsdf_mesh_count(self._stream(), ctypes.byref(vol), ctypes.byref(sc))
-            if rc < 0:
-                raise RuntimeError("ibgs_tsdf_mesh_count failed (%d): %s" % (rc, _lib.last_error()))
+            _device.call(self.device, "ibgs_tsdf_mesh_count", ctypes.byref(vol), ctypes.byref(sc))
             c = self._counters()          # the one read-back: overflow, and the totals that size the outputs
             self._raise_if_failed(c)
             V, F = c["vertices"], c["faces"]
@@ -233,10 +225,8 @@ class TSDFVolume:
             nrm = torch.empty(V, 3, dtype=torch.float32, device=self.device)
             col = torch.empty(V, 3, dtype=torch.float32, device=self.device)
             faces = torch.empty(F, 3, dtype=torch.int32, device=self.device)
-            rc = self._lib.ibgs_tsdf_mesh_emit(self._stream(), ctypes.byref(vol), ctypes.byref(sc), V, F, vert.data_ptr(), nrm.data_ptr(),
-                                               col.data_ptr(), faces.data_ptr())
-            if rc < 0:
-                raise RuntimeError("ibgs_tsdf_mesh_emit failed (%d): %s" % (rc, _lib.last_error()))
+            _device.call(self.device, "ibgs_tsdf_mesh_emit", ctypes.byref(vol), ctypes.byref(sc), V, F, vert.data_ptr(), nrm.data_ptr(), col.data_ptr(),
+                         faces.data_ptr())
         return TriangleMesh(vert, faces, col, nrm)
 
     def mesh_overruns(self):
