@@ -31,6 +31,12 @@ EXTRA = {
     "render_bwd": ["-fno-slp-vectorize", "-fno-signed-zeros"],
 }
 ARCH = "gfx950"
+BASE_FLAGS = ["-O3", "-fPIC", "-std=c++17"]
+
+
+def compile_flags(name):
+    """Every flag a translation unit is compiled with, target included (tools/hot_loop_isa.py reads its assembly with the same list)."""
+    return ["--offload-arch=" + ARCH] + BASE_FLAGS + EXTRA.get(name, [])
 # headers that only one unit includes: hashed into that unit's profile stamp alone (tu_shas), rebuild triggers like the others
 UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "mesh": [os.path.join(HERE, "..", "include", "ibgs_mesh.h")],
                 "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")],
@@ -128,7 +134,7 @@ def build(force=False, verbose=False):
         newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
-        cmd = [hipcc, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-c", src, "-o", obj] + EXTRA.get(name, [])
+        cmd = [hipcc] + compile_flags(name) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)

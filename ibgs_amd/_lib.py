@@ -115,7 +115,7 @@ class BackwardArgs(ctypes.Structure):
 EXPORTS = ["ibgs_required_geom", "ibgs_required_img", "ibgs_required_binning", "ibgs_required_tex",
            "ibgs_forward", "ibgs_backward", "ibgs_mark_visible", "ibgs_tile_order_slots",
            "ibgs_geom_offset", "ibgs_img_offset", "ibgs_binning_offset",
-           "ibgs_sizeof_forward_args", "ibgs_sizeof_backward_args", "ibgs_timing_enable", "ibgs_timing_collect",
+           "ibgs_sizeof_forward_args", "ibgs_sizeof_backward_args", "ibgs_grad_acc_offsets_fit32", "ibgs_timing_enable", "ibgs_timing_collect",
            "ibgs_required_knn", "ibgs_knn_mean_dist2", "ibgs_sh_grad_from_views", "ibgs_adam_step", "ibgs_adam_step_sh",
            "ibgs_required_compact", "ibgs_compact_plan", "ibgs_compact_apply", "ibgs_densify_stats", "ibgs_required_deterministic", "ibgs_required_geo_table", "ibgs_required_deterministic_for", "ibgs_required_geo_table_for", "ibgs_last_forward_stats", "ibgs_check_async",
            "ibgs_required_l1", "ibgs_l1_loss", "ibgs_l1_grad", "ibgs_l1_rescale",
@@ -341,6 +341,8 @@ def load():
                     (lib.ibgs_pcreg_moments, [vp, i32, vp, vp, i32, vp, vp, vp, sz, vp, vp])):
         f.restype = i32
         f.argtypes = args
+    lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
+    lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t
     lib.ibgs_sizeof_backward_args.restype = ctypes.c_size_t
     if (lib.ibgs_sizeof_forward_args() != ctypes.sizeof(ForwardArgs)

@@ -12,6 +12,9 @@ constexpr int TILE = IBGS_TILE;
 constexpr int WAVE = 64;
 constexpr int REC_FLOATS = 16;   // one 64-byte record per Gaussian (see GaussRec)
 constexpr int GACC_FLOATS = 16;  // one 64-byte gradient accumulation row per Gaussian
+// Does every byte offset into an accumulation arena of P rows fit 32 unsigned bits (P * 64 <= 2^32)?  Then the colour backward adds to a row at
+// (scalar base) + (one 32-bit register per lane); beyond that it forms 64-bit addresses (render_bwd.hip).  The host decides, once per launch.
+constexpr bool grad_acc_offsets_fit32(long long P) { return P >= 0 && P <= (1ll << 32) / (long long)(GACC_FLOATS * sizeof(float)); }
 
 // Field indices of the per-Gaussian render record written by preprocess and staged (as 16-byte
 // quads) by the render kernels.  Quad 0 = {x, y, opacity, pad}, quad 1 = {conic a,b,c, dist},

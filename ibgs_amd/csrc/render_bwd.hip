@@ -57,6 +57,7 @@ struct BwdParams {
     const uint32_t* order;      // balanced launch order of the colour kernel: workgroup -> tile (0xFFFFFFFF: none), nullptr: the tile map decides
     int slab_ipt;         // rows per list entry in `slab` when that is not the body's own waves per tile (hybrid kernel: 4), else 0
     int hybrid_grid1;     // hybrid colour kernel: slots of `order` = workgroups that are a tile's first wave (hybrid_item, common.h)
+    int acc32;            // every byte offset into gacc fits 32 unsigned bits (grad_acc_offsets_fit32, common.h): the colour body's atomic takes gacc as its scalar base
     float* slab;          // IBGS_FLAG_DETERMINISTIC: (R x waves per tile) x 16, one row per (list entry, wave of its tile), written instead of the atomics (else nullptr)
 };
 
@@ -203,10 +204,12 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
     const bool lds_red = LDSRED && bg0 && p.slab == nullptr;                              // wave-uniform
     float* const s_gpl = reinterpret_cast<float*>(&s_gpix[0][0]);                         // lds_red: [4][3][WAVE] planes r, g, b per quadrant, 3 KB
     float* const s_red = s_gpl + 4 * 3 * WAVE;                                            //          the reducer's 1 KB
+    // the lane's byte offsets into both layouts, 4 L (planes, the reducer's stores) and 16 L (float4 entries, the reducer's read): TWO registers held across
+    // the loops, every LDS access of the lane an immediate offset from one of them (lds_at, wave_reduce.h)
+    const uint32_t lane4 = lane_byte_offset<2>(lane), lane16 = lane_byte_offset<4>(lane);
     static_assert(!LDSRED || 4 * 3 * WAVE * sizeof(float) + LDS_REDUCE12_BYTES <= 4 * WAVE * sizeof(float4), "dL/dC and the reduce buffer share s_gpix's 4 KB");
-    int col = lds_red ? lds_reduce12_column(lane) : reduce12_column(lane);
-    if (col >= 11) col = -1;
-    float* const acc_col = (p.slab ? p.slab : p.gacc) + col;          // the lane's column of whichever accumulator this launch writes: ONE pointer held across the loops (dereferenced where col >= 0 only)
+    const int col = lds_red ? lds_reduce12_column(lane) : reduce12_column(lane);
+    const int col4 = (col < 0 || col >= 11) ? -4 : col * 4;          // byte offset of the lane's column in a 64-byte accumulation row (< 0: the lane holds no total): ONE register held across the loops
     constexpr int IPT = 4 / PPL;
     const int quad0 = sub * PPL;
     const int W = p.cam.W, H = p.cam.H;
@@ -242,6 +245,21 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
     // entries >= top contribute to no pixel of this wave; readfirstlane makes the loop control scalar (nmax is the same in
     // every lane after the butterfly, which the compiler cannot see)
     int top = __builtin_amdgcn_readfirstlane(min((int)nmax, n));
+    // the wave's one atomic instruction per entry.  Rows are 64 bytes, so while P * 64 fits 32 unsigned bits (p.acc32, the host's word) the address is the scalar
+    // base gacc plus ONE 32-bit register, id * 64 + col4; beyond that the row's 64-bit address, formed on the scalar unit, is the base.  (No test allocates an
+    // arena of more than 2^26 rows: the second branch is covered by review only -- id is wave-uniform, the readfirstlane sits inside `col4 >= 0`, so it reads an
+    // active lane, and the row's address is formed in size_t.  tests/test_kernel_resources.py tests the host's choice between the two.)
+    auto add_to_row = [&](const uint32_t id, const float tot) {
+        if (p.acc32) atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(p.gacc) + (id * (uint32_t)(GACC_FLOATS * sizeof(float)) + (uint32_t)col4)), tot);
+        else atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(p.gacc + (size_t)__builtin_amdgcn_readfirstlane(id) * GACC_FLOATS) + (uint32_t)col4), tot);          // (id is the same in every lane: the row's 64-bit address is formed on the scalar unit)
+    };
+    // ... or, in the deterministic mode, its store to the slab row of (list entry, wave of the tile)
+    auto store_to_slab = [&](const uint32_t k, const float tot) {
+        float* const row = p.slab + ((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS;          // wave-uniform
+        uint32_t off = (uint32_t)col4;
+        asm volatile("" : "+v"(off));          // (else slab + col4 is formed once in front of the loops: a 64-bit pointer per lane that the kernel has no registers for)
+        *reinterpret_cast<float*>(reinterpret_cast<char*>(row) + off) = tot;
+    };
 
     while (top > 0) {
         const int count = min(CHUNK, top);
@@ -254,7 +272,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
             float4 c1 = r[1];
             risky = conic_takes_ref_power(c1.x, c1.y, c1.z);
             stage_for_exp2(ra, c1);                            // as the forward stages them (common.h): same numbers, same decisions
-            s_rec[0][lane] = ra; s_rec[1][lane] = c1; s_rec[2][lane] = r[2];
+            lds_store4(&s_rec[0][0], lane16, ra); lds_store4(&s_rec[1][0], lane16, c1); lds_store4(&s_rec[2][0], lane16, r[2]);          // = s_rec[.][lane]
         }
         const uint64_t riskm = p.power_skip ? __builtin_amdgcn_ballot_w64(risky) : 0ull;      // near-singular conics: the forward's rare branch
         // pixels that take part: k < n_contrib.  k runs from top-1 down to top-count in this chunk and a pixel only ever
@@ -340,16 +358,16 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         if (__builtin_amdgcn_ballot_w64(rany) != 0ull) {
                             float v[12] = {rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rR, rG, rB, 0.f};
                             const float tot = wave_transpose_reduce12(v, lane);
-                            if (col >= 0) {
-                                if (p.slab) acc_col[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS] = tot;
-                                else atomicAdd(acc_col + (size_t)gid * GACC_FLOATS, tot);
+                            if (col4 >= 0) {
+                                if (p.slab) store_to_slab(k, tot);
+                                else add_to_row(gid, tot);
                             }
                         }
                         continue;
                     }
                 }
                 float Q[PPL], aX = 0.f, aY = 0.f, vR = 0.f, vG = 0.f, vB = 0.f;
-                bool any = false;
+                uint64_t anym = 0ull;          // OR of the quadrants' lane masks: "somebody blends this entry" stays on the scalar unit
                 IBGS_LANES_ADD(0, 1);
 #pragma unroll
                 for (int q = 0; q < PPL; q++) {
@@ -357,8 +375,8 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                     const uint64_t live = STABLE ? ncm[q] : __builtin_amdgcn_ballot_w64(k < ncontrib[q]);
                     const uint64_t okm = live & __builtin_amdgcn_ballot_w64(p2q[q] <= ALPHA_SKIP_E);
                     Q[q] = 0.f;
+                    anym |= okm;
                     if (okm != 0ull) {
-                        any = true;
                         IBGS_LANES_ADD(2, 64); IBGS_LANES_ADD(3, __builtin_popcountll(okm));
                         // lanes that fail the test run the same instructions with G = 0: alpha = 0 leaves T and S
                         // unchanged (1 / (1 - 0) = 1 exactly) and every sum receives a zero
@@ -370,8 +388,8 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         T[q] = T[q] * rinv;
                         const float w = alpha * T[q];
                         float4 gp;
-                        if constexpr (LR) gp = make_float4(s_gpl[(q * 3 + 0) * WAVE + lane], s_gpl[(q * 3 + 1) * WAVE + lane], s_gpl[(q * 3 + 2) * WAVE + lane], 0.f);
-                        else gp = s_gpix[q][lane];
+                        if constexpr (LR) gp = make_float4(*lds_at<float>(s_gpl, lane4 + (q * 3 + 0) * WAVE * 4), *lds_at<float>(s_gpl, lane4 + (q * 3 + 1) * WAVE * 4), *lds_at<float>(s_gpl, lane4 + (q * 3 + 2) * WAVE * 4), 0.f);
+                        else gp = lds_load4(s_gpix, lane16 + q * WAVE * 16);
                         // S = (colour behind this Gaussian) . (pixel gradient): scalar form of the reference's per-channel
                         // accum_rec / last_color / last_alpha recurrence (backward.cu:665-669), folded into one fma:
                         // behind_k = alpha_k c_k + (1 - alpha_k) behind_{k+1} = behind_{k+1} + alpha_k (c_k - behind_{k+1})
@@ -386,7 +404,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         if constexpr (ABS) { aX = fmaf(fabsf(qv), fabsf(lxq[q]), aX); aY = fmaf(fabsf(qv), fabsf(lyq[q]), aY); }      // |a b| = |a| |b|: one v_fma with source modifiers
                     }
                 }
-                if (__builtin_amdgcn_ballot_w64(any) != 0ull) {   // wave-uniform
+                if (anym != 0ull) {   // wave-uniform
                     IBGS_LANES_ADD(1, 1);
                     // v[]: 0 Sx, 1 Sy, 2 Ax, 3 Ay, 4 Sxx, 5 Sxy, 6 Syy, 7 S0, 8-10 rgb (= grad_acc columns)
                     float v[12];
@@ -407,12 +425,12 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                     v[2] = aX; v[3] = aY;          // (conic * d was formed with the scaled conic: preprocess_bwd multiplies these two sums by EXP2_UNSCALE)
                     v[8] = vR; v[9] = vG; v[10] = vB; v[11] = 0.f;
                     float tot;
-                    if constexpr (LR) tot = wave_lds_reduce12(v, lane, s_red);
+                    if constexpr (LR) tot = wave_lds_reduce12(v, lane, s_red, lane4, lane16);
                     else tot = wave_transpose_reduce12(v, lane);
                     const uint32_t id = __float_as_uint(q0.w);
-                    if (col >= 0) {
-                        if (!LR && p.slab) acc_col[((size_t)(r0 + k) * (p.slab_ipt ? p.slab_ipt : IPT) + (size_t)sub) * GACC_FLOATS] = tot;      // wave-uniform choice
-                        else atomicAdd(acc_col + (size_t)id * GACC_FLOATS, tot);
+                    if (col4 >= 0) {
+                        if (!LR && p.slab) store_to_slab(k, tot);      // wave-uniform choice
+                        else add_to_row(id, tot);
                     }
                 }
             }
@@ -1046,7 +1064,7 @@ int launch_render_backward(hipStream_t s, const ibgs_backward_args& a, const Geo
     p.valid_idx = im.valid_idx; p.valid_w = im.valid_w;
     p.depth_pixels = a.out_depth; p.warped_pixels = a.out_warped;
     p.dL_dcolor = a.dL_dcolor; p.dL_dnormal = a.dL_dnormal; p.dL_ddepth = a.dL_ddepth; p.dL_dwarped = a.dL_dwarped;
-    p.gacc = a.grad_acc; p.slab = slab; p.order = nullptr; p.slab_ipt = 0; p.hybrid_grid1 = 0;
+    p.gacc = a.grad_acc; p.acc32 = grad_acc_offsets_fit32((long long)a.P) ? 1 : 0; p.slab = slab; p.order = nullptr; p.slab_ipt = 0; p.hybrid_grid1 = 0;
     p.slot_c = im.slot_c; p.meta = im.meta; p.tab = geo_tab;
     p.tab_slots = (a.buffer_length >= 1 && a.buffer_length < IBGS_MAX_BUFFER_LENGTH) ? a.buffer_length + 1 : IBGS_MAX_BUFFER_LENGTH;          // as ibgs_required_geo_table_for sizes it
     const int nt = p.ntiles;

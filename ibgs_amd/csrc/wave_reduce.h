@@ -37,6 +37,11 @@ __device__ __forceinline__ float min_099(float x)
     return r;
 }
 
+// Pins two values to the place they were computed at (no instruction).  The callers use a reducer's result under `if (column >= 0)`; left alone the
+// optimiser sinks the last fold's adds into that branch, away from their DPP moves, and each fold then costs v_mov 0 + v_mov_dpp + v_add instead of
+// the one v_add_f32_dpp of the stages before it.
+#define IBGS_KEEP_HERE(a, b) asm volatile("" : "+v"(a), "+v"(b))
+
 // v_permlane32_swap: lanes [32,63] of `a` <-> lanes [0,31] of `b`; v_permlane16_swap: odd 16-lane rows of
 // `a` <-> even rows of `b` (lane maps verified on hardware by tests/csrc/probe_dpp.hip).  Inline asm because
 // hipcc (ROCm 7.2) mis-assigns the second result of __builtin_amdgcn_permlane{16,32}_swap (it emitted
@@ -79,6 +84,7 @@ __device__ __forceinline__ float wave_transpose_reduce12(float (&v)[12], int lan
     A += IBGS_DPP(0.f, A, 0x141 /* row_half_mirror */, 0xF); B += IBGS_DPP(0.f, B, 0x141, 0xF);
     A += IBGS_DPP(0.f, A, 0xB1 /* quad_perm [1,0,3,2] */, 0xF); B += IBGS_DPP(0.f, B, 0xB1, 0xF);
     A += IBGS_DPP(0.f, A, 0x4E /* quad_perm [2,3,0,1] */, 0xF); B += IBGS_DPP(0.f, B, 0x4E, 0xF);
+    IBGS_KEEP_HERE(A, B);
     return (lane & 15) == 1 ? B : A;
 }
 
@@ -93,7 +99,7 @@ __device__ __forceinline__ float wave_transpose_reduce12(float (&v)[12], int lan
 // go out back to back: the wave waits for one LDS round trip, not three (counted lgkmcnt, placed by the compiler).  The fences
 // keep the compiler from moving a read over the stores around it; at wavefront scope they emit no instruction.
 // The three partial sums per lane are then folded over the row's 16 lanes as the butterfly's tail folds its three values.
-// 21 VALU instructions (the read offset, 9 adds, 9 DPP adds, 2 selects), 12 ds_write_b32 (hipcc pairs them: 6 ds_write2st64_b32), 3 ds_read_b128.
+// 20 VALU instructions (9 adds, 9 DPP adds, 2 selects; the two byte offsets are the caller's, below), 12 ds_write_b32 (hipcc pairs them: 6 ds_write2st64_b32), 3 ds_read_b128.
 // In: v[0..11] per lane.  Out: in the lanes where lds_reduce12_column(lane) = c >= 0, the sum over all 64 lanes of v[c].
 // The sum is associated differently from wave_transpose_reduce12's: equal up to rounding, not to the bit.
 constexpr int LDS_REDUCE12_BYTES = 1024;
@@ -102,21 +108,48 @@ __device__ __forceinline__ int lds_reduce12_column(int lane)
     const int row = lane >> 4, l = lane & 15;
     return l == 0 ? row : (l == 8 ? 4 + row : (l == 1 ? 8 + row : -1));
 }
-__device__ __forceinline__ float wave_lds_reduce12(const float (&v)[12], int lane, float* buf /* LDS, 16-byte aligned, LDS_REDUCE12_BYTES */)
+// An LDS location by its byte offset from an LDS pointer: base + off.  With `off` in a register the optimiser cannot see into (lane_byte_offset) the access is
+// ONE ds instruction on that register, every constant folded into its offset field.
+typedef __attribute__((address_space(3))) char lds_char;
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(3))) T* lds_at(const void* base, uint32_t off)
 {
-    // The read's byte offset 16 L is formed here, once per call, and hidden from the optimiser: hoisted out of the caller's loop it is one more
-    // VGPR held beside 4 L (the stores' offset), and the colour kernels have none to spare (64 of 64: it was spilled, and reloaded per entry).
-    int rd;
-    asm volatile("v_lshlrev_b32 %0, 4, %1" : "=v"(rd) : "v"(lane));
+    return (__attribute__((address_space(3))) T*)((lds_char*)base + off);
+}
+// ... a float4 there as one 16-byte access (HIP's float4 is a class, which cannot live in a named address space: the access goes through the plain vector type)
+typedef float lds_vec4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 lds_load4(const void* base, uint32_t off)
+{
+    const lds_vec4 t = *lds_at<const lds_vec4>(base, off);
+    return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void lds_store4(void* base, uint32_t off, const float4& v)
+{
+    lds_vec4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+    *lds_at<lds_vec4>(base, off) = t;
+}
+// lane << SHIFT in a register of its own, formed here and nowhere else: left to itself the optimiser keeps the multiples of the lane number it likes (16 L and
+// -12 L in the colour backward) and adds them up again at every use inside the loops.
+template <int SHIFT>
+__device__ __forceinline__ uint32_t lane_byte_offset(int lane)
+{
+    uint32_t r;
+    asm volatile("v_lshlrev_b32 %0, %1, %2" : "=v"(r) : "n"(SHIFT), "v"(lane));
+    return r;
+}
+// lane4 = 4 L (the stores' byte offset), lane16 = 16 L (the read's): registers the caller holds across its loop (lane_byte_offset) -- the colour backward reads
+// dL/dC through the same two.
+__device__ __forceinline__ float wave_lds_reduce12(const float (&v)[12], int lane, float* buf /* LDS, 16-byte aligned, LDS_REDUCE12_BYTES */, uint32_t lane4, uint32_t lane16)
+{
     float p[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
 #pragma unroll
-        for (int c = 0; c < 4; c++) buf[c * 64 + lane] = v[4 * r + c];
+        for (int c = 0; c < 4; c++) *lds_at<float>(buf, lane4 + c * 256) = v[4 * r + c];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const float4 t = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(buf) + rd);
+        const float4 t = lds_load4(buf, lane16);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -131,7 +164,15 @@ __device__ __forceinline__ float wave_lds_reduce12(const float (&v)[12], int lan
     A += IBGS_DPP(0.f, A, 0x141 /* row_half_mirror */, 0xF); B += IBGS_DPP(0.f, B, 0x141, 0xF);
     A += IBGS_DPP(0.f, A, 0xB1 /* quad_perm [1,0,3,2] */, 0xF); B += IBGS_DPP(0.f, B, 0xB1, 0xF);
     A += IBGS_DPP(0.f, A, 0x4E /* quad_perm [2,3,0,1] */, 0xF); B += IBGS_DPP(0.f, B, 0x4E, 0xF);
+    IBGS_KEEP_HERE(A, B);
     return (lane & 15) == 1 ? B : A;
+}
+
+// The same for a caller that holds no offsets: the read's byte offset 16 L is formed here, once per call, hidden from the optimiser (hoisted out of a
+// caller's loop it is one more VGPR held beside 4 L).
+__device__ __forceinline__ float wave_lds_reduce12(const float (&v)[12], int lane, float* buf /* LDS, 16-byte aligned, LDS_REDUCE12_BYTES */)
+{
+    return wave_lds_reduce12(v, lane, buf, (uint32_t)lane * 4u, lane_byte_offset<4>(lane));
 }
 
 // ---- 16 values (geo backward: 15 live) ---------------------------------------------------------

@@ -439,6 +439,10 @@ int32_t ibgs_timing_collect(float* ms /* IBGS_NUM_STAGES */, int32_t* launches /
 size_t ibgs_sizeof_forward_args(void);
 size_t ibgs_sizeof_backward_args(void);
 
+/* 1 while every byte offset into a gradient accumulation arena of P rows (64 bytes each) fits 32 unsigned bits, P <= 2^26: the colour backward then
+   addresses a row by a 32-bit offset from the arena's base, else by 64-bit addresses.  ibgs_backward decides with this function; exported for tests. */
+int32_t ibgs_grad_acc_offsets_fit32(int64_t P);
+
 const char* ibgs_last_error(void);
 const char* ibgs_version(void);
 
