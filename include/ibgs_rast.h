@@ -248,7 +248,8 @@ typedef struct ibgs_backward_args {
     const float* dL_ddepth;   /* 1 x H x W */
     const float* dL_dwarped;  /* 15 x H x W   (both NULL: the median / warp window pass of the backward is not run and `tex` / `geo_table` are not touched -- same
                                  gradients, bit for bit under IBGS_FLAG_DETERMINISTIC, as zero-filled arrays) */
-    /* scratch: P x 16 floats, ZEROED by the caller (per-Gaussian accumulation rows) */
+    /* scratch: P x 16 floats, ZEROED by the caller (per-Gaussian accumulation rows).  The blend ADDS to what arrives in the rows and the per-Gaussian stage
+       reads them as they then stand: with R = 0 no blend runs and that stage runs on the rows as given (tests/test_gpu_bwd_rows.py relies on it) */
     float* grad_acc;
     /* gradient outputs: fully overwritten (dL_dscale / dL_drot only when scales is given, dL_dsh only when shs is) */
     float* dL_dmean2D;     /* P x 3 */

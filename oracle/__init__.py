@@ -23,6 +23,7 @@ _SO_FMA = os.path.join(_HERE, "_build", "libibgs_oracle_fma.so")
 _SO_F64 = os.path.join(_HERE, "_build", "libibgs_oracle_f64.so")
 _SO_ACC32 = os.path.join(_HERE, "_build", "libibgs_oracle_acc32.so")
 _SO_LFORM = os.path.join(_HERE, "_build", "libibgs_oracle_lform.so")
+_SO_F64_LFORM = os.path.join(_HERE, "_build", "libibgs_oracle_f64_lform.so")
 _RT = np.float32          # element type of the float arrays at the C interface: float32, float64 inside `variant("f64")`
 _SRC = os.path.join(_HERE, "ibgs_oracle.c")
 _lib = None
@@ -38,10 +39,13 @@ def build(force=False):
     the reference's own arithmetic leaves undetermined -- tests use it as the noise floor of ill-conditioned quantities.
     A third build, `variant("f64")`, turns every float of the source into a double (-DORC_F64): the arbiter for ill-conditioned quantities --
     a float build is as good as its distance from this one.  A fourth, `variant("acc32")` (-DORC_ACC_FLOAT), is the oracle proper with its per-Gaussian gradient
-    sums kept in float like the reference's atomicAdd (single-threaded, pixel order): a diagnostic for what float accumulation alone costs."""
+    sums kept in float like the reference's atomicAdd (single-threaded, pixel order): a diagnostic for what float accumulation alone costs.
+    `variant("lform")` is that build with the conic sums and the chain's first step in the l-form of the HIP path's near-singular conics (-DORC_LFORM), and
+    `variant("f64_lform")` the float64 build with the same define: the arbiter of the l-form chain (tests/bwd_rows.py)."""
     os.makedirs(os.path.dirname(_SO), exist_ok=True)
     for so, flags in ((_SO, ["-ffp-contract=off"]), (_SO_FMA, ["-ffp-contract=fast", "-mfma"]), (_SO_F64, ["-ffp-contract=off", "-DORC_F64"]),
-                      (_SO_ACC32, ["-ffp-contract=off", "-DORC_ACC_FLOAT"]), (_SO_LFORM, ["-ffp-contract=off", "-DORC_ACC_FLOAT", "-DORC_LFORM"])):
+                      (_SO_ACC32, ["-ffp-contract=off", "-DORC_ACC_FLOAT"]), (_SO_LFORM, ["-ffp-contract=off", "-DORC_ACC_FLOAT", "-DORC_LFORM"]),
+                      (_SO_F64_LFORM, ["-ffp-contract=off", "-DORC_F64", "-DORC_LFORM"])):
         if (not force) and os.path.exists(so) and os.path.getmtime(so) >= os.path.getmtime(_SRC):
             continue
         subprocess.check_call(["gcc", "-O2"] + flags + ["-fno-fast-math", "-fopenmp", "-shared", "-fPIC", "-o", so, _SRC, "-lm"])
@@ -70,9 +74,9 @@ class variant:
     build in which every float is a double (inputs are converted, results come back as float64 arrays) -- see build()."""
 
     def __init__(self, name):
-        assert name in ("fma", "plain", "f64", "acc32", "lform")
-        self.path = {"fma": _SO_FMA, "plain": _SO, "f64": _SO_F64, "acc32": _SO_ACC32, "lform": _SO_LFORM}[name]
-        self.rt = np.float64 if name == "f64" else np.float32
+        assert name in ("fma", "plain", "f64", "acc32", "lform", "f64_lform")
+        self.path = {"fma": _SO_FMA, "plain": _SO, "f64": _SO_F64, "acc32": _SO_ACC32, "lform": _SO_LFORM, "f64_lform": _SO_F64_LFORM}[name]
+        self.rt = np.float64 if name in ("f64", "f64_lform") else np.float32
 
     def __enter__(self):
         global _lib, _RT
@@ -213,12 +217,9 @@ def backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=No
     means3D = np.ascontiguousarray(np.asarray(inp["means3D"], dtype=_RT)).reshape(-1, 3); P = means3D.shape[0]
     W, H = int(inp["W"]), int(inp["H"])
     shs = _f32(inp.get("shs")); colors_precomp = _f32(inp.get("colors_precomp"))
-    scales = _f32(inp.get("scales")); rotations = _f32(inp.get("rotations"))
     cov3D_precomp = _f32(inp.get("cov3D_precomp")); all_map = _f32(inp.get("all_map"))
-    vm = _f32(inp["viewmatrix"]).reshape(-1); pm = _f32(inp["projmatrix"]).reshape(-1)
-    campos = _f32(inp["campos"]).reshape(-1); bg = _f32(inp["bg"]).reshape(-1)
-    D = int(inp.get("sh_degree", 0)); M = 0 if shs is None else int(shs.shape[1])
-    mod = float(inp.get("scale_modifier", 1.0))
+    bg = _f32(inp["bg"]).reshape(-1)
+    M = 0 if shs is None else int(shs.shape[1])
     tanx, tany = float(inp["tanfovx"]), float(inp["tanfovy"])
     render_geo = bool(inp.get("render_geo", False))
     n_src = int(inp.get("n_src", 1))
@@ -258,13 +259,33 @@ def backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=No
     res["dL_dmeans2D"][:, :2] = acc_m; res["dL_dmeans2D_abs"][:, :2] = acc_ma
     res["dL_dconic"][:, 0] = acc_c[:, 0]; res["dL_dconic"][:, 1] = acc_c[:, 1]; res["dL_dconic"][:, 3] = acc_c[:, 2]
     res["dL_dopacity"][:, 0] = acc_o; res["dL_dcolors"][:] = acc_col; res["dL_dall_map"][:] = acc_am
-    cov = cov3D_precomp if cov3D_precomp is not None else fwd["cov3D"]
-    L.orc_preprocess_backward(_ci(P), _ci(D), _ci(M), _p(means3D), _p(fwd["radii"]), _p(shs), _p(fwd["clamped"]),
-                              _p(scales), _p(rotations), _cf(mod), _p(cov), _p(vm), _p(pm), _p(campos),
-                              _ci(W), _ci(H), _cf(tanx), _cf(tany),
-                              _p(res["dL_dmeans2D"]), _p(res["dL_dconic"]), _p(res["dL_dcolors"]),
-                              _p(res["dL_dmeans3D"]), _p(res["dL_dcov3D"]), _p(res["dL_dsh"]),
-                              _p(res["dL_dscales"]), _p(res["dL_drotations"]))
+    pre = preprocess_backward(inp, fwd["radii"], fwd["clamped"], cov3D_precomp if cov3D_precomp is not None else fwd["cov3D"],
+                              res["dL_dmeans2D"], res["dL_dconic"], res["dL_dcolors"])
+    res.update(pre)
+    return res
+
+
+def preprocess_backward(inp, radii, clamped, cov3D, dL_dmean2D, dL_dconic, dL_dcolors):
+    """The per-Gaussian stage alone (orc_preprocess_backward: B3 + B4) on gradients the caller chooses: dL_dmean2D (P,3; x, y used), dL_dconic (P,4; x, y, w
+    used -- inside variant("lform") / variant("f64_lform") they are dL/dcov2D's a, b, c instead), dL_dcolors (P,3).  `radii` (P,) int32, `clamped` (P,3) uint8 and
+    `cov3D` (P,6) are taken as given (a forward's, of either implementation).  Returns dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations."""
+    L = lib()
+    means3D = np.ascontiguousarray(np.asarray(inp["means3D"], dtype=_RT)).reshape(-1, 3); P = means3D.shape[0]
+    shs = _f32(inp.get("shs")); scales = _f32(inp.get("scales")); rotations = _f32(inp.get("rotations"))
+    M = 0 if shs is None else int(shs.shape[1])
+    res = {"dL_dmeans3D": np.zeros((P, 3), _RT), "dL_dcov3D": np.zeros((P, 6), _RT), "dL_dsh": np.zeros((P, M, 3), _RT),
+           "dL_dscales": np.zeros((P, 3), _RT), "dL_drotations": np.zeros((P, 4), _RT)}
+    if P == 0:
+        return res
+    radii = np.ascontiguousarray(np.asarray(radii, np.int32)).reshape(P); clamped = np.ascontiguousarray(np.asarray(clamped, np.uint8)).reshape(P, 3)
+    g2 = np.ascontiguousarray(np.asarray(dL_dmean2D, dtype=_RT)).reshape(P, 3); gc = np.ascontiguousarray(np.asarray(dL_dconic, dtype=_RT)).reshape(P, 4)
+    gcol = np.ascontiguousarray(np.asarray(dL_dcolors, dtype=_RT)).reshape(P, 3); cov = np.ascontiguousarray(np.asarray(cov3D, dtype=_RT)).reshape(P, 6)
+    vm = _f32(inp["viewmatrix"]).reshape(-1); pm = _f32(inp["projmatrix"]).reshape(-1); campos = _f32(inp["campos"]).reshape(-1)          # (kept alive across the call)
+    L.orc_preprocess_backward(_ci(P), _ci(int(inp.get("sh_degree", 0))), _ci(M), _p(means3D), _p(radii), _p(shs), _p(clamped),
+                              _p(scales), _p(rotations), _cf(float(inp.get("scale_modifier", 1.0))), _p(cov), _p(vm), _p(pm), _p(campos),
+                              _ci(int(inp["W"])), _ci(int(inp["H"])), _cf(float(inp["tanfovx"])), _cf(float(inp["tanfovy"])),
+                              _p(g2), _p(gc), _p(gcol),
+                              _p(res["dL_dmeans3D"]), _p(res["dL_dcov3D"]), _p(res["dL_dsh"]), _p(res["dL_dscales"]), _p(res["dL_drotations"]))
     return res
 
 
