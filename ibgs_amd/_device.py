@@ -1,4 +1,4 @@
-"""What the geometry units (knn, tsdf, mesh, mesh_eval, registration) share on the Python side: how the library is called on a tensor's device and
+"""What the geometry units (knn, tsdf, mesh, mesh_eval, registration, dtu) share on the Python side: how the library is called on a tensor's device and
 stream, how CPU tensors are refused, how state words and scratch are allocated, and the argument checks for clouds and positive numbers.  The modules of
 the training step (rasterizer, renderer, optim, ...) do not come through here: their host path is timed."""
 import math

@@ -179,6 +179,14 @@ PCREG_MAX_INDEX = (1 << 21) - 1
 PCREG_LONG_SEGMENT = 64
 PCREG_MOMENTS = 18
 
+# every symbol include/ibgs_dtu.h declares (tests/test_dtu_host.py compares the two)
+DTU_EXPORTS = ["ibgs_dtu_required_dilate_scratch", "ibgs_dtu_dilate", "ibgs_dtu_cull_vertices", "ibgs_dtu_required_cull_scratch", "ibgs_dtu_cull_count",
+               "ibgs_dtu_cull_emit", "ibgs_dtu_obs_filter", "ibgs_dtu_above_plane"]
+DTU_STATE_WORDS = 8
+DTU_BAD_FACES, DTU_BAD_POINTS, DTU_OVERRUN, DTU_VERTICES_OUT, DTU_FACES_OUT = range(5)
+DTU_MAX_RADIUS = 255
+DTU_MAX_SIDE = 65536
+
 
 _lib = None
 
@@ -339,6 +347,21 @@ def load():
                     (lib.ibgs_pcreg_voxel_count, [vp, i32, vp, vp, sz, vp, vp]),
                     (lib.ibgs_pcreg_voxel_emit, [vp, i32, vp, vp, vp, vp, sz, i32, vp, vp, vp]),
                     (lib.ibgs_pcreg_moments, [vp, i32, vp, vp, i32, vp, vp, vp, sz, vp, vp])):
+        f.restype = i32
+        f.argtypes = args
+    for name in DTU_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_dtu_required_dilate_scratch.restype = sz
+    lib.ibgs_dtu_required_dilate_scratch.argtypes = [i64, i64, i64]
+    lib.ibgs_dtu_required_cull_scratch.restype = sz
+    lib.ibgs_dtu_required_cull_scratch.argtypes = [i64, i64]
+    for f, args in ((lib.ibgs_dtu_dilate, [vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+                    (lib.ibgs_dtu_cull_vertices, [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp]),
+                    (lib.ibgs_dtu_cull_count, [vp, i32, i32, vp, vp, vp, sz, vp]),
+                    (lib.ibgs_dtu_cull_emit, [vp, i32, i32, vp, vp, vp, vp, vp, sz, f32, vp, i32, i32, vp, vp, vp, vp, vp]),
+                    (lib.ibgs_dtu_obs_filter, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, f64, vp, vp, vp]),
+                    (lib.ibgs_dtu_above_plane, [vp, i32, vp, vp, vp, vp])):
         f.restype = i32
         f.argtypes = args
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32

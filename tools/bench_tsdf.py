@@ -16,7 +16,11 @@ ground truth is the thinned sampling of the raw mesh at 1.5 densities), and skle
 points of the same clouds, a size the host finishes.
 `--tnt`: ibgs_amd/registration.py on each span's post-processed mesh: its vertices, moved by the inverse of a planted similarity, against the thinned
 sampling of the raw mesh inside a polygon volume that cuts off one corner (tau = two thirds of the voxel): every stage's time, the time of one ICP
-iteration, the whole evaluate_tnt, and the numpy restatement (tests/registration_ref.py) on `--mesh-eval-host` points of the same clouds."""
+iteration, the whole evaluate_tnt, and the numpy restatement (tests/registration_ref.py) on `--mesh-eval-host` points of the same clouds.
+`--dtu`: ibgs_amd/dtu.py on each span's meshes: dilate_masks for 49 object masks of 1600 x 1200 at radius 24 (an ellipse each), cull_vertices and cull_mesh of the
+raw mesh against them (49 cameras on two rings around the mesh), the two point filters on the sampled cloud, the whole evaluate_dtu on the post-processed mesh
+(density = a third of the voxel, max_dist = 100 densities, gt = the thinned sampling of the raw mesh), and the numpy restatement (tests/dtu_ref.py) of the
+dilation on one mask and of the vertex rule on `--mesh-eval-host` vertices, for information."""
 import argparse
 import csv
 import glob
@@ -30,11 +34,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _lib, mesh as meshpp, mesh_eval, registration, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
+from ibgs_amd import _lib, dtu, mesh as meshpp, mesh_eval, registration, renderer, simple_scene, synthetic as syn, tsdf  # noqa: E402
 from tests import scenes  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-KERNEL_FILTER = ("tsdf_", "mesh_", "meval_", "pcreg_", "scan_chunk_kernel", "scan_add_kernel")
+KERNEL_FILTER = ("tsdf_", "mesh_", "meval_", "pcreg_", "dtu_", "scan_chunk_kernel", "scan_add_kernel")
 
 
 def render_views(n, W, H, P, dev):
@@ -267,7 +271,120 @@ def print_tnt(r):
               % (h["n"], h["transform_s"], h["crop_s"], h["voxel_s"], h["nearest_s"], h["moments_s"], h["dev_voxel_ms"], h["dev_moments_ms"]))
 
 
-def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None, tnt_host=None):
+DTU_VIEWS, DTU_W, DTU_H, DTU_RADIUS = 49, 1600, 1200, 24
+
+
+def bench_dtu(raw, post, voxel, host_vertices):
+    """Stage times of ibgs_amd/dtu.py (hipEvents around the Python calls, median of 3 after a warm-up, read-backs included)."""
+    from tests import dtu_ref as ref
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps=3):
+        out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            a, b = ev(), ev()
+            a.record()
+            out = fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), out
+
+    dev = raw.vertices.device
+    n, W, H = DTU_VIEWS, DTU_W, DTU_H
+    # the post-processed mesh (the largest cluster) frames the scene: the raw mesh's bounds are those of its farthest floater
+    lo, hi = post.vertices.amin(0).cpu().numpy().astype(np.float64), post.vertices.amax(0).cpu().numpy().astype(np.float64)
+    centre, ext = (lo + hi) / 2, hi - lo
+    up_axis = int(np.argmin(ext))
+    up = np.zeros(3)
+    up[up_axis] = 1.0
+    a1, a2 = [k for k in range(3) if k != up_axis]
+    dist = 1.2 * float(ext.max())
+    P = []
+    for i in range(n):
+        az, el = 2 * np.pi * i / n, np.deg2rad(30.0 if i % 2 == 0 else 55.0)
+        eye = centre.copy()
+        eye[a1] += dist * np.cos(el) * np.cos(az)
+        eye[a2] += dist * np.cos(el) * np.sin(az)
+        eye[up_axis] += dist * np.sin(el)
+        P.append(ref.look_at(eye, centre, -up, 1.1 * W, W, H))
+    P = torch.as_tensor(np.stack(P), device=dev)
+    yy, xx = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+    masks = torch.stack([(((xx - W / 2 - 40 * np.cos(i)) / (0.45 * W)) ** 2 + ((yy - H / 2 - 30 * np.sin(i)) / (0.45 * H)) ** 2 <= 1.0) for i in range(n)]).to(torch.uint8)
+    density = voxel / 3
+    r = {"V": int(raw.vertices.shape[0]), "F": int(raw.faces.shape[0]), "density": density, "F_post": int(post.faces.shape[0])}
+    r["dilate_ms"], bits = timed(lambda: dtu.dilate_masks(masks, DTU_RADIUS))
+    r["mask_set"] = float(masks.float().mean())
+    r["cull_vertices_ms"], keep = timed(lambda: dtu.cull_vertices(raw.vertices, P, bits))
+    r["kept"] = int(keep.sum())
+    r["cull_mesh_ms"], culled = timed(lambda: dtu.cull_mesh(raw, P, bits, scale=1.0, offset=(0.0, 0.0, 0.0)))
+    r["cull_mesh_raw_ms"], _ = timed(lambda: dtu.cull_mesh(raw, P, masks, radius=DTU_RADIUS))
+    r["V2"], r["F2"] = int(culled.vertices.shape[0]), int(culled.faces.shape[0])
+    gt_cloud = mesh_eval.sample_surface(raw, 1.5 * density)
+    gt = gt_cloud[mesh_eval.downsample(gt_cloud, 1.5 * density)]
+    del gt_cloud
+    res = float(ext.max()) / 200
+    inner = np.where(np.arange(3) == up_axis, 1.0, 0.7)          # the box: 70 % of the mesh's extent across, all of it along the up axis
+    b0 = centre - inner * ext / 2
+    cells = np.ceil(inner * ext / res)
+    bb = np.stack([b0, b0 + res * cells]).astype(np.float32)
+    shape = tuple(int(x) + 1 for x in cells)
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    obs = (torch.rand(shape, generator=g, device=dev) < 0.7).to(torch.uint8)
+    plane = np.zeros(4)
+    plane[up_axis], plane[3] = 1.0, -(lo[up_axis] + 0.2 * ext[up_axis])
+    patch = 5 * res
+    cloud = mesh_eval.sample_surface(post, density)
+    r["cloud"], r["gt"], r["obs_shape"] = int(cloud.shape[0]), int(gt.shape[0]), shape
+    r["obs_filter_ms"], filt = timed(lambda: dtu.obs_mask_filter(cloud, obs, bb, res, patch))
+    r["above_plane_ms"], above = timed(lambda: dtu.above_plane(gt, plane))
+    r["inbound"], r["in_obs"], r["above"] = int(filt.inbound.sum()), int(filt.in_obs.sum()), int(above.sum())
+    del cloud, filt
+    r["evaluate_ms"], e = timed(lambda: dtu.evaluate_dtu(post, gt, obs, bb, res, plane, density=density, max_dist=100 * density, patch=patch))
+    r["evaluate_cull_ms"], ec = timed(lambda: dtu.evaluate_dtu(post, gt, obs, bb, res, plane, density=density, max_dist=100 * density, patch=patch,
+                                                                cull=dtu.Cull(P, bits)))
+    r["evaluate"], r["evaluate_cull"] = e, ec
+    if host_vertices:
+        one = masks[0].cpu().numpy()
+        t0 = time.perf_counter()
+        want = ref.dilate(one, DTU_RADIUS)
+        t1 = time.perf_counter()
+        same_d = bool(np.array_equal(ref.pack_bits(want[None])[0], bits.words[0].cpu().numpy()))
+        m = min(host_vertices, r["V"])
+        sub = raw.vertices[torch.randperm(r["V"], device=dev)[:m]].contiguous()
+        dil = ref.unpack_bits(bits.words.cpu().numpy(), W)[0]
+        hv, hP = sub.cpu().numpy(), P.cpu().numpy()
+        t2 = time.perf_counter()
+        hk = ref.cull_vertices(hv, hP, dil)
+        t3 = time.perf_counter()
+        dev_ms, dk = timed(lambda: dtu.cull_vertices(sub, P, bits))
+        r["host"] = {"dilate_one_s": t1 - t0, "dilate_equal": same_d, "n": m, "cull_s": t3 - t2, "cull_equal": bool(np.array_equal(hk, dk.cpu().numpy())),
+                     "dev_cull_ms": dev_ms}
+    return r
+
+
+def print_dtu(r):
+    print("DTU front end on the raw mesh (V %d, F %d), %d masks of %d x %d (%.0f %% set), radius %d:" % (r["V"], r["F"], DTU_VIEWS, DTU_W, DTU_H, 100 * r["mask_set"], DTU_RADIUS))
+    print("  dilate_masks (pack + dilate): %.3f ms = %.1f G pixels/s" % (r["dilate_ms"], DTU_VIEWS * DTU_W * DTU_H / r["dilate_ms"] / 1e6))
+    print("  cull_vertices (kernel + read-back): %.3f ms -> %d kept; %.1f G vertex-views/s if no thread stopped early" % (r["cull_vertices_ms"], r["kept"], r["V"] * DTU_VIEWS / r["cull_vertices_ms"] / 1e6))
+    print("  cull_mesh from dilated bits (cull + mark + 2 scans + read-back + emit + read-back): %.3f ms -> V' %d, F' %d; from raw masks (dilation included): %.3f ms"
+          % (r["cull_mesh_ms"], r["V2"], r["F2"], r["cull_mesh_raw_ms"]))
+    print("  obs_mask_filter on the %d sampled points of the post-processed mesh (F %d), ObsMask %s: %.3f ms -> %d in bounds, %d observed; above_plane on %d gt points: %.3f ms -> %d"
+          % (r["cloud"], r["F_post"], "x".join(str(x) for x in r["obs_shape"]), r["obs_filter_ms"], r["inbound"], r["in_obs"], r["gt"], r["above_plane_ms"], r["above"]))
+    print("  evaluate_dtu (sample + thin + filters + chamfer): %.3f ms; with the cull in front: %.3f ms" % (r["evaluate_ms"], r["evaluate_cull_ms"]))
+    print("    %s" % r["evaluate"])
+    print("    %s" % r["evaluate_cull"])
+    h = r.get("host")
+    if h:
+        print("  numpy restatement (host, for information): dilation of ONE mask %.2f s (x %d masks = %.0f s), equal to the device's: %s; the vertex rule on %d vertices x %d views %.2f s, "
+              "equal: %s; the device on the same vertices: %.3f ms" % (h["dilate_one_s"], DTU_VIEWS, DTU_VIEWS * h["dilate_one_s"], h["dilate_equal"], h["n"], DTU_VIEWS, h["cull_s"],
+                                                                      h["cull_equal"], h["dev_cull_ms"]))
+
+
+def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None, tnt_host=None, dtu_host=None):
     voxel = 2 * scenes.GROUND_HALF / span
     vol = tsdf.TSDFVolume(voxel, 4 * voxel, block_capacity=1 << 21)
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -322,7 +439,8 @@ def bench_voxel(views, span, dedup_ab=True, keep_mesh=None, mesh_eval_host=None,
         keep_mesh.append((mesh, cl, post))
     me = bench_mesh_eval(mesh, post, voxel, mesh_eval_host) if mesh_eval_host is not None else None
     tnt = bench_tnt(mesh, post, voxel, tnt_host) if tnt_host is not None else None
-    return {"pp": pp, "mesh_eval": me, "tnt": tnt, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
+    du = bench_dtu(mesh, post, voxel, dtu_host) if dtu_host is not None else None
+    return {"pp": pp, "mesh_eval": me, "tnt": tnt, "dtu": du, "span": span, "voxel": voxel, "ms": ms, "ms_again": ms2, "ms_nodedup": ms_nd, "active": active, "blocks": blocks, "extract_ms": ext,
             "V": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0])}
 
 
@@ -380,6 +498,7 @@ def main():
     ap.add_argument("--mesh-eval", action="store_true", help="time every stage of ibgs_amd/mesh_eval.py on each span's post-processed mesh")
     ap.add_argument("--mesh-eval-host", type=int, default=300000, help="with --mesh-eval / --tnt: points handed to the host engine (sklearn's kd-tree / the numpy restatement; 0: skip)")
     ap.add_argument("--tnt", action="store_true", help="time every stage of ibgs_amd/registration.py (evaluate_tnt) on each span's post-processed mesh")
+    ap.add_argument("--dtu", action="store_true", help="time every stage of ibgs_amd/dtu.py (dilate_masks, cull_vertices, cull_mesh, the filters, evaluate_dtu) on each span's meshes")
     a = ap.parse_args()
     if a.kstats_only:
         print_split(a.kstats, a.active, a.faces)
@@ -395,7 +514,8 @@ def main():
     first_mesh = []
     for span in [int(s) for s in a.spans.split(",")]:
         r = bench_voxel(views, span, dedup_ab=not a.no_ab, keep_mesh=first_mesh if a.mesh_restatement and not first_mesh else None,
-                        mesh_eval_host=a.mesh_eval_host if a.mesh_eval else None, tnt_host=a.mesh_eval_host if a.tnt else None)
+                        mesh_eval_host=a.mesh_eval_host if a.mesh_eval else None, tnt_host=a.mesh_eval_host if a.tnt else None,
+                        dtu_host=a.mesh_eval_host if a.dtu else None)
         act = np.array(r["active"], np.float64)
         med = lambda x: float(np.median(x))
         print("\n== ground square spans %d voxels: voxel %.6f, sdf_trunc %.6f" % (span, r["voxel"], 4 * r["voxel"]))
@@ -418,6 +538,8 @@ def main():
             print_mesh_eval(r["mesh_eval"])
         if r["tnt"]:
             print_tnt(r["tnt"])
+        if r["dtu"]:
+            print_dtu(r["dtu"])
     if ks:
         print_split(a.kstats)
     if first_mesh:
