@@ -187,6 +187,11 @@ DTU_BAD_FACES, DTU_BAD_POINTS, DTU_OVERRUN, DTU_VERTICES_OUT, DTU_FACES_OUT = ra
 DTU_MAX_RADIUS = 255
 DTU_MAX_SIDE = 65536
 
+# every symbol include/ibgs_ssim.h declares (tests/test_ssim_host.py compares the two)
+SSIM_EXPORTS = ["ibgs_ssim_required_scratch", "ibgs_ssim_tile", "ibgs_ssim_forward", "ibgs_ssim_backward"]
+SSIM_WINDOW = 11
+SSIM_MAX_SIDE = 65536
+
 
 _lib = None
 
@@ -364,6 +369,17 @@ def load():
                     (lib.ibgs_dtu_above_plane, [vp, i32, vp, vp, vp, vp])):
         f.restype = i32
         f.argtypes = args
+    for name in SSIM_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_ssim_required_scratch.restype = sz
+    lib.ibgs_ssim_required_scratch.argtypes = [i64, i64, i64]
+    lib.ibgs_ssim_tile.restype = None
+    lib.ibgs_ssim_tile.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.ibgs_ssim_forward.restype = i32
+    lib.ibgs_ssim_forward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 10 + [sz]
+    lib.ibgs_ssim_backward.restype = i32
+    lib.ibgs_ssim_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 6
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t

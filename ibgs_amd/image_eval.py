@@ -1,0 +1,69 @@
+"""The image side of the reference's evaluation (metrics.py:75-98) on the device: SSIM and PSNR per test view, and their means.
+
+`image_metrics` is one launch of the fused SSIM forward (csrc/ssim.hip, C ABI include/ibgs_ssim.h) with no per-pixel output: the same pass over the two
+images that sums the SSIM map also sums (x - y)^2 and |x - y|, so SSIM, PSNR (utils/image_utils.py:18-20) and L1 of every image of a batch cost one read of
+the batch.  `evaluate_images` stacks views of the same size into such launches and reads the numbers back once.
+
+LPIPS, the third column of the reference's table, is NOT computed: it needs the VGG weights of the `lpips` package, which this library does not ship.
+
+HIP only: raises for CPU tensors (there is no CPU path)."""
+import torch
+
+from . import losses
+
+
+def image_metrics(renders, gts):
+    """renders, gts: (N, C, H, W) (or (C, H, W): one image).  -> {"ssim": (N,), "psnr": (N,), "l1": (N,)} float32 on the device, nothing waits for it.
+    ssim = `ssim(render, gt)` per image, psnr = 20 log10(1 / sqrt(mse)) per image, l1 = mean |render - gt| per image."""
+    dims = losses._ssim_check("image_metrics", renders, gts, 11, (3, 4))
+    x = renders.detach().float().contiguous()
+    y = gts.detach().float().contiguous()
+    n = dims[0]
+    with torch.cuda.device(x.device):
+        per, mse, l1 = (torch.empty(n, dtype=torch.float32, device=x.device) for _ in range(3))
+    losses._ssim_forward(dims, x, y, per_image=per, mse=mse, l1_per_image=l1)
+    psnr = 20.0 * torch.log10(1.0 / torch.sqrt(mse))
+    return {"ssim": per, "psnr": psnr, "l1": l1}
+
+
+def evaluate_images(renders, gts, names=None):
+    """What metrics.py:75-98 computes for SSIM and PSNR.  renders, gts: a 4-D tensor each, or lists of (3, H, W) / (1, 3, H, W) tensors whose sizes may differ
+    from view to view (views of one size go into one launch).  names: one per view (default "00000", "00001", ..).
+    -> {"SSIM": mean, "PSNR": mean, "per_view": {"SSIM": {name: value}, "PSNR": {name: value}}}, Python floats, after ONE device-to-host copy.
+    LPIPS is not computed (see the module's docstring)."""
+    def views(t, what):
+        if torch.is_tensor(t):
+            if t.dim() != 4:
+                raise ValueError("evaluate_images: %s must be a 4-D tensor or a list of images, got %s" % (what, tuple(t.shape)))
+            return list(t.unbind(0))
+        out = []
+        for v in t:
+            if not torch.is_tensor(v) or v.dim() not in (3, 4) or (v.dim() == 4 and v.shape[0] != 1):
+                raise ValueError("evaluate_images: every entry of %s must be a (C, H, W) or (1, C, H, W) tensor" % what)
+            out.append(v[0] if v.dim() == 4 else v)
+        return out
+
+    r, g = views(renders, "renders"), views(gts, "gts")
+    if len(r) != len(g) or not r:
+        raise ValueError("evaluate_images: %d renders, %d ground-truth images" % (len(r), len(g)))
+    names = ["%05d" % i for i in range(len(r))] if names is None else [str(n) for n in names]
+    if len(names) != len(r) or len(set(names)) != len(names):
+        raise ValueError("evaluate_images: %d distinct names for %d views" % (len(set(names)), len(r)))
+    groups = {}
+    for i, (a, b) in enumerate(zip(r, g)):
+        if a.shape != b.shape:
+            raise ValueError("evaluate_images: view %s: render %s, ground truth %s" % (names[i], tuple(a.shape), tuple(b.shape)))
+        groups.setdefault((tuple(a.shape), a.device), []).append(i)
+    order, parts = [], []
+    for idx in groups.values():
+        m = image_metrics(torch.stack([r[i] for i in idx]), torch.stack([g[i] for i in idx]))
+        order += idx
+        parts.append(torch.stack([m["ssim"], m["psnr"]]).to(parts[0].device if parts else m["ssim"].device))
+    table = torch.cat(parts, dim=1)
+    rows = torch.cat([table, table.mean(dim=1, keepdim=True)], dim=1).tolist()          # the one copy to the host
+    per = {"SSIM": {}, "PSNR": {}}
+    pos = {view: k for k, view in enumerate(order)}
+    for i, name in enumerate(names):
+        per["SSIM"][name] = rows[0][pos[i]]
+        per["PSNR"][name] = rows[1][pos[i]]
+    return {"SSIM": rows[0][-1], "PSNR": rows[1][-1], "per_view": per}
