@@ -23,6 +23,7 @@ FLAG_DETERMINISTIC = 128
 FLAG_TEX_PACKED = 256
 FLAG_NO_REF_POWER_SKIP = 512
 FLAG_NO_ABS_GRAD = 1024
+FLAG_NO_PLAIN_CHUNKS = 2048
 FLAG_REF_ARITH = 4096
 FLAG_SRC_DEPTH_SLOTS = 8192
 PLANE_NONE, PLANE_LEARNT, PLANE_SMALLEST_AXIS = 0, 1, 2
@@ -115,7 +116,7 @@ class BackwardArgs(ctypes.Structure):
 EXPORTS = ["ibgs_required_geom", "ibgs_required_img", "ibgs_required_binning", "ibgs_required_tex",
            "ibgs_forward", "ibgs_backward", "ibgs_mark_visible", "ibgs_tile_order_slots",
            "ibgs_geom_offset", "ibgs_img_offset", "ibgs_binning_offset",
-           "ibgs_sizeof_forward_args", "ibgs_sizeof_backward_args", "ibgs_grad_acc_offsets_fit32", "ibgs_timing_enable", "ibgs_timing_collect",
+           "ibgs_sizeof_forward_args", "ibgs_sizeof_backward_args", "ibgs_grad_acc_offsets_fit32", "ibgs_clamp_free", "ibgs_clamp_free_threshold", "ibgs_timing_enable", "ibgs_timing_collect",
            "ibgs_required_knn", "ibgs_knn_mean_dist2", "ibgs_sh_grad_from_views", "ibgs_adam_step", "ibgs_adam_step_sh",
            "ibgs_required_compact", "ibgs_compact_plan", "ibgs_compact_apply", "ibgs_densify_stats", "ibgs_required_deterministic", "ibgs_required_geo_table", "ibgs_required_deterministic_for", "ibgs_required_geo_table_for", "ibgs_last_forward_stats", "ibgs_check_async",
            "ibgs_required_l1", "ibgs_l1_loss", "ibgs_l1_grad", "ibgs_l1_rescale",
@@ -382,6 +383,10 @@ def load():
     lib.ibgs_ssim_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 6
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
+    lib.ibgs_clamp_free.restype = ctypes.c_int32
+    lib.ibgs_clamp_free.argtypes = [ctypes.c_float]
+    lib.ibgs_clamp_free_threshold.restype = ctypes.c_float
+    lib.ibgs_clamp_free_threshold.argtypes = []
     lib.ibgs_sizeof_forward_args.restype = ctypes.c_size_t
     lib.ibgs_sizeof_backward_args.restype = ctypes.c_size_t
     if (lib.ibgs_sizeof_forward_args() != ctypes.sizeof(ForwardArgs)

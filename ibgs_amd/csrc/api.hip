@@ -180,6 +180,8 @@ int32_t ibgs_timing_collect(float* ms, int32_t* launches)
     g_pairs.clear();
     return 0;
 }
+int32_t ibgs_clamp_free(float neg_log2_opacity) { return clamp_free(neg_log2_opacity) ? 1 : 0; }          // the plain-chunk test of one staged record (common.h)
+float ibgs_clamp_free_threshold(void) { return CLAMP_FREE_NLO; }
 int32_t ibgs_grad_acc_offsets_fit32(int64_t P) { return grad_acc_offsets_fit32((long long)P) ? 1 : 0; }          // which atomic path the colour backward takes for P Gaussians (common.h)
 size_t ibgs_sizeof_forward_args(void) { return sizeof(ibgs_forward_args); }
 size_t ibgs_sizeof_backward_args(void) { return sizeof(ibgs_backward_args); }

@@ -118,6 +118,26 @@ __device__ __forceinline__ void stage_for_exp2(float4& pos_opacity_quad, float4&
     pos_opacity_quad.z = -__builtin_amdgcn_logf(pos_opacity_quad.z);          // v_log_f32 = log2; o = 0 -> +inf -> never passes
 }
 
+// ---- staged records whose alpha the 0.99 clamp cannot reach (round 10) ------------------------------------------------------------------
+// alpha = min(0.99, exp2(-E)) and E = nlo + q, with nlo = -log2(o) as stage_for_exp2 leaves it and q = 0.5 log2(e) d^T conic d.  For a positive definite
+// conic that does not take the reference-power branch (b^2 <= 0.999 a c, a > 0) the exact q is >= (1 - |b| / sqrt(a c)) S / 2 >= 2.5e-4 S >= 0 with
+// S = a dx^2 + c dy^2 (scaled), so the exact E is >= nlo and only rounding can take the computed E below it.  The lane's quadrant-0 pixel: a few ulp of S, and
+// q >= 2.5e-4 S outweighs them.  The other three quadrants are SHIFTED from it, E_q = P0 + 64 a - 16 l_x (+ 64 c - 16 l_y + 128 b): their rounding is a few ulp of the
+// largest intermediate, |P0| + 64 (a + c) + 128 |b|, whatever S is at the shifted pixel.  That is bounded because the conic is: preprocess adds the 0.3 low-pass to the
+// diagonal of cov2D, so a, c <= 1 / 0.3 unscaled, 2.4 scaled, |b| < 2.4, and a pixel that passes the alpha test 8 pixels from one with E up to ~64 (2.4 + 2.4 + 4.8) + 8
+// has intermediates <= ~1e3: the computed E is >= nlo - O(1e-4).  With nlo >= CLAMP_FREE_NLO = -log2(0.98) = 0.029146 (the clamp binds from -log2(0.99) = 0.014500 on)
+// that leaves 0.0146 in the exponent, two orders of magnitude more, against which v_log_f32 / v_exp_f32's 1 ulp each (1.2e-7 relative in alpha, 1e-7 absolute in nlo)
+// do not count: exp2(-E) <= 0.98 (1 + 1e-4) < 0.99 and min(0.99, exp2(-E)) is the identity.  (A record whose conic came from elsewhere than that low-pass is covered
+// while |P0| + 64 (a + c) + 128 |b| stays below ~1e5, i.e. conic entries below ~500.)  A chunk of staged records ALL of which pass (and none of which is near-singular) is "plain": the blend kernels
+// walk it with loops that hold no clamp and none of the near-singular plumbing (render_fwd.hip, render_bwd.hip).  NaN and -0 compare false: not free.
+constexpr float CLAMP_FREE_NLO = 0.029146346f;
+__host__ __device__ __forceinline__ bool clamp_free(float neg_log2_opacity) { return neg_log2_opacity >= CLAMP_FREE_NLO; }
+// ... and the whole test of one staged record, from the staged numbers (scaled conic; a > 0 with b^2 <= 0.999 a c makes the conic positive definite)
+__device__ __forceinline__ bool record_is_plain(float neg_log2_opacity, float conic_a, bool takes_ref_power)
+{
+    return clamp_free(neg_log2_opacity) && conic_a > 0.0f && !takes_ref_power;
+}
+
 // ---- the reference's `power > 0` skip (forward.cu:420, backward.cu:645) -------------------------------------------------------------
 // `power` = -0.5 (a dx^2 + c dy^2) - b dx dy is <= 0 for a positive definite conic; the reference's fp32 evaluation can come out
 // positive only through rounding: |rounding| <= ~4 ulp of S = a dx^2 + c dy^2, while -power >= S (1 - |b| / sqrt(a c)) / 2, so a pair can

@@ -57,6 +57,7 @@ struct BwdParams {
     const uint32_t* order;      // balanced launch order of the colour kernel: workgroup -> tile (0xFFFFFFFF: none), nullptr: the tile map decides
     int slab_ipt;         // rows per list entry in `slab` when that is not the body's own waves per tile (hybrid kernel: 4), else 0
     int hybrid_grid1;     // hybrid colour kernel: slots of `order` = workgroups that are a tile's first wave (hybrid_item, common.h)
+    int no_plain;         // IBGS_FLAG_NO_PLAIN_CHUNKS: no chunk of the colour body counts as plain (below); tests and A/B only
     int acc32;            // every byte offset into gacc fits 32 unsigned bits (grad_acc_offsets_fit32, common.h): the colour body's atomic takes gacc as its scalar base
     float* slab;          // IBGS_FLAG_DETERMINISTIC: (R x waves per tile) x 16, one row per (list entry, wave of its tile), written instead of the atomics (else nullptr)
 };
@@ -263,7 +264,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
 
     while (top > 0) {
         const int count = min(CHUNK, top);
-        bool risky = false;
+        bool risky = false, ordinary = false;
         if (lane < count) {   // stage in processing order: slot l holds entry top-1-l
             const uint32_t id = p.point_list[r0 + (uint32_t)(top - 1 - lane)];
             const float4* r = p.rec + (size_t)id * 4;
@@ -272,9 +273,12 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
             float4 c1 = r[1];
             risky = conic_takes_ref_power(c1.x, c1.y, c1.z);
             stage_for_exp2(ra, c1);                            // as the forward stages them (common.h): same numbers, same decisions
+            ordinary = !record_is_plain(ra.z, c1.x, risky);
             lds_store4(&s_rec[0][0], lane16, ra); lds_store4(&s_rec[1][0], lane16, c1); lds_store4(&s_rec[2][0], lane16, r[2]);          // = s_rec[.][lane]
         }
         const uint64_t riskm = p.power_skip ? __builtin_amdgcn_ballot_w64(risky) : 0ull;      // near-singular conics: the forward's rare branch
+        // a PLAIN chunk (common.h: clamp_free): the 0.99 clamp binds for none of its records and none is near-singular -- decided once per chunk, the loop dispatched whole
+        const bool plain = !RISK && bg0 && !p.no_plain && __builtin_amdgcn_ballot_w64(ordinary) == 0ull;          // wave-uniform
         // pixels that take part: k < n_contrib.  k runs from top-1 down to top-count in this chunk and a pixel only ever
         // switches ON (at k = n_contrib - 1), so when the masks at both ends agree they hold for the whole chunk.
         uint64_t ncm[PPL];
@@ -285,11 +289,13 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
             stable = stable && (ncm[q] == __builtin_amdgcn_ballot_w64((uint32_t)(top - 1) < ncontrib[q]));
         }
         __syncthreads();
-        auto chunk = [&](auto stable_tag, auto bg0_tag, auto lds_tag) {
+        auto chunk = [&](auto stable_tag, auto bg0_tag, auto lds_tag, auto plain_tag) {
             constexpr bool STABLE = decltype(stable_tag)::value;
             constexpr bool BG0 = decltype(bg0_tag)::value;          // black background: the -T_final (bg . g) / (1 - alpha) term is zero
             constexpr bool LR = decltype(lds_tag)::value;           // lds_red: dL/dC in the plane layout, the moments summed through LDS
+            constexpr bool PLAIN = decltype(plain_tag)::value;      // plain chunk: alpha = o G unclamped, no near-singular record (riskm == 0) -- the same bits as the ordinary loop's
             static_assert(!LR || (BG0 && LDSRED), "the plane layout has no room for the background term");
+            static_assert(!PLAIN || (BG0 && !RISK), "plain loops exist for the black background's fast kernels only");
             for (int j = 0; j < count; j++) {
                 const uint32_t k = (uint32_t)(top - 1 - j);          // 0-based position in the tile list
                 const float4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j];
@@ -313,7 +319,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         lxq[3] = fmaf(-8.0f, cb, lxq[1]); lyq[3] = fmaf(-8.0f, cc, lyq[1]);
                     }
                 }
-                if constexpr (!RISK) {
+                if constexpr (!RISK && !PLAIN) {
                     if ((riskm >> j) & 1ull) {          // wave-uniform and rare: E from the reference's expression, `power > 0` pairs dropped (common.h); the sums: l_moments below
                         const uint32_t gid = __builtin_amdgcn_readfirstlane(__float_as_uint(q0.w));
                         const float4 g0 = p.rec[(size_t)gid * 4], g1 = p.rec[(size_t)gid * 4 + 1];
@@ -383,7 +389,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         // (exp2(-E) = o G.  The select is inline asm and the first reader of the transcendental's result: it carries its own
                         // wait state -- hipcc pads none inside asm, cdna_hip_programming.md 5.7)
                         const float oG = select_or_zero_after_trans(okm, __builtin_amdgcn_exp2f(-p2q[q]));
-                        const float alpha = min_099(oG);
+                        const float alpha = PLAIN ? oG : min_099(oG);          // (plain: the clamp is the identity, bit for bit)
                         const float rinv = __builtin_amdgcn_rcpf(1.f - alpha);
                         T[q] = T[q] * rinv;
                         const float w = alpha * T[q];
@@ -399,6 +405,8 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         vR = fmaf(w, gp.x, vR); vG = fmaf(w, gp.y, vG); vB = fmaf(w, gp.z, vB);
                         if constexpr (BG0) dL_dalpha = dL_dalpha * T[q];
                         else dL_dalpha = fmaf(dL_dalpha, T[q], gp.w * rinv);      // ... - T_final (bg . g) / (1 - alpha)
+                        // (plain: q = w dL/dalpha would save this multiply -- alpha = o G, w = o G T is at hand -- but it rounds differently: on tests/test_gpu_plain_chunks.py's
+                        // scenes dL/dscales then sat 3.2e-7 .. 3.7e-7 from the ordinary loops', 2.5 - 3.2 x the run-to-run distance of the float atomics; not taken)
                         const float qv = oG * dL_dalpha;                          // dL/dG * G
                         Q[q] = qv;
                         if constexpr (ABS) { aX = fmaf(fabsf(qv), fabsf(lxq[q]), aX); aY = fmaf(fabsf(qv), fabsf(lyq[q]), aY); }      // |a b| = |a| |b|: one v_fma with source modifiers
@@ -408,7 +416,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                     IBGS_LANES_ADD(1, 1);
                     // v[]: 0 Sx, 1 Sy, 2 Ax, 3 Ay, 4 Sxx, 5 Sxy, 6 Syy, 7 S0, 8-10 rgb (= grad_acc columns)
                     float v[12];
-                    if (!RISK && ((riskm >> j) & 1ull)) l_moments<PPL>(v, Q, dx0, dy0, ca, cb, cc);          // wave-uniform: a near-singular conic (see above)
+                    if (!RISK && !PLAIN && ((riskm >> j) & 1ull)) l_moments<PPL>(v, Q, dx0, dy0, ca, cb, cc);          // wave-uniform: a near-singular conic (see above)
                     else
                     if constexpr (PPL == 4) {
                         const float A = Q[1] + Q[3], B = Q[2] + Q[3], S0 = (Q[0] + Q[2]) + A;
@@ -435,12 +443,21 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                 }
             }
         };
+        constexpr std::true_type yes{}; constexpr std::false_type no{};
         if constexpr (LDSRED) {
-            if (lds_red) { if (stable) chunk(std::true_type{}, std::true_type{}, std::true_type{}); else chunk(std::false_type{}, std::true_type{}, std::true_type{}); }
+            if (lds_red) {
+                if (plain) { if (stable) chunk(yes, yes, yes, yes); else chunk(no, yes, yes, yes); }
+                else { if (stable) chunk(yes, yes, yes, no); else chunk(no, yes, yes, no); }
+            }
         }
         if (!lds_red) {
-            if (bg0) { if (stable) chunk(std::true_type{}, std::true_type{}, std::false_type{}); else chunk(std::false_type{}, std::true_type{}, std::false_type{}); }
-            else { if (stable) chunk(std::true_type{}, std::false_type{}, std::false_type{}); else chunk(std::false_type{}, std::false_type{}, std::false_type{}); }
+            if constexpr (!RISK) {
+                if (plain) { if (stable) chunk(yes, yes, no, yes); else chunk(no, yes, no, yes); }
+            }
+            if (!plain) {
+                if (bg0) { if (stable) chunk(yes, yes, no, no); else chunk(no, yes, no, no); }
+                else { if (stable) chunk(yes, no, no, no); else chunk(no, no, no, no); }
+            }
         }
         __syncthreads();
         top -= count;
@@ -1058,6 +1075,7 @@ int launch_render_backward(hipStream_t s, const ibgs_backward_args& a, const Geo
     p.ntiles = p.cam.gx * p.cam.gy;
     p.n_src = a.n_src; p.tex_quant = (a.flags & IBGS_FLAG_TEX_QUANT) ? 1 : 0;
     p.power_skip = render_backward_ref_arith(a.flags);
+    p.no_plain = (a.flags & IBGS_FLAG_NO_PLAIN_CHUNKS) ? 1 : 0;
     p.tile_risky = (p.power_skip & RA_ASSOC) ? im.tile_risky : nullptr;          // IBGS_FLAG_REF_ARITH: the flagged tiles go to the *_risk_kernel, the fast kernels skip them
     p.ref_to_src = a.ref_to_src; p.src_rgba = src_rgba;
     p.final_T = im.final_T; p.n_contrib = im.n_contrib; p.sum_w = im.sum_w; p.low_high = im.low_high;

@@ -47,6 +47,7 @@ struct FwdParams {
     // outputs
     float* out_color; float* out_normal; float* out_depth; float* out_cam_feat; float* out_warped;
     float* out_min_depth_diff; float* out_camera_ray; int32_t* out_mask;
+    int no_plain;        // IBGS_FLAG_NO_PLAIN_CHUNKS: no staging round of the colour pass counts as plain (render_fwd_body); tests and A/B only
 };
 
 enum { MODE_COLOR = 0, MODE_GEO = 1, MODE_DEPTH = 2 };
@@ -214,6 +215,7 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
     uint64_t riskany = 0ull;          // a staged record had a near-singular conic: the backward walks this tile with its reference-arithmetic kernel (render_bwd.hip)
     for (; base < n; base += CHUNK) {
         uint64_t riskm = 0ull;          // staged records whose conic is near-singular: the reference's power expression decides for them (common.h)
+        bool plain = false;             // colour: a PLAIN round (common.h: clamp_free) -- the 0.99 clamp binds for none of its records and none is near-singular; wave-uniform
         if constexpr (GEO) {
             float4 v = ahead;
             const int qd = lane & 3;
@@ -226,22 +228,87 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
             ahead = fetch_quad(base + CHUNK);
         } else {   // stage up to 64 records: lane e loads the quads of entry base+e
             const int e = base + lane;
-            bool risky = false;
+            bool risky = false, ordinary = false;
             if (e < n) {
                 const uint32_t id = p.point_list[r0 + e];
                 const float4* r = p.rec + (size_t)id * 4;
                 float4 c0 = r[0], c1 = r[1];
                 risky = conic_takes_ref_power(c1.x, c1.y, c1.z);
                 stage_for_exp2(c0, c1);                        // conic in units of the exp2 exponent, opacity as -log2 (common.h)
+                if constexpr (MODE == MODE_COLOR) ordinary = !record_is_plain(c0.z, c1.x, risky);
                 s_rec[0][lane] = c0;
                 s_rec[1][lane] = c1;
                 s_rec[2][lane] = DEPTH ? r[3] : r[2];          // rgb (colour / geo) or the normal (depth-only)
             }
             if (p.power_skip) riskm = __builtin_amdgcn_ballot_w64(risky);
+            if constexpr (MODE == MODE_COLOR) plain = !p.no_plain && __builtin_amdgcn_ballot_w64(ordinary) == 0ull;
         }
         riskany |= riskm;
         __syncthreads();
-        const int count = min(CHUNK, n - base);
+        int count = min(CHUNK, n - base);
+        // Colour, a plain round: the entry loop below for the colour pass alone, without the near-singular branch (riskm == 0) and with alpha = exp2(-E) unclamped --
+        // min(0.99, .) is the identity there (common.h), so the same bits.  Every other line is the loop below's, operation by operation: a change there belongs here too
+        // (tests/test_gpu_plain_chunks.py holds the two to the same bits).  The two loops run in SEQUENCE, one of them with no trips, not as `if (plain) ... else ...`:
+        // the alternative came out of hipcc as a flag-and-join shape in which both loops' copies of the blend state (T, C, last contributor: 20 registers) are live at once --
+        // 68 VGPRs and 40-60 moves per round; in sequence each loop works on the state in place (48 VGPRs as before, no scratch) for one scalar compare per loop and round.
+        if constexpr (MODE == MODE_COLOR) {
+            const int nplain = plain ? count : 0;
+            count -= nplain;
+            for (int j = 0; j < nplain; j++) {
+                const float4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j];
+                IBGS_LANES_ADD(0, 1);
+#ifdef IBGS_COUNT_LANES
+                bool lc_any_ = false;
+#endif
+                uint32_t e1v = (uint32_t)(base + j + 1);
+                asm volatile("" : "+v"(e1v));
+                const float dx0 = q0.x - (TILE_Q >= 0 ? pxf_t0 : pxf[0]), dy0 = q0.y - (TILE_Q >= 0 ? pyf_t0 : pyf[0]);
+                const float lx0 = q1.x * dx0 + q1.y * dy0, ly0 = q1.y * dx0 + q1.z * dy0;
+                const float P0 = fmaf(dx0, lx0, fmaf(dy0, ly0, q0.z));
+                float p2q[PPL];
+                p2q[0] = P0;
+                if constexpr (PPL >= 2) p2q[1] = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
+                if constexpr (PPL == 4) {
+                    p2q[2] = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
+                    p2q[3] = fmaf(128.0f, q1.y, p2q[2] + (p2q[1] - P0));
+                }
+                if constexpr (TILE_Q >= 1 && PPL == 1) {
+                    const float E1 = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
+                    const float E2 = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
+                    p2q[0] = TILE_Q == 1 ? E1 : (TILE_Q == 2 ? E2 : fmaf(128.0f, q1.y, E2 + (E1 - P0)));
+                }
+#pragma unroll
+                for (int q = 0; q < PPL; q++) {
+                    if (live[q] == 0ull) continue;
+                    const float p2 = p2q[q];
+                    uint64_t m = __builtin_amdgcn_ballot_w64(p2 <= ALPHA_SKIP_E) & live[q];
+                    if (m == 0ull) continue;
+                    IBGS_LANES_ADD(2, 64); IBGS_LANES_ADD(3, __builtin_popcountll(m));
+#ifdef IBGS_COUNT_LANES
+                    lc_any_ = true;
+#endif
+                    const float alpha = __builtin_amdgcn_exp2f(-p2);          // (no clamp)
+                    const float aeff = __builtin_amdgcn_inverse_ballot_w64(m) ? alpha : 0.f;
+                    float aT = aeff * T[q];
+                    float test_T = T[q] - aT;
+                    const uint64_t fin = __builtin_amdgcn_ballot_w64(test_T < 0.0001f) & m;
+                    if (fin != 0ull) {
+                        const bool pf = __builtin_amdgcn_inverse_ballot_w64(fin);
+                        aT = pf ? 0.f : aT;
+                        test_T = pf ? T[q] : test_T;
+                        live[q] &= ~fin;
+                        m &= ~fin;
+                    }
+                    const bool acc = __builtin_amdgcn_inverse_ballot_w64(m);
+                    C[q][0] += q2.x * aT; C[q][1] += q2.y * aT; C[q][2] += q2.z * aT;
+                    T[q] = test_T;
+                    lastc[q] = acc ? e1v : lastc[q];
+                }
+#ifdef IBGS_COUNT_LANES
+                if (lc_any_) IBGS_LANES_ADD(1, 1);
+#endif
+            }
+        }
         for (int j = 0; j < count; j++) {
             const float4 q0 = s_rec[0][j];      // x, y, opacity
             const float4 q1 = s_rec[1][j];      // conic a, b, c, plane distance
@@ -612,6 +679,7 @@ int launch_render_forward(hipStream_t s, const ibgs_forward_args& a, const GeomS
     p.n_src = a.n_src; p.L = a.buffer_length; p.thr = a.depth_error_threshold;
     p.tex_quant = (a.flags & IBGS_FLAG_TEX_QUANT) ? 1 : 0;
     p.power_skip = (a.flags & IBGS_FLAG_NO_REF_POWER_SKIP) ? 0 : 1;
+    p.no_plain = (a.flags & IBGS_FLAG_NO_PLAIN_CHUNKS) ? 1 : 0;
     p.ref_to_src = a.ref_to_src; p.src_cam_pos = a.src_cam_pos; p.src_rgba = src_rgba; p.src_depths = a.src_depths;
     {   // the depth plane of every source: its own number, or the caller's table slot
         const bool slots = (a.flags & IBGS_FLAG_SRC_DEPTH_SLOTS) != 0;

@@ -44,6 +44,10 @@ REF_POWER_SKIP = True
 # their sums (SURVEY Q1 as a switch; farther from a float64 evaluation, like every fp32 evaluation of those expressions).
 REF_ARITH = False
 
+# Plain chunks (csrc/common.h: clamp_free): the colour blend walks chunks of records that cannot reach the alpha clamp with clamp-free loops.  False =
+# IBGS_FLAG_NO_PLAIN_CHUNKS, every chunk takes the ordinary loops (tests and A/B only: the same bits in both passes).
+PLAIN_CHUNKS = True
+
 KEEP_DET_SCRATCH = False          # diagnostics: keep the last deterministic backward's scratch alive as _CModule.last_det
 # Deterministic backward (IBGS_FLAG_DETERMINISTIC): no float atomics, gradients bit-identical from run to run (CI mode, slower).
 DETERMINISTIC = False
@@ -59,7 +63,8 @@ WAVE_SHAPE = None
 
 def _shape_flag():
     return ({None: 0, "tile": _lib.FLAG_TILE_WAVES, "quadrant": _lib.FLAG_QUADRANT_WAVES}[WAVE_SHAPE]
-            | (0 if REF_POWER_SKIP else _lib.FLAG_NO_REF_POWER_SKIP) | (_lib.FLAG_REF_ARITH if REF_ARITH else 0))
+            | (0 if REF_POWER_SKIP else _lib.FLAG_NO_REF_POWER_SKIP) | (_lib.FLAG_REF_ARITH if REF_ARITH else 0)
+            | (0 if PLAIN_CHUNKS else _lib.FLAG_NO_PLAIN_CHUNKS))
 
 
 # View-parallel training (ibgs_amd/dist.py): while a `capture_sh_factors()` block is active the backward leaves

@@ -97,6 +97,10 @@ typedef char* (*ibgs_alloc_fn)(size_t bytes, void* user);
                                      chain (backward.cu:405-420), without its cancellation: 3-10 x closer to a float64 evaluation than ANY fp32 evaluation of the reference's own
                                      expressions (profiles/r06_ref_arith_ab.txt).  With this flag they are formed exactly as the reference forms them: the eight per-pair quantities of
                                      backward.cu:779-804 in its association, uncontracted, and the chain of :405-420 on their sums.  Every other Gaussian: unchanged */
+#define IBGS_FLAG_NO_PLAIN_CHUNKS 2048u /* both passes, tests and A/B only.  The colour blend kernels walk a chunk of staged records none of which can reach the
+                                          alpha clamp (-log2 opacity >= CLAMP_FREE_NLO, csrc/common.h: clamp_free) and none of which is near-singular with loops
+                                          that hold neither the clamp nor the near-singular branches ("plain" chunks).  With this flag no chunk counts as plain:
+                                          both passes compute the same bits either way (the clamp is the identity on a plain chunk) */
 #define IBGS_FLAG_SRC_DEPTH_SLOTS 8192u /* ibgs_forward only: src_depths is a table of planes, source m reads plane src_depth_slot[m] (ibgs_forward_args) */
 #define IBGS_FLAG_NO_ABS_GRAD 1024u /* ibgs_backward only: dL_dmean2D_abs is not wanted (it may be NULL and is not written).  It is the densification statistic of
                                        train.py:400-410 (sum over pixels of |dL/dmean2D| per Gaussian, backward.cu:793-804): nobody reads it after
@@ -443,6 +447,10 @@ size_t ibgs_sizeof_backward_args(void);
 /* 1 while every byte offset into a gradient accumulation arena of P rows (64 bytes each) fits 32 unsigned bits, P <= 2^26: the colour backward then
    addresses a row by a 32-bit offset from the arena's base, else by 64-bit addresses.  ibgs_backward decides with this function; exported for tests. */
 int32_t ibgs_grad_acc_offsets_fit32(int64_t P);
+/* 1 when a record whose staged -log2(opacity) is `neg_log2_opacity` cannot reach the alpha clamp (csrc/common.h: clamp_free; NaN and -0: 0).  The blend kernels decide
+   with this function; exported for tests.  ibgs_clamp_free_threshold: the constant it compares against (CLAMP_FREE_NLO). */
+int32_t ibgs_clamp_free(float neg_log2_opacity);
+float ibgs_clamp_free_threshold(void);
 
 const char* ibgs_last_error(void);
 const char* ibgs_version(void);
