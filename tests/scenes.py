@@ -14,6 +14,30 @@ def scene(P=4000, W=208, H=144, deg=3, seed=1, opacity="init", planes=False, sca
     return inp
 
 
+def camera_at(W, H, eye, target, fovx, fovy):
+    """A camera at `eye` looking at `target` with the two fields of view given INDEPENDENTLY (make_camera derives fovy from fovx's focal length, so
+    fx == fy there; here fx = W / (2 tan(fovx / 2)) and fy = H / (2 tan(fovy / 2)) are whatever the arguments make them)."""
+    R, t = syn.look_at_camera(eye, target)
+    return syn.camera_from_pose(W, H, R, t, fovx, fovy)
+
+
+def inside_cloud(P, W, H, eye, target, fovx, fovy, seed, deg, opacity, scale_mul=1.0, anisotropy=None, planes=False):
+    """make_scene's random cloud (half-extent 1.3) seen by camera_at from an eye INSIDE it: most Gaussians fail the near cull, half lie behind the camera,
+    the survivors come as close as z = 0.2 with footprints many times the frame, and most visible centres are off the frame and beyond the 1.3 tan clamp.
+    Returns make_gaussians' arrays plus make_scene's input dict with that camera (also as inp["_cam"])."""
+    g = syn.make_gaussians(P, seed, sh_degree=deg, opacity=opacity, anisotropy=anisotropy)
+    if scale_mul != 1.0:
+        g["scales"] = (g["scales"] * scale_mul).astype(np.float32)
+    cam = camera_at(W, H, eye, target, fovx, fovy)
+    inp = dict(g)
+    inp.update({"W": W, "H": H, "tanfovx": cam["tanfovx"], "tanfovy": cam["tanfovy"], "viewmatrix": cam["viewmatrix"], "projmatrix": cam["projmatrix"],
+                "campos": cam["campos"], "bg": np.zeros(3, np.float32), "sh_degree": deg, "scale_modifier": 1.0, "render_geo": False,
+                "render_depth_only": False, "n_src": 1, "buffer_length": 4, "depth_thr": 0.01, "_cam": cam})
+    if planes:
+        inp["all_map"] = syn.plane_all_map(g["means3D"], g["scales"], g["rotations"], cam)
+    return inp
+
+
 def giant_needles(P=300, W=208, H=144, seed=5, stretch=4.0, thin=0.05, deg=1, opacity="trained"):
     """Needles far longer than the frame and thinner than a pixel: the fp32 inversion of cov2D leaves conics within rounding of singular
     (some indefinite), the regime in which the reference's `power > 0` test (forward.cu:420, backward.cu:645) decides which pairs blend.
@@ -30,9 +54,13 @@ def giant_needles(P=300, W=208, H=144, seed=5, stretch=4.0, thin=0.05, deg=1, op
 SRC_AZIMUTHS = (7.0, -7.0, 14.0, -14.0, 21.0)         # add_sources' source views (make_camera azimuths; the reference view is at 0)
 
 
-def add_sources(inp, n_src=3, L=4, seed=5, depth=None):
+def add_sources(inp, n_src=3, L=4, seed=5, depth=None, srcs=None):
+    """Geo inputs for `inp`: source views (the orbit cameras at SRC_AZIMUTHS, or the camera dicts `srcs`, which then set n_src), uniform-noise source
+    images and, unless `depth` is given, the oracle's depth-only renders of the same Gaussians from those views as source depths."""
     W, H = inp["W"], inp["H"]
-    srcs = [syn.make_camera(W, H, azimuth_deg=a) for a in SRC_AZIMUTHS[:n_src]]
+    if srcs is None:
+        srcs = [syn.make_camera(W, H, azimuth_deg=a) for a in SRC_AZIMUTHS[:n_src]]
+    n_src = len(srcs)
     r2s, scp = syn.ref_to_src(inp["_cam"], srcs)
     rng = np.random.default_rng(seed)
     if depth is None:   # plausible source depths: the oracle's own depth-only render of each source view
@@ -119,20 +147,33 @@ def linear_source_images(n_src, W, H, seed):
     return img.astype(np.float32), coef
 
 
-def surface_scene(P=20000, W=176, H=112, seed=1, n_src=5, L=4, deg=2, images="noise", depth_thr=0.01, **disc_kw):
+def surface_scene(P=20000, W=176, H=112, seed=1, n_src=5, L=4, deg=2, images="noise", depth_thr=0.01, ref_pose=None, src_poses=None, fovx=None, fovy=None,
+                  **disc_kw):
     """The multi-view-consistent geo scene: surface_discs seen from make_camera(azimuth 0) with add_sources' n_src source views, source depths = the
     oracle's depth-only renders of the same discs from those views, depth_thr 0.01 (the trainer's).  images = "noise" (add_sources' uniform noise) or
-    "linear" (linear_source_images; the coefficients are returned as inp["_src_coef"]).  inp["_g"] holds surface_discs' dict."""
+    "linear" (linear_source_images; the coefficients are returned as inp["_src_coef"]).  inp["_g"] holds surface_discs' dict.
+    With ref_pose = (eye, target), src_poses = [(eye, target), ...] and fovx, fovy the reference and source views are camera_at's instead (all with the
+    same two fields of view; n_src = len(src_poses)), and the source cameras are returned as inp["_srcs"]."""
     g = surface_discs(P, seed, deg=deg, **disc_kw)
-    cam = syn.make_camera(W, H)
+    posed = ref_pose is not None
+    assert posed == (src_poses is not None) == (fovx is not None) == (fovy is not None), "ref_pose, src_poses, fovx and fovy come together"
+    srcs = None
+    if posed:
+        cam = camera_at(W, H, ref_pose[0], ref_pose[1], fovx, fovy)
+        srcs = [camera_at(W, H, e, t, fovx, fovy) for e, t in src_poses]
+        n_src = len(srcs)
+    else:
+        cam = syn.make_camera(W, H)
     inp = {k: g[k] for k in ("means3D", "shs", "scales", "rotations", "opacities")}
     inp.update({"W": W, "H": H, "tanfovx": cam["tanfovx"], "tanfovy": cam["tanfovy"], "viewmatrix": cam["viewmatrix"], "projmatrix": cam["projmatrix"],
                 "campos": cam["campos"], "bg": np.zeros(3, np.float32), "sh_degree": deg, "scale_modifier": 1.0, "render_geo": False,
                 "render_depth_only": False, "n_src": 1, "buffer_length": L, "depth_thr": depth_thr, "_cam": cam,
                 "all_map": syn.plane_all_map(g["means3D"], g["scales"], g["rotations"], cam)})
-    inp = add_sources(inp, n_src=n_src, L=L, seed=seed + 1)
+    inp = add_sources(inp, n_src=n_src, L=L, seed=seed + 1, srcs=srcs)
     inp["depth_thr"] = depth_thr
     inp["_g"] = g
+    if posed:
+        inp["_srcs"] = srcs
     if images == "linear":
         inp["src_images"], inp["_src_coef"] = linear_source_images(n_src, W, H, seed + 2)
     return inp

@@ -75,18 +75,18 @@ def check_grads_arbitered(pairs, label=""):
 
 # ---------------------------------------------------------------------------------------------------
 # (a) small frames: every slot level and L, both wave shapes
-@pytest.mark.parametrize("n_src,L", [(4, 4), (5, 8), (5, 1), (3, 5), (2, 2)])
-def test_surface_scene_small_frames(n_src, L, wave_shape):
-    inp = surface_scene(P=20000, W=176, H=112, seed=30 + 2 * n_src + L, n_src=n_src, L=L)
-    H, W = inp["H"], inp["W"]
-    grads = {"color": rnd((3, H, W), 7), "normal_map": rnd((3, H, W), 8), "median_depth": rnd((1, H, W), 9), "warped_image": rnd((15, H, W), 10)}
+def small_frame_geo_checks(inp, grads, label, regime=None):
+    """One small geo frame through the product path, judged like test_surface_scene_small_frames: stages and colour, the decision budgets against the
+    oracle's fma twin, sum_w, the seven planes and the per-source weights on the pixels whose valid sources agree, every gradient by the arbiter.
+    regime(mean, hist): asserts the oracle's valid-source histogram before anything is compared.  Returns (ref, o, ist)."""
+    H, W, n_src = inp["H"], inp["W"], inp["n_src"]
     ref, o, ist, leaves, gb = run(inp, grads)
-    label = "[surface %s n_src %d L %d]" % (wave_shape, n_src, L)
     h_ref, m_ref = valid_source_histogram(ref["valid_src_idx"], ref["final_T"], n_src)
     h_hip, m_hip = valid_source_histogram(ist["valid_idx"], ist["final_T"], n_src)
     print("\n%s valid sources per covered pixel: oracle mean %.2f [%s], HIP mean %.2f [%s]" % (label, m_ref, " ".join("%.3f" % x for x in h_ref), m_hip,
                                                                                              " ".join("%.3f" % x for x in h_hip)))
-    assert m_ref >= min(MIN_MEAN_VALID, 0.75 * n_src) and (n_src != 5 or h_ref[5] >= MIN_ALL_VALID_5)
+    if regime is not None:
+        regime(m_ref, h_ref)
     check_stages(ist, o, ref); check_color(o, ist, ref)
     with oracle.variant("fma"):
         tw = oracle.forward(inp, tex_quant=rasterizer.TEX_QUANT, cull=True)
@@ -105,6 +105,18 @@ def test_surface_scene_small_frames(n_src, L, wave_shape):
     f64 = functools.lru_cache(None)(lambda: f64_truth(inp, grads)[1])
     check_grads_arbitered([(lk, leaves[lk].grad.cpu().numpy(), gb[rk].reshape(leaves[lk].grad.shape), (lambda rk=rk, lk=lk: np.asarray(f64()[rk]).reshape(leaves[lk].grad.shape)))
                            for lk, rk in GRAD_PAIRS if leaves.get(lk) is not None], label)
+    return ref, o, ist
+
+
+@pytest.mark.parametrize("n_src,L", [(4, 4), (5, 8), (5, 1), (3, 5), (2, 2)])
+def test_surface_scene_small_frames(n_src, L, wave_shape):
+    inp = surface_scene(P=20000, W=176, H=112, seed=30 + 2 * n_src + L, n_src=n_src, L=L)
+    H, W = inp["H"], inp["W"]
+    grads = {"color": rnd((3, H, W), 7), "normal_map": rnd((3, H, W), 8), "median_depth": rnd((1, H, W), 9), "warped_image": rnd((15, H, W), 10)}
+
+    def regime(m_ref, h_ref):
+        assert m_ref >= min(MIN_MEAN_VALID, 0.75 * n_src) and (n_src != 5 or h_ref[5] >= MIN_ALL_VALID_5)
+    small_frame_geo_checks(inp, grads, "[surface %s n_src %d L %d]" % (wave_shape, n_src, L), regime)
 
 
 # ---------------------------------------------------------------------------------------------------
