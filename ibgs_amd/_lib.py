@@ -193,6 +193,12 @@ SSIM_EXPORTS = ["ibgs_ssim_required_scratch", "ibgs_ssim_tile", "ibgs_ssim_forwa
 SSIM_WINDOW = 11
 SSIM_MAX_SIDE = 65536
 
+# every symbol include/ibgs_geo_loss.h declares (tests/test_geoloss_host.py compares the two)
+GEOLOSS_EXPORTS = ["ibgs_geoloss_required_scratch", "ibgs_geoloss_tile", "ibgs_geoloss_photo_forward", "ibgs_geoloss_photo_backward",
+                   "ibgs_geoloss_normal_forward", "ibgs_geoloss_rescale"]
+GEOLOSS_MAX_SRC = 5
+GEOLOSS_MAX_SIDE = 65536
+
 
 _lib = None
 
@@ -381,6 +387,21 @@ def load():
     lib.ibgs_ssim_forward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 10 + [sz]
     lib.ibgs_ssim_backward.restype = i32
     lib.ibgs_ssim_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 6
+    for name in GEOLOSS_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_geoloss_required_scratch.restype = sz
+    lib.ibgs_geoloss_required_scratch.argtypes = [i64, i64, i64]
+    lib.ibgs_geoloss_tile.restype = None
+    lib.ibgs_geoloss_tile.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.ibgs_geoloss_photo_forward.restype = i32
+    lib.ibgs_geoloss_photo_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, f64, f64, vp, vp, vp, vp, sz]
+    lib.ibgs_geoloss_photo_backward.restype = i32
+    lib.ibgs_geoloss_photo_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 6 + [f64, f64, vp]
+    lib.ibgs_geoloss_normal_forward.restype = i32
+    lib.ibgs_geoloss_normal_forward.argtypes = [vp, i32, i32, vp, vp, f64, vp, vp, vp, vp, sz]
+    lib.ibgs_geoloss_rescale.restype = i32
+    lib.ibgs_geoloss_rescale.argtypes = [vp, i64, vp, vp]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32
