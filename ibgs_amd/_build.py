@@ -7,7 +7,8 @@ C oracle (see the header of that file); so is scan_sort.hip, whose depth sort la
 colours (sh_color.h); so is tsdf.hip, whose f32 operation order is part of the TSDF contract (its header, tests/tsdf_ref.py), and mesh.hip (the f64 triangle areas), and mesh_eval.hip (f64 sample positions, f32 squared distances),
 and registration.hip (the f64 transform, crop, voxel index and moment terms), and dtu.hip (the f32 projection chain of the vertex culling, the f64 filters).
 ssim.hip takes no such flag: its contract is a tolerance, its filter passes are fma chains, and the per-pixel expressions that must not be contracted say so
-themselves (#pragma clang fp contract(off)); geoloss.hip, which carries its own copy of those passes and forms, is built the same way.
+themselves (#pragma clang fp contract(off)); geoloss.hip, which carries its own copy of those passes and forms, is built the same way, and so is coloragg.hip
+(the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -20,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -46,7 +47,8 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "registration": [os.path.join(HERE, "..", "include", "ibgs_registration.h")],
                 "dtu": [os.path.join(HERE, "..", "include", "ibgs_dtu.h")],
                 "ssim": [os.path.join(HERE, "..", "include", "ibgs_ssim.h")],
-                "geoloss": [os.path.join(HERE, "..", "include", "ibgs_geo_loss.h")]}
+                "geoloss": [os.path.join(HERE, "..", "include", "ibgs_geo_loss.h")],
+                "coloragg": [os.path.join(HERE, "..", "include", "ibgs_color_agg.h")]}
 
 
 def _hipcc():
@@ -89,7 +91,7 @@ def csrc_sha():
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning; "dtu_" before "mesh_" and "scan_":
 # a dtu_emit_mesh_* or dtu_scan_* would otherwise go to those units)
-KERNEL_TU = (("meval_", "mesh_eval"), ("geoloss_", "geoloss"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+KERNEL_TU = (("meval_", "mesh_eval"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"))

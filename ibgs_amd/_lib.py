@@ -199,6 +199,13 @@ GEOLOSS_EXPORTS = ["ibgs_geoloss_required_scratch", "ibgs_geoloss_tile", "ibgs_g
 GEOLOSS_MAX_SRC = 5
 GEOLOSS_MAX_SIDE = 65536
 
+# every symbol include/ibgs_color_agg.h declares (tests/test_coloragg_host.py compares the two)
+CAGG_EXPORTS = ["ibgs_cagg_required_scratch", "ibgs_cagg_levels", "ibgs_cagg_forward", "ibgs_cagg_backward"]
+CAGG_MAX_SRC = 5
+CAGG_MAX_SIDE = 65536
+CAGG_FEATURES = 32
+CAGG_MEAN, CAGG_MAX = 0, 1
+
 
 _lib = None
 
@@ -402,6 +409,17 @@ def load():
     lib.ibgs_geoloss_normal_forward.argtypes = [vp, i32, i32, vp, vp, f64, vp, vp, vp, vp, sz]
     lib.ibgs_geoloss_rescale.restype = i32
     lib.ibgs_geoloss_rescale.argtypes = [vp, i64, vp, vp]
+    for name in CAGG_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_cagg_required_scratch.restype = sz
+    lib.ibgs_cagg_required_scratch.argtypes = [i64, i64, i64]
+    lib.ibgs_cagg_levels.restype = i32
+    lib.ibgs_cagg_levels.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, sz]
+    lib.ibgs_cagg_forward.restype = i32
+    lib.ibgs_cagg_forward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 10
+    lib.ibgs_cagg_backward.restype = i32
+    lib.ibgs_cagg_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 16 + [sz]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

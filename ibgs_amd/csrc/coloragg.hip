@@ -1,0 +1,512 @@
+// The per-view front end of the reference's colour aggregation network on the device (C ABI: include/ibgs_color_agg.h; Python: ibgs_amd/coloragg.py):
+// what fuse_color and ColorFusionResidualNet.forward do between the rasterizer's planes and the input of the hourglass CNN
+// (color_aggregation_network.py:102-133, 156-198, 229-233) -- permutes, a mask, a subtraction, a concatenation into (HW, M, 7), two Linear + ReLU over HW M
+// rows of 32 floats, a mean over the views, a transpose and a concatenation into (1, 38, H, W), and one host sync to count the slot levels -- as one kernel
+// forward and one backward that keep the 64 intermediate floats per pixel and source in registers.  Nothing waits for the host: the level count stays in a
+// device word.
+//
+// CONTRACT
+//   levels     min(slots of `warped` with any value != 0, nb_visible_src_frames, S), in a device word; the first `levels` slots are used.
+//   slot k     v = (((f0 + f1) + f2) + f3) > 0 in float32, in that order (cam_feat is signed); x = [(warped - render) v, f0 .. f3];
+//              h1 = relu(w1 x + b1), h2 = relu(w2 h1 + b2): each element an f32 fma chain started from the bias (the order of the 32 terms of the second
+//              layer is the matrix cores': below).
+//   agg        mean: ((h2_0 + h2_1) + ..) / levels; max: the maximum over k; zeros when levels == 0.  out = [agg, camera_ray, render].
+//   backward   recomputes h1 and h2 with the same instructions (the same bits), then dz2 = g (h2 > 0) with g = grad_out / levels (mean) or grad_out at the
+//              first slot attaining the maximum (max), dz1 = (w2^T dz2) (h1 > 0), dx = w1^T dz1; grad_warped[3k + c] = dx[c] v, grad_render[c] =
+//              grad_out[35 + c] - sum_k dx[c] v; slots from `levels` on: zeros.
+//   parameter gradients   dW2 = sum_p dz2 (x) h1, db2 = sum_p dz2, dW1 = sum_p dz1 (x) x, db1 = sum_p dz1.  Each wave sums its own 32 pixels of every chunk
+//              and slot in a fixed order: dW2 as the matrix cores' f32 fma chain over one chunk's pixels and slots, from there on in f64; the other three in
+//              f64 throughout (the products are exact there).  The four waves of a workgroup are added in order and the workgroup's 1312 f64 sums go to the
+//              scratch arena; cagg_final_kernel adds the workgroups: sixteen strided series per element, then those in order, one rounding to f32 at the
+//              end.  No float atomics.
+//
+// THE 32 x 32 PRODUCTS run on the matrix cores in exact f32 (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, at the vector fp32 rate).  A wave
+// holds 32 pixels: lane l = (pixel l & 31, half h = l >> 5), and register r of a 16-register tile belongs to channel ch(r, h) = (r & 3) + 8 (r >> 2) + 4 h:
+// the layout in which the instruction leaves a result whose rows are channels and whose columns are pixels.  That result is the NEXT product's B operand as
+// it stands -- k-step kk takes register kk, i.e. the channels ch(kk, 0) and ch(kk, 1) -- so the weights are loaded once per wave in that (permuted) k order, 16
+// registers per matrix, and h1, h2, dz2, dz1 never leave the registers.  Only the weight gradient, whose long dimension is the pixels, goes through LDS: each
+// lane stores its pixel's dz2, h1 and dz1 as rows and the wave reads them back a pixel pair per k-step.
+//
+// KERNELS
+//   cagg_levels_kernel   S x B workgroups scan the slots; a workgroup that found a value ORs its slot's bit into a word, takes a ticket, and the last one
+//                        writes the count (integer atomics on two words the entry point zeroes with a memset in front).
+//   cagg_fwd_kernel      256 threads = 4 waves of 32 pixels; 20 MFMA per wave and slot.
+//   cagg_bwd_kernel      the same over a capped grid that walks the frame in chunks of 128 pixels; 52 MFMA per wave and slot with parameter gradients.
+//   cagg_final_kernel    82 workgroups: 16 elements each.
+// What bounds them, storing against recomputing, and the matrix cores against the VALU: DESIGN.md section 14.
+#include "common.h"
+#include "../../include/ibgs_color_agg.h"
+
+namespace ibgs {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int CT = 256;                              // threads per workgroup
+constexpr int CWAVES = CT / 64;
+constexpr int CB = 32;                               // pixels per wave
+constexpr int CHUNK = CWAVES * CB;                   // pixels per workgroup and step
+constexpr int CF = IBGS_CAGG_FEATURES;               // feature width
+constexpr int CIN = 7, CINP = 8;                     // inputs of the first layer, and the row they are kept in
+constexpr int CROW = 33;                             // row stride of the staged rows: the 32 lanes of a half store one column into 32 banks
+constexpr int CAGG_PARTIAL = CF * CINP + CF * CF + CF;          // a workgroup's sums: [dW1 | db1] (32 x 8), dW2 (32 x 32), db2 (32)
+constexpr int CAGG_MAX_GROUPS = 512;                 // workgroups of the backward (256 CUs x 2 resident): what bounds the arena
+constexpr int CAGG_FWD_MAX_GROUPS = 4096;
+constexpr int CAGG_WAVE_WORDS = CF * CF + CF * CINP + 2 * CF;   // a wave's accumulators as the cross-wave sum reads them
+constexpr int LV_THREADS = 256, LV_MAX_BLOCKS = 128; // level count: workgroups per slot
+constexpr int FIN_ELEMS = 16, FIN_SERIES = 16;       // final kernel: elements per workgroup, strided series per element
+static_assert(CF == 32 && CB == 32 && CAGG_PARTIAL % FIN_ELEMS == 0 && FIN_ELEMS * FIN_SERIES == CT, "the lane maps below");
+static_assert(CWAVES * CAGG_WAVE_WORDS * sizeof(double) <= CWAVES * 3 * CB * CROW * sizeof(float), "the cross-wave sum reuses the staged rows");
+
+// the channel of register r of a tile in half h
+__device__ __forceinline__ constexpr int cagg_ch(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+__device__ __forceinline__ f32x16 cagg_mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+
+// A lane's share of the weights, loaded once: the A operands of the two layers (row = this lane's l & 31, k-step kk = the inputs 2 kk + h of the first
+// layer and the channels ch(kk, h) of the second).
+struct CaggFrag {
+    float a1[4], a2[16];
+    __device__ __forceinline__ CaggFrag(const float* __restrict__ w1, const float* __restrict__ w2, int row, int h)
+    {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) a1[kk] = 2 * kk + h < CIN ? w1[row * CIN + 2 * kk + h] : 0.0f;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) a2[kk] = w2[row * CF + cagg_ch(kk, h)];
+    }
+};
+
+// The biases as the tiles the chains start from: [layer][half][register], the same for every pixel, so they live in LDS and are read as broadcasts
+// (32 registers per lane otherwise).  Ends with a barrier.
+struct __attribute__((aligned(16))) CaggBias { float t[2][2][16]; };
+__device__ __forceinline__ void cagg_stage_bias(CaggBias& s, const float* __restrict__ b1, const float* __restrict__ b2)
+{
+    if (threadIdx.x < 64) {
+        const int layer = threadIdx.x >> 5, hh = (threadIdx.x >> 4) & 1, r = threadIdx.x & 15;
+        s.t[layer][hh][r] = (layer ? b2 : b1)[cagg_ch(r, hh)];
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ f32x16 cagg_bias_tile(const CaggBias& s, int layer, int h)
+{
+    f32x16 z;
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(&s.t[layer][h][i]);
+        z[i] = v.x; z[i + 1] = v.y; z[i + 2] = v.z; z[i + 3] = v.w;
+    }
+    return z;
+}
+
+__device__ __forceinline__ int cagg_levels_of(const int32_t* __restrict__ levels, int S)
+{
+    const int l = *levels;          // (wave-uniform)
+    return l < 0 ? 0 : (l > S ? S : l);
+}
+
+// the features of slot k of pixel p; x[7] = 0: the eighth input of the first layer's four k-steps.  -> v as a float
+__device__ __forceinline__ float cagg_slot(const float* __restrict__ warped, const float* __restrict__ feat, const float (&r)[3], size_t plane, size_t p, int k, float (&x)[CINP])
+{
+#pragma clang fp contract(off)
+    const float* const f = feat + (size_t)k * 4 * plane + p;
+    const float* const w = warped + (size_t)k * 3 * plane + p;
+    x[3] = f[0]; x[4] = f[plane]; x[5] = f[2 * plane]; x[6] = f[3 * plane];
+    const float v = (((x[3] + x[4]) + x[5]) + x[6]) > 0.0f ? 1.0f : 0.0f;          // the sum's order is the contract
+    x[0] = (w[0] - r[0]) * v; x[1] = (w[plane] - r[1]) * v; x[2] = (w[2 * plane] - r[2]) * v;
+    x[7] = 0.0f;
+    return v;
+}
+
+// both layers of the lane's pixel: its 16 channels of h1 and of h2 (the forward and the backward's recomputation run the same instructions: the same bits)
+__device__ __forceinline__ void cagg_mlp(const CaggFrag& f, const CaggBias& bias, const float (&x)[CINP], int h, f32x16& h1, f32x16& h2)
+{
+    f32x16 z = cagg_bias_tile(bias, 0, h);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) z = cagg_mfma(f.a1[kk], h ? x[2 * kk + 1] : x[2 * kk], z);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) h1[r] = z[r] > 0.0f ? z[r] : 0.0f;
+    z = cagg_bias_tile(bias, 1, h);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) z = cagg_mfma(f.a2[kk], h1[kk], z);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) h2[r] = z[r] > 0.0f ? z[r] : 0.0f;
+}
+
+// slot's grid: S x per_slot workgroups; state[0]: the slots that hold a value, state[1]: workgroups done (both zero on entry)
+__global__ void __launch_bounds__(LV_THREADS) cagg_levels_kernel(const float* __restrict__ warped, size_t slot_elems, int per_slot, int S, int nb, uint32_t* __restrict__ state,
+                                                                 int32_t* __restrict__ levels_out)
+{
+    const int slot = (int)(blockIdx.x / (unsigned)per_slot), b = (int)(blockIdx.x - (unsigned)slot * (unsigned)per_slot);
+    const float* const base = warped + (size_t)slot * slot_elems;
+    int any = 0;
+    for (size_t i = (size_t)b * LV_THREADS + threadIdx.x; i < slot_elems; i += (size_t)per_slot * LV_THREADS) any |= base[i] != 0.0f ? 1 : 0;
+    any = __syncthreads_or(any);
+    if (threadIdx.x == 0) {
+        if (any) __hip_atomic_fetch_or(&state[0], 1u << slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // release what this workgroup found, acquire what the others did: the last ticket sees every bit
+        const uint32_t ticket = __hip_atomic_fetch_add(&state[1], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == gridDim.x - 1) {
+            const int n = __popc(__hip_atomic_load(&state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            *levels_out = min(n, min(nb, S));
+        }
+    }
+}
+
+// a wave per block of 32 pixels (wave-uniform bounds: the matrix instructions run with every lane on; a lane past the frame recomputes the last pixel)
+template <int MODE>
+__global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ render, const float* __restrict__ warped, const float* __restrict__ feat,
+                                                      const float* __restrict__ ray, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                      const float* __restrict__ w2, const float* __restrict__ b2, const int32_t* __restrict__ levels, int S, size_t plane,
+                                                      float* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+    const CaggFrag f(w1, w2, c, h);
+    __shared__ CaggBias bias;
+    cagg_stage_bias(bias, b1, b2);
+    const int L = cagg_levels_of(levels, S);
+    const size_t blocks = (plane + CB - 1) / CB;
+    for (size_t b = (size_t)blockIdx.x * CWAVES + wave; b < blocks; b += (size_t)gridDim.x * CWAVES) {
+        const size_t q = b * CB + c;
+        const bool in = q < plane;
+        const size_t p = in ? q : plane - 1;
+        const float r[3] = {render[p], render[plane + p], render[2 * plane + p]};
+        f32x16 agg;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) agg[j] = 0.0f;
+        for (int k = 0; k < L; ++k) {
+            float x[CINP];
+            f32x16 h1, h2;
+            cagg_slot(warped, feat, r, plane, p, k, x);
+            cagg_mlp(f, bias, x, h, h1, h2);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) agg[j] = MODE == IBGS_CAGG_MEAN ? agg[j] + h2[j] : fmaxf(agg[j], h2[j]);          // (h2 >= 0: the maximum may start from 0)
+        }
+        if (MODE == IBGS_CAGG_MEAN && L > 1) {
+            const float n = (float)L;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) agg[j] = agg[j] / n;
+        }
+        if (in) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) out[(size_t)cagg_ch(j, h) * plane + p] = agg[j];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {          // half 0 passes the ray on, half 1 the colour
+                const float* const src = h ? render : ray;
+                out[(size_t)(CF + 3 * h + ch) * plane + p] = src[(size_t)ch * plane + p];
+            }
+        }
+    }
+}
+
+// IG: an image gradient is asked for; PG: a parameter gradient is.  go: 38 planes; partials: gridDim.x x CAGG_PARTIAL
+template <int MODE, bool IG, bool PG>
+__global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict__ render, const float* __restrict__ warped, const float* __restrict__ feat,
+                                                      const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+                                                      const float* __restrict__ b2, const int32_t* __restrict__ levels, int S, size_t plane, const float* __restrict__ go,
+                                                      float* __restrict__ d_render, float* __restrict__ d_warped, double* __restrict__ partials)
+{
+    __shared__ __attribute__((aligned(16))) float s_t[PG ? CWAVES : 1][PG ? 3 : 1][PG ? CB : 1][PG ? CROW : 1];          // per wave: its pixels' dz2, h1, dz1 as rows
+    __shared__ __attribute__((aligned(16))) float s_x[PG ? CWAVES : 1][PG ? CB : 1][CINP];  // ... and [x | 1]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+    const CaggFrag f(w1, w2, c, h);
+    __shared__ CaggBias bias;
+    cagg_stage_bias(bias, b1, b2);
+    float a2t[16];          // the A operand of w2^T dz2: row = this lane's input channel c, k-step kk = the output channels ch(kk, h)
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) a2t[kk] = w2[cagg_ch(kk, h) * CF + c];
+    __shared__ float4 s_w1c[2][16];          // w1's first three columns at the 16 channels of each half (the same for every pixel: read as a broadcast)
+    if (IG && threadIdx.x < 32) {
+        const int r = threadIdx.x & 15, hh = threadIdx.x >> 4;
+        s_w1c[hh][r] = make_float4(w1[cagg_ch(r, hh) * CIN], w1[cagg_ch(r, hh) * CIN + 1], w1[cagg_ch(r, hh) * CIN + 2], 0.0f);
+    }
+    __syncthreads();
+    const int L = cagg_levels_of(levels, S);
+    const int r1 = lane >> 1, c0 = (lane & 1) * 4;          // this lane's elements of [dW1 | db1]: row r1 (dz1), columns c0 .. c0 + 3 (x, 1)
+    f32x16 acc2;          // dW2: register r = row ch(r, h) (dz2), column c (h1); the f32 chain of one chunk's pixels and slots, then added to acc2d
+    double acc2d[16], acc1[4] = {0.0, 0.0, 0.0, 0.0}, accb = 0.0;          // accb: db2 of channel c over the pixels 16 h .. 16 h + 15 of the wave
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc2[r] = 0.0f; acc2d[r] = 0.0; }
+    const size_t chunks = (plane + CHUNK - 1) / CHUNK;
+    for (size_t ck = blockIdx.x; ck < chunks; ck += gridDim.x) {          // (uniform over the workgroup: the barriers below are reached by every thread)
+        const size_t q = ck * CHUNK + (size_t)wave * CB + c;
+        const bool in = q < plane;
+        const size_t p = in ? q : plane - 1;          // a lane past the frame recomputes the last pixel under a zero gradient: it adds zeros
+        const float r[3] = {render[p], render[plane + p], render[2 * plane + p]};
+        f32x16 g;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) g[j] = in ? go[(size_t)cagg_ch(j, h) * plane + p] : 0.0f;
+        if (MODE == IBGS_CAGG_MEAN && L > 1) {
+            const float n = (float)L;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) g[j] = g[j] / n;
+        }
+        f32x16 hmax;
+        uint32_t taken = 0u;          // max mode: the channels whose maximum an earlier slot attained
+        if (MODE == IBGS_CAGG_MAX) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) hmax[j] = 0.0f;
+            for (int k = 0; k < L; ++k) {
+                float x[CINP];
+                f32x16 h1, h2;
+                cagg_slot(warped, feat, r, plane, p, k, x);
+                cagg_mlp(f, bias, x, h, h1, h2);
+#pragma unroll
+                for (int j = 0; j < 16; ++j) hmax[j] = fmaxf(hmax[j], h2[j]);
+            }
+        }
+        float dr[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < L; ++k) {
+            float x[CINP];
+            f32x16 h1, dz2, dz1;
+            const float v = cagg_slot(warped, feat, r, plane, p, k, x);
+            cagg_mlp(f, bias, x, h, h1, dz2);          // dz2 = h2 for now
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                bool on = dz2[j] > 0.0f;
+                if (MODE == IBGS_CAGG_MAX) {
+                    const bool mine = dz2[j] == hmax[j] && !((taken >> j) & 1u);
+                    if (mine) taken |= 1u << j;
+                    on = on && mine;
+                }
+                dz2[j] = on ? g[j] : 0.0f;
+                dz1[j] = 0.0f;
+            }
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) dz1 = cagg_mfma(a2t[kk], dz2[kk], dz1);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) dz1[j] = h1[j] > 0.0f ? dz1[j] : 0.0f;
+            if constexpr (IG) {
+                float dx[3] = {0.0f, 0.0f, 0.0f};          // the lane's 16 channels, then the other half's
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const float4 w = s_w1c[h][j];
+                    dx[0] = fmaf(w.x, dz1[j], dx[0]); dx[1] = fmaf(w.y, dz1[j], dx[1]); dx[2] = fmaf(w.z, dz1[j], dx[2]);
+                }
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float gx = (dx[ch] + __shfl_xor(dx[ch], 32, 64)) * v;
+                    dr[ch] -= gx;
+                    if (d_warped && in && h == 0) d_warped[((size_t)k * 3 + ch) * plane + p] = gx;
+                }
+            }
+            if constexpr (PG) {
+                // A wave writes and reads only its own rows (s_t[wave], s_x[wave]): what the data flow needs is that the wave's own stores have landed before its
+                // loads of other lanes' rows, and the reverse before the next slot's stores.  __syncthreads() is the construct that promises exactly that for
+                // LDS, at the price of lining the four waves up twice per slot; a wave-scope fence in its place was measured, not adopted
+                // (docs/EXPERIMENTS.md section 15).
+                __syncthreads();          // the rows of the slot before have been read
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    s_t[wave][0][c][cagg_ch(j, h)] = dz2[j];
+                    s_t[wave][1][c][cagg_ch(j, h)] = h1[j];
+                    s_t[wave][2][c][cagg_ch(j, h)] = dz1[j];
+                }
+                *reinterpret_cast<float4*>(&s_x[wave][c][4 * h]) = h ? make_float4(x[4], x[5], x[6], in ? 1.0f : 0.0f) : make_float4(x[0], x[1], x[2], x[3]);
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < 16; ++kk) acc2 = cagg_mfma(s_t[wave][0][2 * kk + h][c], s_t[wave][1][2 * kk + h][c], acc2);          // pixels in order
+#pragma unroll 4
+                for (int t = 0; t < 16; ++t) accb += (double)s_t[wave][0][16 * h + t][c];
+#pragma unroll 4
+                for (int t = 0; t < CB; ++t) {
+                    const double d = (double)s_t[wave][2][t][r1];          // (a product of two floats is exact in f64)
+                    const float4 xe = *reinterpret_cast<const float4*>(&s_x[wave][t][c0]);
+                    acc1[0] = fma(d, (double)xe.x, acc1[0]); acc1[1] = fma(d, (double)xe.y, acc1[1]); acc1[2] = fma(d, (double)xe.z, acc1[2]); acc1[3] = fma(d, (double)xe.w, acc1[3]);
+                }
+            }
+        }
+        if constexpr (PG) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc2d[r] += (double)acc2[r]; acc2[r] = 0.0f; }
+        }
+        if (IG && in && h == 0) {
+            if (d_render) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) d_render[(size_t)ch * plane + p] = go[(size_t)(CF + 3 + ch) * plane + p] + dr[ch];
+            }
+            if (d_warped)
+                for (int k = L; k < S; ++k)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) d_warped[((size_t)k * 3 + ch) * plane + p] = 0.0f;
+        }
+    }
+    if constexpr (PG) {
+        double* const buf = reinterpret_cast<double*>(&s_t[0][0][0][0]);
+        double* const mine = buf + wave * CAGG_WAVE_WORDS;          // [dW2 (32 x 32) | dW1, db1 (32 x 8) | db2 by half (2 x 32)]
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mine[cagg_ch(r, h) * CF + c] = acc2d[r];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) mine[CF * CF + r1 * CINP + c0 + m] = acc1[m];
+        mine[CF * CF + CF * CINP + h * CF + c] = accb;
+        __syncthreads();
+        for (int e = threadIdx.x; e < CAGG_PARTIAL; e += CT) {          // the waves in order
+            double sum = 0.0;
+            for (int w = 0; w < CWAVES; ++w) {
+                const double* const src = buf + w * CAGG_WAVE_WORDS;
+                if (e < CF * CINP) sum += src[CF * CF + e];
+                else if (e < CF * CINP + CF * CF) sum += src[e - CF * CINP];
+                else sum += src[CF * CF + CF * CINP + (e - CF * CINP - CF * CF)] + src[CF * CF + CF * CINP + CF + (e - CF * CINP - CF * CF)];
+            }
+            partials[(size_t)blockIdx.x * CAGG_PARTIAL + e] = sum;
+        }
+    }
+}
+
+// element e of the workgroups' sums: series s adds the workgroups s, s + 16, .. in that order in f64, thread e adds the series in order
+__global__ void __launch_bounds__(CT) cagg_final_kernel(const double* __restrict__ partials, int groups, float* __restrict__ d_w1, float* __restrict__ d_b1,
+                                                        float* __restrict__ d_w2, float* __restrict__ d_b2)
+{
+    __shared__ double s_sum[FIN_SERIES][FIN_ELEMS];
+    const int el = threadIdx.x & (FIN_ELEMS - 1), series = threadIdx.x / FIN_ELEMS;
+    const int e = blockIdx.x * FIN_ELEMS + el;
+    double a = 0.0;
+    for (int g = series; g < groups; g += FIN_SERIES) a += partials[(size_t)g * CAGG_PARTIAL + e];
+    s_sum[series][el] = a;
+    __syncthreads();
+    if (threadIdx.x < FIN_ELEMS) {
+        double t = s_sum[0][el];
+        for (int k = 1; k < FIN_SERIES; ++k) t += s_sum[k][el];
+        const float v = (float)t;
+        if (e < CF * CINP) {
+            const int i = e >> 3, c = e & 7;
+            if (c < CIN) { if (d_w1) d_w1[i * CIN + c] = v; }
+            else if (d_b1) d_b1[i] = v;
+        } else if (e < CF * CINP + CF * CF) {
+            if (d_w2) d_w2[e - CF * CINP] = v;
+        } else if (d_b2) d_b2[e - CF * CINP - CF * CF] = v;
+    }
+}
+
+// who == nullptr: silent (the size query)
+static bool cagg_shape_ok(const char* who, int64_t S, int64_t H, int64_t W, size_t* plane)
+{
+    if (S < 1 || S > IBGS_CAGG_MAX_SRC || H < 1 || W < 1 || H > IBGS_CAGG_MAX_SIDE || W > IBGS_CAGG_MAX_SIDE) {
+        if (who) set_error("%s: %lld sources of %lld x %lld out of range (1 .. %d sources, sides 1 .. %d)", who, (long long)S, (long long)H, (long long)W, IBGS_CAGG_MAX_SRC,
+                           IBGS_CAGG_MAX_SIDE);
+        return false;
+    }
+    *plane = (size_t)H * (size_t)W;
+    return true;
+}
+
+static bool cagg_mode_ok(const char* who, int32_t mode)
+{
+    if (mode == IBGS_CAGG_MEAN || mode == IBGS_CAGG_MAX) return true;
+    set_error("%s: mode %d is neither IBGS_CAGG_MEAN nor IBGS_CAGG_MAX", who, mode);
+    return false;
+}
+
+static unsigned cagg_bwd_groups(size_t plane)
+{
+    const size_t chunks = (plane + CHUNK - 1) / CHUNK;
+    return (unsigned)(chunks < (size_t)CAGG_MAX_GROUPS ? chunks : (size_t)CAGG_MAX_GROUPS);
+}
+
+struct CaggScratch {
+    uint32_t* state;          // 2 words: the level count's flags and tickets
+    double* partials;         // workgroups of the backward x CAGG_PARTIAL
+    static CaggScratch carve(char* base, size_t plane, size_t* total)
+    {
+        CaggScratch d;
+        Carver c(base);
+        d.state = c.take<uint32_t>(2);
+        d.partials = c.take<double>((size_t)cagg_bwd_groups(plane) * CAGG_PARTIAL);
+        if (total) *total = c.cur - reinterpret_cast<uintptr_t>(base) + 128;
+        return d;
+    }
+};
+
+template <int MODE>
+static void cagg_launch_bwd(hipStream_t st, unsigned groups, bool ig, bool pg, const float* render, const float* warped, const float* feat, const float* w1, const float* b1,
+                            const float* w2, const float* b2, const int32_t* levels, int S, size_t plane, const float* go, float* d_render, float* d_warped, double* partials)
+{
+    if (ig && pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, true>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+    else if (pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, false, true>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+    else hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, false>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+}
+
+}  // namespace ibgs
+
+using namespace ibgs;
+
+extern "C" {
+
+size_t ibgs_cagg_required_scratch(int64_t S, int64_t H, int64_t W)
+{
+    size_t plane = 0, total = 0;
+    if (!cagg_shape_ok(nullptr, S, H, W, &plane)) return 0;
+    CaggScratch::carve(nullptr, plane, &total);
+    return total;
+}
+
+int32_t ibgs_cagg_levels(void* stream, int32_t S, int32_t H, int32_t W, const float* warped, int32_t nb_visible_src_frames, int32_t* levels_out, void* scratch,
+                         size_t scratch_bytes)
+{
+    size_t plane = 0, need = 0;
+    if (!cagg_shape_ok("cagg_levels", S, H, W, &plane)) return -IBGS_ERR_INVALID;
+    if (nb_visible_src_frames < 1) { set_error("cagg_levels: nb_visible_src_frames %d out of range (>= 1)", nb_visible_src_frames); return -IBGS_ERR_INVALID; }
+    if (!warped) { set_error("cagg_levels: null image"); return -IBGS_ERR_INVALID; }
+    if (!levels_out) { set_error("cagg_levels: null outputs: levels_out is required"); return -IBGS_ERR_INVALID; }
+    const CaggScratch sc = CaggScratch::carve(static_cast<char*>(scratch), plane, &need);
+    if (!arena_ok("cagg_levels", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t slot_elems = 3 * plane;
+    size_t per_slot = (slot_elems + (size_t)LV_THREADS * 16 - 1) / ((size_t)LV_THREADS * 16);
+    if (per_slot > (size_t)LV_MAX_BLOCKS) per_slot = LV_MAX_BLOCKS;
+    IBGS_HIP(hipMemsetAsync(sc.state, 0, 2 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cagg_levels_kernel, dim3((unsigned)((size_t)S * per_slot)), dim3(LV_THREADS), 0, st, warped, slot_elems, (int)per_slot, (int)S, (int)nb_visible_src_frames,
+                       sc.state, levels_out);
+    IBGS_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t ibgs_cagg_forward(void* stream, int32_t S, int32_t H, int32_t W, int32_t mode, const float* render, const float* warped, const float* cam_feat,
+                          const float* camera_ray, const float* w1, const float* b1, const float* w2, const float* b2, const int32_t* levels, float* out)
+{
+    size_t plane = 0;
+    if (!cagg_shape_ok("cagg_forward", S, H, W, &plane) || !cagg_mode_ok("cagg_forward", mode)) return -IBGS_ERR_INVALID;
+    if (!render || !warped || !cam_feat || !camera_ray) { set_error("cagg_forward: null image"); return -IBGS_ERR_INVALID; }
+    if (!w1 || !b1 || !w2 || !b2) { set_error("cagg_forward: null parameters"); return -IBGS_ERR_INVALID; }
+    if (!levels) { set_error("cagg_forward: null levels: the device word of cagg_levels is required"); return -IBGS_ERR_INVALID; }
+    if (!out) { set_error("cagg_forward: null outputs: out is required"); return -IBGS_ERR_INVALID; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    size_t groups = (plane + CHUNK - 1) / CHUNK;
+    if (groups > (size_t)CAGG_FWD_MAX_GROUPS) groups = CAGG_FWD_MAX_GROUPS;
+    if (mode == IBGS_CAGG_MEAN)
+        hipLaunchKernelGGL((cagg_fwd_kernel<IBGS_CAGG_MEAN>), dim3((unsigned)groups), dim3(CT), 0, st, render, warped, cam_feat, camera_ray, w1, b1, w2, b2, levels, (int)S, plane, out);
+    else
+        hipLaunchKernelGGL((cagg_fwd_kernel<IBGS_CAGG_MAX>), dim3((unsigned)groups), dim3(CT), 0, st, render, warped, cam_feat, camera_ray, w1, b1, w2, b2, levels, (int)S, plane, out);
+    IBGS_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t ibgs_cagg_backward(void* stream, int32_t S, int32_t H, int32_t W, int32_t mode, const float* render, const float* warped, const float* cam_feat,
+                           const float* w1, const float* b1, const float* w2, const float* b2, const int32_t* levels, const float* grad_out, float* grad_render,
+                           float* grad_warped, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* scratch, size_t scratch_bytes)
+{
+    size_t plane = 0, need = 0;
+    if (!cagg_shape_ok("cagg_backward", S, H, W, &plane) || !cagg_mode_ok("cagg_backward", mode)) return -IBGS_ERR_INVALID;
+    if (!render || !warped || !cam_feat) { set_error("cagg_backward: null image"); return -IBGS_ERR_INVALID; }
+    if (!w1 || !b1 || !w2 || !b2) { set_error("cagg_backward: null parameters"); return -IBGS_ERR_INVALID; }
+    if (!levels) { set_error("cagg_backward: null levels: the device word of cagg_levels is required"); return -IBGS_ERR_INVALID; }
+    if (!grad_out) { set_error("cagg_backward: null grad_out"); return -IBGS_ERR_INVALID; }
+    const bool ig = grad_render || grad_warped, pg = grad_w1 || grad_b1 || grad_w2 || grad_b2;
+    if (!ig && !pg) { set_error("cagg_backward: null outputs: no gradient is asked for"); return -IBGS_ERR_INVALID; }
+    CaggScratch sc = CaggScratch::carve(static_cast<char*>(scratch), plane, &need);
+    if (pg && !arena_ok("cagg_backward", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
+    if (!pg) sc.partials = nullptr;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned groups = cagg_bwd_groups(plane);
+    if (mode == IBGS_CAGG_MEAN)
+        cagg_launch_bwd<IBGS_CAGG_MEAN>(st, groups, ig, pg, render, warped, cam_feat, w1, b1, w2, b2, levels, (int)S, plane, grad_out, grad_render, grad_warped, sc.partials);
+    else
+        cagg_launch_bwd<IBGS_CAGG_MAX>(st, groups, ig, pg, render, warped, cam_feat, w1, b1, w2, b2, levels, (int)S, plane, grad_out, grad_render, grad_warped, sc.partials);
+    IBGS_HIP(hipGetLastError());
+    if (pg) {
+        hipLaunchKernelGGL(cagg_final_kernel, dim3(CAGG_PARTIAL / FIN_ELEMS), dim3(CT), 0, st, sc.partials, (int)groups, grad_w1, grad_b1, grad_w2, grad_b2);
+        IBGS_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // extern "C"
