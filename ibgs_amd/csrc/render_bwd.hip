@@ -26,11 +26,11 @@
 //   * geo: the median / warp block (B2) runs as a pixel-parallel pre-pass that leaves a per-pixel table; the blend loop only
 //     looks entries up (geo_window_kernel below).
 //
-// Deviations (documented in DESIGN.md): the skip test is the forward's single compare E <= log2(255) on the same staged numbers
-// (render_fwd.hip, common.h), so both passes visit exactly the same (pixel, Gaussian) pairs; alpha is recomputed with the
+// Deviations (documented in DESIGN.md): the skip test is the forward's single compare E <= log2(255) on the same staged numbers,
+// E formed by the one definition both units call (quadrant_E, blend.h), so both passes visit exactly the same (pixel, Gaussian) pairs; alpha is recomputed with the
 // same fast exp2 as the forward (the reference uses __expf forward / exp backward); 1/(1-alpha) is the hardware
 // reciprocal (1 ulp) instead of an IEEE division.
-#include "common.h"
+#include "blend.h"
 #include <stdlib.h>
 #include "wave_reduce.h"
 #include <type_traits>
@@ -62,14 +62,13 @@ struct BwdParams {
     float* slab;          // IBGS_FLAG_DETERMINISTIC: (R x waves per tile) x 16, one row per (list entry, wave of its tile), written instead of the atomics (else nullptr)
 };
 
-__device__ __forceinline__ float quant8b(float a, int quant) { return quant ? floorf(a * 256.0f + 0.5f) * (1.0f / 256.0f) : a; }
-
+// (not one function with render_fwd.hip's tex_rgba: this one is compiled uncontracted, that one is not -- merging them changes bits)
 __device__ __forceinline__ float4 tex_rgba_b(const float4* __restrict__ img, int W, int H, float x, float y, int quant)
 {
 #pragma clang fp contract(off)          // operation by operation like the oracle's tex_rgb (the pass that calls it is bound by its gathers)
     const float xb = x - 0.5f, yb = y - 0.5f;
     const float fxi = floorf(xb), fyi = floorf(yb);
-    const float a = quant8b(xb - fxi, quant), b = quant8b(yb - fyi, quant);
+    const float a = quant8(xb - fxi, quant), b = quant8(yb - fyi, quant);
     const int i0 = min(W - 1, max(0, (int)fxi)), i1 = min(W - 1, max(0, (int)fxi + 1));
     const int j0 = min(H - 1, max(0, (int)fyi)), j1 = min(H - 1, max(0, (int)fyi + 1));
     const float4 t00 = img[(size_t)j0 * W + i0], t10 = img[(size_t)j0 * W + i1];
@@ -82,14 +81,6 @@ __device__ __forceinline__ float4 tex_rgba_b(const float4* __restrict__ img, int
     r.w = 1.0f;
     return r;
 }
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, WAVE));
-    return v;
-}
-
 
 __device__ __forceinline__ float fast_rcp(float x)
 {   // v_rcp_f32 (1 ulp) + one Newton step
@@ -107,7 +98,7 @@ __device__ __forceinline__ float fast_rcp(float x)
 // order of the additions alone (ratio to the fp32 oracle builds: 0.8 .. 3.9 on one scene).  No per-pair value carries that; the chain does.  So for those
 // Gaussians the blend sums what the chain really needs,
 //        dL/dcov2D = 0.5 sum_pairs q l l^T,   l = conic d   (algebraically the same: -c^2 dx^2 + 2bc dx dy - b^2 dy^2 = -(c dx - b dy)^2 = -(det l_x)^2),
-// per pixel, where nothing cancels (RA_LFORM, the default: l_moments below, a wave-uniform branch of the fast kernels; preprocess_bwd.hip takes the three
+// per pixel, where nothing cancels (RA_LFORM, the default: l_moments, blend.h, a wave-uniform branch of the fast kernels; preprocess_bwd.hip takes the three
 // sums as dL/dcov2D): 3-10 x closer to float64 than the reference's own fp32 arithmetic and the same from run to run, whatever the order.
 // IBGS_FLAG_REF_ARITH selects the reference's arithmetic to the letter instead (RA_ASSOC; SURVEY Q1 as a switch): G = exp(power) at libm accuracy
 // (backward.cu:648), T / (1 - alpha) as an IEEE division (:654), the eight per-pair quantities of :779-804 in its association, uncontracted; the row then
@@ -117,11 +108,6 @@ __device__ __forceinline__ float fast_rcp(float x)
 // instantiation of the bodies below, launched behind the blend kernel, which skips those tiles).
 // The DECISIONS (which pairs blend) are the forward's either way: both passes visit the same pairs.
 constexpr int RA_DECIDE = 1, RA_LFORM = 2, RA_ASSOC = 4;
-__device__ __forceinline__ float ref_power(float dx, float dy, float a, float b, float c)
-{
-#pragma clang fp contract(off)
-    return -0.5f * (a * dx * dx + c * dy * dy) - b * dx * dy;          // forward.cu:419, backward.cu:644
-}
 // RA_ASSOC: rs[0..1] dL/dG dG/ddel{x,y} (x 0.5 W / 0.5 H in preprocess_bwd), rs[2..3] their magnitudes, rs[4..6] gd{x,x,y} d{x,y,y} dL/dG (x -0.5 there), rs[7] G dL/dalpha
 __device__ __forceinline__ void ref_pair_sums(float (&rs)[8], float G, float dL_dalpha, float dx, float dy, float o, float a, float b, float c)
 {
@@ -134,26 +120,6 @@ __device__ __forceinline__ void ref_pair_sums(float (&rs)[8], float G, float dL_
     rs[0] += mx; rs[1] += my; rs[2] += fabsf(mx); rs[3] += fabsf(my);
     rs[4] += gdx * dx * dL_dG; rs[5] += gdx * dy * dL_dG; rs[6] += gdy * dy * dL_dG;
     rs[7] += G * dL_dalpha;
-}
-// The six geometric sums of a near-singular conic on the fast path, in l-space: v[0..1] = sum q l, v[4..6] = sum q l l^T, v[7] = sum q over the lane's pixels, with
-// l = (scaled conic) d formed per pixel -- the quadrant-0 value shifted like E (d_q = d_0 - (8,0), (0,8), (8,8)).  What cancels catastrophically downstream of the
-// d-moments (K S K with K = conic) never enters: l is small where the Gaussian is.  ~30 instructions instead of 17, for these Gaussians only (a wave-uniform branch).
-// preprocess_bwd.hip undoes the exp2 scale of the conic (EXP2_UNSCALE, squared for the second moments) and takes the second moments as dL/dcov2D.
-template <int PPL, int NV>
-__device__ __forceinline__ void l_moments(float (&v)[NV], const float (&Q)[PPL], float dx0, float dy0, float ca, float cb, float cc)
-{
-    const float lx0 = ca * dx0 + cb * dy0, ly0 = cb * dx0 + cc * dy0;
-    float sx = 0.f, sy = 0.f, sxx = 0.f, sxy = 0.f, syy = 0.f, s0 = 0.f;
-#pragma unroll
-    for (int q = 0; q < PPL; q++) {
-        // pixel offsets of the lane's quadrants: PPL == 4: (0,0), (8,0), (0,8), (8,8); PPL == 2: (0,0), (8,0)
-        const float ox = (PPL == 4) ? (float)((q & 1) * 8) : (float)(q * 8), oy = (PPL == 4) ? (float)((q >> 1) * 8) : 0.f;
-        const float lx = fmaf(-ox, ca, fmaf(-oy, cb, lx0)), ly = fmaf(-ox, cb, fmaf(-oy, cc, ly0));
-        const float qx = Q[q] * lx, qy = Q[q] * ly;
-        sx += qx; sy += qy; s0 += Q[q];
-        sxx = fmaf(qx, lx, sxx); sxy = fmaf(qx, ly, sxy); syy = fmaf(qy, ly, syy);
-    }
-    v[0] = sx; v[1] = sy; v[4] = sxx; v[5] = sxy; v[6] = syy; v[7] = s0;
 }
 // is `tile` one of the flagged tiles?  (four words per tile: one per wave of the forward variant that walked it, unused ones zero)
 __device__ __forceinline__ bool tile_is_risky(const uint32_t* __restrict__ tile_risky, int tile)
@@ -168,12 +134,8 @@ __device__ __forceinline__ bool tile_is_risky(const uint32_t* __restrict__ tile_
 // ~24 VALU instructions instead of ~41 (the kernel is VALU-issue bound):
 //   * what a lane keeps per quadrant is ONE number, Q_q = o G dL/dalpha of its pixel there (0 when the quadrant is skipped);
 //     the six geometric moments are formed once per Gaussian from Q_0..Q_3 and the lane's d0 = (Gaussian centre - its
-//     quadrant-0 pixel): the other three pixels sit at d0 - (8,0), (0,8), (8,8), so
-//         sum Q d   = d0 S0 - 8 (A, B),                      A = Q1 + Q3, B = Q2 + Q3, S0 = Q0 + Q1 + Q2 + Q3
-//         sum Q dx^2 = dx0 (dx0 S0 - 16 A) + 64 A            (likewise y)
-//         sum Q dx dy = dy0 Sx - 8 (dx0 B - 8 Q3)
-//     -- 17 instructions per Gaussian instead of 8 per (Gaussian, quadrant);
-//   * conic * d of the other quadrants (only the |.| moments need it) comes from the quadrant-0 value by one fma each;
+//     quadrant-0 pixel) -- d_moments, blend.h: 17 instructions per Gaussian instead of 8 per (Gaussian, quadrant);
+//   * conic * d of the other quadrants (only the |.| moments need it) comes from the quadrant-0 value by one fma each (quadrant_E_l, blend.h);
 //   * the per-pixel constants dL/dC and -T_final (bg . dL/dC) travel as ONE 16-byte LDS read;
 //   * one select (on G) instead of two, 1/(1 - alpha) is the bare v_rcp_f32 (1 ulp; the Newton step bought nothing that the
 //     parity bars see: T picks up ~1e-7 sqrt(k) relative noise over k divisions);
@@ -220,7 +182,9 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
     float T[PPL], S[PPL];
     uint32_t ncontrib[PPL];
     uint32_t nmax = 0;
-    const float pxf0 = (float)(tx0 + (quad0 & 1) * 8 + (lane & 7)), pyf0 = (float)(ty0 + (quad0 >> 1) * 8 + (lane >> 3));
+    const float pxf0 = (float)quadrant_x(tx0, quad0, lane), pyf0 = (float)quadrant_y(ty0, quad0, lane);
+    // per-pixel prologue: written out here and in render_bwd_geo_body (pixel mapping included) -- as a shared helper it changed the branch shape of the guarded
+    // loads in every blend kernel (docs/EXPERIMENTS.md section 16)
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
         const int qq = quad0 + q;
@@ -266,28 +230,18 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
         const int count = min(CHUNK, top);
         bool risky = false, ordinary = false;
         if (lane < count) {   // stage in processing order: slot l holds entry top-1-l
-            const uint32_t id = p.point_list[r0 + (uint32_t)(top - 1 - lane)];
-            const float4* r = p.rec + (size_t)id * 4;
-            float4 ra = r[0];
-            ra.w = __uint_as_float(id);            // the record's spare slot carries the Gaussian index to the atomic
-            float4 c1 = r[1];
-            risky = conic_takes_ref_power(c1.x, c1.y, c1.z);
-            stage_for_exp2(ra, c1);                            // as the forward stages them (common.h): same numbers, same decisions
+            float4 ra, c1;
+            const float4* r = bwd_stage_record(p.point_list, p.rec, r0 + (uint32_t)(top - 1 - lane), ra, c1, risky);
             ordinary = !record_is_plain(ra.z, c1.x, risky);
             lds_store4(&s_rec[0][0], lane16, ra); lds_store4(&s_rec[1][0], lane16, c1); lds_store4(&s_rec[2][0], lane16, r[2]);          // = s_rec[.][lane]
         }
         const uint64_t riskm = p.power_skip ? __builtin_amdgcn_ballot_w64(risky) : 0ull;      // near-singular conics: the forward's rare branch
         // a PLAIN chunk (common.h: clamp_free): the 0.99 clamp binds for none of its records and none is near-singular -- decided once per chunk, the loop dispatched whole
         const bool plain = !RISK && bg0 && !p.no_plain && __builtin_amdgcn_ballot_w64(ordinary) == 0ull;          // wave-uniform
-        // pixels that take part: k < n_contrib.  k runs from top-1 down to top-count in this chunk and a pixel only ever
-        // switches ON (at k = n_contrib - 1), so when the masks at both ends agree they hold for the whole chunk.
-        uint64_t ncm[PPL];
+        uint64_t ncm[PPL];          // pixels that take part: k < n_contrib, good for the whole chunk when `stable`
         bool stable = true;
 #pragma unroll
-        for (int q = 0; q < PPL; q++) {
-            ncm[q] = __builtin_amdgcn_ballot_w64((uint32_t)(top - count) < ncontrib[q]);
-            stable = stable && (ncm[q] == __builtin_amdgcn_ballot_w64((uint32_t)(top - 1) < ncontrib[q]));
-        }
+        for (int q = 0; q < PPL; q++) ncm[q] = bwd_chunk_mask(ncontrib[q], top, count, stable);
         __syncthreads();
         auto chunk = [&](auto stable_tag, auto bg0_tag, auto lds_tag, auto plain_tag) {
             constexpr bool STABLE = decltype(stable_tag)::value;
@@ -300,32 +254,16 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                 const uint32_t k = (uint32_t)(top - 1 - j);          // 0-based position in the tile list
                 const float4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j];
                 const float ca = q1.x, cb = q1.y, cc = q1.z, nlo = q0.z;          // scaled conic, -log2(opacity)
-                // same evaluation of p2 = d^T conic d as the forward (render_fwd.hip): once per lane, shifted to the
-                // other three quadrants, so both passes take identical alpha decisions
-                const float dx0 = q0.x - pxf0, dy0 = q0.y - pyf0;
-                const float lx0 = ca * dx0 + cb * dy0, ly0 = cb * dx0 + cc * dy0;
-                const float P0 = fmaf(dx0, lx0, fmaf(dy0, ly0, nlo));          // the forward's E (render_fwd.hip)
-                float p2q[PPL], lxq[PPL], lyq[PPL];
-                p2q[0] = P0; lxq[0] = lx0; lyq[0] = ly0;
-                if constexpr (PPL >= 2) {
-                    p2q[1] = fmaf(-16.0f, lx0, P0 + 64.0f * ca);
-                    if constexpr (ABS) { lxq[1] = fmaf(-8.0f, ca, lx0); lyq[1] = fmaf(-8.0f, cb, ly0); }
-                }
-                if constexpr (PPL == 4) {
-                    p2q[2] = fmaf(-16.0f, ly0, P0 + 64.0f * cc);
-                    p2q[3] = fmaf(128.0f, cb, p2q[2] + (p2q[1] - P0));          // E3 = E2 + (E1 - E0) + 128 b: three instructions, as the forward
-                    if constexpr (ABS) {
-                        lxq[2] = fmaf(-8.0f, cb, lx0); lyq[2] = fmaf(-8.0f, cc, ly0);
-                        lxq[3] = fmaf(-8.0f, cb, lxq[1]); lyq[3] = fmaf(-8.0f, cc, lyq[1]);
-                    }
-                }
+                float p2q[PPL], lxq[PPL], lyq[PPL], dx0, dy0;          // the forward's E, by the forward's expressions (blend.h): both passes take identical alpha decisions
+                quadrant_E_l<PPL, ABS>(p2q, lxq, lyq, dx0, dy0, q0, q1, pxf0, pyf0);
                 if constexpr (!RISK && !PLAIN) {
                     if ((riskm >> j) & 1ull) {          // wave-uniform and rare: E from the reference's expression, `power > 0` pairs dropped (common.h); the sums: l_moments below
                         const uint32_t gid = __builtin_amdgcn_readfirstlane(__float_as_uint(q0.w));
                         const float4 g0 = p.rec[(size_t)gid * 4], g1 = p.rec[(size_t)gid * 4 + 1];
 #pragma unroll
                         for (int q = 0; q < PPL; q++) {
-                            const float ox = (PPL == 4) ? (float)((q & 1) * 8) : (float)(q * 8), oy = (PPL == 4) ? (float)((q >> 1) * 8) : 0.f;
+                            float ox, oy;
+                            quadrant_offset<PPL>(q, ox, oy);
                             p2q[q] = ref_power_E(g0.x - (pxf0 + ox), g0.y - (pyf0 + oy), g1.x, g1.y, g1.z, nlo);
                         }
                     }
@@ -339,27 +277,18 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                         bool rany = false;
 #pragma unroll
                         for (int q = 0; q < PPL; q++) {
-                            const float ox = (PPL == 4) ? (float)((q & 1) * 8) : (float)(q * 8), oy = (PPL == 4) ? (float)((q >> 1) * 8) : 0.f;
-                            const float dx = g0.x - (pxf0 + ox), dy = g0.y - (pyf0 + oy);
-                            const float power = ref_power(dx, dy, g1.x, g1.y, g1.z);
-                            const float E = ref_power_E(dx, dy, g1.x, g1.y, g1.z, nlo);          // what both passes decide on (+inf: `power > 0`)
-                            const uint64_t okm = __builtin_amdgcn_ballot_w64(k < ncontrib[q]) & __builtin_amdgcn_ballot_w64(E <= ALPHA_SKIP_E);
-                            if (okm == 0ull) continue;
+                            const RefPair rp = ref_pair_head<PPL>(q, pxf0, pyf0, g0, g1, nlo, k, ncontrib[q], T[q]);
+                            if (rp.okm == 0ull) continue;
                             rany = true;
-                            const float Gr = __builtin_amdgcn_inverse_ballot_w64(okm) ? expf(power) : 0.f;          // backward.cu:648; 0 where the test fails: alpha = 0 leaves T and S unchanged
-                            const float oG = g0.z * Gr;
-                            const float alpha = fminf(0.99f, oG);
-                            const float om = 1.f - alpha;
-                            T[q] = T[q] / om;          // backward.cu:654
-                            const float w = alpha * T[q];
+                            const float alpha = rp.alpha, w = rp.w;
                             const float4 gp = s_gpix[q][lane];
                             const float cg = q2.x * gp.x + q2.y * gp.y + q2.z * gp.z;
                             float dL_dalpha = cg - S[q];
                             S[q] = fmaf(alpha, dL_dalpha, S[q]);
                             rR = fmaf(w, gp.x, rR); rG = fmaf(w, gp.y, rG); rB = fmaf(w, gp.z, rB);
                             dL_dalpha = dL_dalpha * T[q];
-                            if constexpr (!BG0) dL_dalpha += gp.w / om;          // ... - T_final (bg . g) / (1 - alpha)
-                            ref_pair_sums(rs, Gr, dL_dalpha, dx, dy, g0.z, g1.x, g1.y, g1.z);
+                            if constexpr (!BG0) dL_dalpha += gp.w / rp.om;          // ... - T_final (bg . g) / (1 - alpha)
+                            ref_pair_sums(rs, rp.G, dL_dalpha, rp.dx, rp.dy, g0.z, g1.x, g1.y, g1.z);
                         }
                         if (__builtin_amdgcn_ballot_w64(rany) != 0ull) {
                             float v[12] = {rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rR, rG, rB, 0.f};
@@ -377,7 +306,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                 IBGS_LANES_ADD(0, 1);
 #pragma unroll
                 for (int q = 0; q < PPL; q++) {
-                    // the forward's test: E <= log2(255) (render_fwd.hip, common.h)
+                    // the forward's test: E <= log2(255) (blend.h, common.h)
                     const uint64_t live = STABLE ? ncm[q] : __builtin_amdgcn_ballot_w64(k < ncontrib[q]);
                     const uint64_t okm = live & __builtin_amdgcn_ballot_w64(p2q[q] <= ALPHA_SKIP_E);
                     Q[q] = 0.f;
@@ -417,19 +346,7 @@ __device__ __forceinline__ void render_bwd_color_body(const BwdParams& p, const 
                     // v[]: 0 Sx, 1 Sy, 2 Ax, 3 Ay, 4 Sxx, 5 Sxy, 6 Syy, 7 S0, 8-10 rgb (= grad_acc columns)
                     float v[12];
                     if (!RISK && !PLAIN && ((riskm >> j) & 1ull)) l_moments<PPL>(v, Q, dx0, dy0, ca, cb, cc);          // wave-uniform: a near-singular conic (see above)
-                    else
-                    if constexpr (PPL == 4) {
-                        const float A = Q[1] + Q[3], B = Q[2] + Q[3], S0 = (Q[0] + Q[2]) + A;
-                        const float t = dx0 * S0, u = dy0 * S0;
-                        v[0] = fmaf(-8.0f, A, t); v[1] = fmaf(-8.0f, B, u);
-                        v[4] = fmaf(dx0, fmaf(-16.0f, A, t), 64.0f * A);
-                        v[6] = fmaf(dy0, fmaf(-16.0f, B, u), 64.0f * B);
-                        v[5] = fmaf(-8.0f, fmaf(-8.0f, Q[3], dx0 * B), dy0 * v[0]);
-                        v[7] = S0;
-                    } else {
-                        const float qdx = Q[0] * dx0, qdy = Q[0] * dy0;
-                        v[0] = qdx; v[1] = qdy; v[4] = qdx * dx0; v[5] = qdx * dy0; v[6] = qdy * dy0; v[7] = Q[0];
-                    }
+                    else d_moments<PPL>(v, Q, dx0, dy0);
                     v[2] = aX; v[3] = aY;          // (conic * d was formed with the scaled conic: preprocess_bwd multiplies these two sums by EXP2_UNSCALE)
                     v[8] = vR; v[9] = vG; v[10] = vB; v[11] = 0.f;
                     float tot;
@@ -584,7 +501,7 @@ __global__ void __launch_bounds__(256, 6) geo_window_kernel(BwdParams p)
                     const float4 t01 = img[(size_t)yj1 * W + xi0], t11 = img[(size_t)yj1 * W + xi1], t21 = img[(size_t)yj1 * W + xi2];
                     const float4 t02 = img[(size_t)yj2 * W + xi0], t12 = img[(size_t)yj2 * W + xi1], t22 = img[(size_t)yj2 * W + xi2];
                     // tex_rgba_b at an integer coordinate: a = b = 0.5 exactly (also after the 8-bit weight rounding), all four weights 0.25
-                    const float a = quant8b(0.5f, p.tex_quant), b = quant8b(0.5f, p.tex_quant);
+                    const float a = quant8(0.5f, p.tex_quant), b = quant8(0.5f, p.tex_quant);
                     const float w00 = (1.f - a) * (1.f - b), w10 = a * (1.f - b), w01 = (1.f - a) * b, w11 = a * b;
                     auto quad = [&](const float4& q00, const float4& q10, const float4& q01, const float4& q11) {
                         float4 r;
@@ -643,7 +560,7 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
     const bool bg0 = p.cam.bg[0] == 0.f && p.cam.bg[1] == 0.f && p.cam.bg[2] == 0.f;      // wave-uniform (scalar loads), as in the colour body
     uint32_t ncontrib[PPL], next_c[PPL], slot[PPL], pixo[PPL];
     uint32_t nmax = 0;
-    const float pxf0 = (float)(tx0 + (quad0 & 1) * 8 + (lane & 7)), pyf0 = (float)(ty0 + (quad0 >> 1) * 8 + (lane >> 3));
+    const float pxf0 = (float)quadrant_x(tx0, quad0, lane), pyf0 = (float)quadrant_y(ty0, quad0, lane);
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
         const int qq = quad0 + q;
@@ -678,23 +595,15 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
         const int count = min(CHUNK, top);
         bool risky = false;
         if (lane < count) {
-            const uint32_t id = p.point_list[r0 + (uint32_t)(top - 1 - lane)];
-            const float4* r = p.rec + (size_t)id * 4;
-            float4 ra = r[0];
-            ra.w = __uint_as_float(id);
-            float4 c1 = r[1];
-            risky = conic_takes_ref_power(c1.x, c1.y, c1.z);
-            stage_for_exp2(ra, c1);
+            float4 ra, c1;
+            const float4* r = bwd_stage_record(p.point_list, p.rec, r0 + (uint32_t)(top - 1 - lane), ra, c1, risky);
             s_rec[0][lane] = ra; s_rec[1][lane] = c1; s_rec[2][lane] = r[2]; s_rec[3][lane] = r[3];
         }
         const uint64_t riskm = p.power_skip ? __builtin_amdgcn_ballot_w64(risky) : 0ull;
         uint64_t ncm[PPL];
         bool stable = true;
 #pragma unroll
-        for (int q = 0; q < PPL; q++) {
-            ncm[q] = __builtin_amdgcn_ballot_w64((uint32_t)(top - count) < ncontrib[q]);
-            stable = stable && (ncm[q] == __builtin_amdgcn_ballot_w64((uint32_t)(top - 1) < ncontrib[q]));
-        }
+        for (int q = 0; q < PPL; q++) ncm[q] = bwd_chunk_mask(ncontrib[q], top, count, stable);
         __syncthreads();
         auto chunk = [&](auto stable_tag, auto bg0_tag) {
             constexpr bool STABLE = decltype(stable_tag)::value;
@@ -703,30 +612,16 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
                 const uint32_t k = (uint32_t)(top - 1 - j);
                 const float4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j], q3 = s_rec[3][j];
                 const float ca = q1.x, cb = q1.y, cc = q1.z, nlo = q0.z;          // scaled conic, -log2(opacity)
-                const float dx0 = q0.x - pxf0, dy0 = q0.y - pyf0;
-                const float lx0 = ca * dx0 + cb * dy0, ly0 = cb * dx0 + cc * dy0;
-                const float P0 = fmaf(dx0, lx0, fmaf(dy0, ly0, nlo));          // the forward's E (render_fwd.hip)
-                float p2q[PPL], lxq[PPL], lyq[PPL];
-                p2q[0] = P0; lxq[0] = lx0; lyq[0] = ly0;
-                if constexpr (PPL >= 2) {
-                    p2q[1] = fmaf(-16.0f, lx0, P0 + 64.0f * ca);
-                    if constexpr (ABS) { lxq[1] = fmaf(-8.0f, ca, lx0); lyq[1] = fmaf(-8.0f, cb, ly0); }
-                }
-                if constexpr (PPL == 4) {
-                    p2q[2] = fmaf(-16.0f, ly0, P0 + 64.0f * cc);
-                    p2q[3] = fmaf(128.0f, cb, p2q[2] + (p2q[1] - P0));          // E3 = E2 + (E1 - E0) + 128 b: three instructions, as the forward
-                    if constexpr (ABS) {
-                        lxq[2] = fmaf(-8.0f, cb, lx0); lyq[2] = fmaf(-8.0f, cc, ly0);
-                        lxq[3] = fmaf(-8.0f, cb, lxq[1]); lyq[3] = fmaf(-8.0f, cc, lyq[1]);
-                    }
-                }
+                float p2q[PPL], lxq[PPL], lyq[PPL], dx0, dy0;          // the forward's E (blend.h)
+                quadrant_E_l<PPL, ABS>(p2q, lxq, lyq, dx0, dy0, q0, q1, pxf0, pyf0);
                 if constexpr (!RISK) {
                     if ((riskm >> j) & 1ull) {          // wave-uniform and rare: E from the reference's expression, `power > 0` pairs dropped (common.h); the sums: l_moments below
                         const uint32_t gid = __builtin_amdgcn_readfirstlane(__float_as_uint(q0.w));
                         const float4 g0 = p.rec[(size_t)gid * 4], g1 = p.rec[(size_t)gid * 4 + 1];
 #pragma unroll
                         for (int q = 0; q < PPL; q++) {
-                            const float ox = (PPL == 4) ? (float)((q & 1) * 8) : (float)(q * 8), oy = (PPL == 4) ? (float)((q >> 1) * 8) : 0.f;
+                            float ox, oy;
+                            quadrant_offset<PPL>(q, ox, oy);
                             p2q[q] = ref_power_E(g0.x - (pxf0 + ox), g0.y - (pyf0 + oy), g1.x, g1.y, g1.z, nlo);
                         }
                     }
@@ -739,19 +634,11 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
                         bool rany = false;
 #pragma unroll
                         for (int q = 0; q < PPL; q++) {
-                            const float ox = (PPL == 4) ? (float)((q & 1) * 8) : (float)(q * 8), oy = (PPL == 4) ? (float)((q >> 1) * 8) : 0.f;
-                            const float dx = g0.x - (pxf0 + ox), dy = g0.y - (pyf0 + oy);
-                            const float power = ref_power(dx, dy, g1.x, g1.y, g1.z);
-                            const float E = ref_power_E(dx, dy, g1.x, g1.y, g1.z, nlo);
-                            const uint64_t okm = __builtin_amdgcn_ballot_w64(k < ncontrib[q]) & __builtin_amdgcn_ballot_w64(E <= ALPHA_SKIP_E);
+                            const RefPair rp = ref_pair_head<PPL>(q, pxf0, pyf0, g0, g1, nlo, k, ncontrib[q], T[q]);
+                            const uint64_t okm = rp.okm;
                             if (okm == 0ull) continue;
                             rany = true;
-                            const float Gr = __builtin_amdgcn_inverse_ballot_w64(okm) ? expf(power) : 0.f;
-                            const float oG = g0.z * Gr;
-                            const float alpha = fminf(0.99f, oG);
-                            const float om = 1.f - alpha;
-                            T[q] = T[q] / om;
-                            const float w = alpha * T[q];
+                            const float alpha = rp.alpha, w = rp.w;
                             const float4 gp = s_gpix[q][lane], gn = s_gnrm[q][lane];
                             const float cg = q2.x * gp.x + q2.y * gp.y + q2.z * gp.z + q3.x * gn.x + q3.y * gn.y + q3.z * gn.z;
                             float dL_dalpha = cg - S[q];
@@ -770,8 +657,8 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
                                 }
                             }
                             dL_dalpha = dL_dalpha * T[q];
-                            if constexpr (!BG0) dL_dalpha += gp.w / om;
-                            ref_pair_sums(rs, Gr, dL_dalpha, dx, dy, g0.z, g1.x, g1.y, g1.z);
+                            if constexpr (!BG0) dL_dalpha += gp.w / rp.om;
+                            ref_pair_sums(rs, rp.G, dL_dalpha, rp.dx, rp.dy, g0.z, g1.x, g1.y, g1.z);
                         }
                         if (__builtin_amdgcn_ballot_w64(rany) != 0ull) {
                             float v[16] = {rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rR, rG, rB, rNx, rNy, rNz, rD, 0.f};
@@ -828,26 +715,7 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
                     // v[]: 0 Sx, 1 Sy, 2 Ax, 3 Ay, 4 Sxx, 5 Sxy, 6 Syy, 7 S0, 8-10 rgb, 11-13 normal, 14 dist (= grad_acc columns)
                     float v[16];
                     if (!RISK && ((riskm >> j) & 1ull)) l_moments<PPL>(v, Q, dx0, dy0, ca, cb, cc);          // wave-uniform: a near-singular conic (see above)
-                    else
-                    if constexpr (PPL == 4) {
-                        const float A = Q[1] + Q[3], B = Q[2] + Q[3], S0 = (Q[0] + Q[2]) + A;
-                        const float t = dx0 * S0, u = dy0 * S0;
-                        v[0] = fmaf(-8.0f, A, t); v[1] = fmaf(-8.0f, B, u);
-                        v[4] = fmaf(dx0, fmaf(-16.0f, A, t), 64.0f * A);
-                        v[6] = fmaf(dy0, fmaf(-16.0f, B, u), 64.0f * B);
-                        v[5] = fmaf(-8.0f, fmaf(-8.0f, Q[3], dx0 * B), dy0 * v[0]);
-                        v[7] = S0;
-                    } else if constexpr (PPL == 2) {       // two quadrants side by side: d1 = d0 - (8, 0)
-                        const float S0 = Q[0] + Q[1];
-                        const float t = dx0 * S0;
-                        v[0] = fmaf(-8.0f, Q[1], t); v[1] = dy0 * S0;
-                        v[4] = fmaf(dx0, fmaf(-16.0f, Q[1], t), 64.0f * Q[1]);
-                        v[5] = dy0 * v[0]; v[6] = dy0 * v[1];
-                        v[7] = S0;
-                    } else {
-                        const float qdx = Q[0] * dx0, qdy = Q[0] * dy0;
-                        v[0] = qdx; v[1] = qdy; v[4] = qdx * dx0; v[5] = qdx * dy0; v[6] = qdy * dy0; v[7] = Q[0];
-                    }
+                    else d_moments<PPL>(v, Q, dx0, dy0);
                     v[2] = aX; v[3] = aY;          // (conic * d was formed with the scaled conic: preprocess_bwd multiplies these two sums by EXP2_UNSCALE)
                     v[8] = vR; v[9] = vG; v[10] = vB; v[11] = vNx; v[12] = vNy; v[13] = vNz; v[14] = vD; v[15] = 0.f;
                     const float tot = wave_transpose_reduce16(v, lane);
@@ -871,6 +739,8 @@ __device__ __forceinline__ void render_bwd_geo_body(const BwdParams& p, const in
 #ifdef IBGS_TRACE_WAVES
 __device__ uint4 g_trace_bwd[IBGS_TRACE_MAX];
 #endif
+// (These two entries and render_bwd_geo_entry decode their order word in place, and the two colour entries are written out twice: behind ordered_tile (blend.h) and
+// one render_bwd_color_entry<ABS> the kernels' scalar entry code came out an instruction longer or shorter -- docs/EXPERIMENTS.md section 16.)
 __global__ void __launch_bounds__(64, 8) render_bwd_color_kernel(BwdParams p)
 {
     IBGS_TRACE_BEGIN();
@@ -901,7 +771,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_color_risk_kernel(BwdParams 
     __shared__ float4 s_rec[3][BWD_CHUNK];
     __shared__ float4 s_gpix[4][WAVE];
     int tile = (int)blockIdx.x;
-    if (p.order) { const uint32_t t = p.order[blockIdx.x]; if (t == 0xFFFFFFFFu) return; tile = (int)(t & ~ORDER_SPLIT_BIT); }
+    if (p.order && !ordered_tile(p.order, blockIdx.x, tile)) return;
     if (tile >= p.ntiles || !tile_is_risky(p.tile_risky, tile)) return;
     render_bwd_color_body<4, ABS, true>(p, tile, 0, s_rec, s_gpix);
 }
@@ -1030,7 +900,7 @@ __global__ void __launch_bounds__(64, 3) render_bwd_geo_risk_kernel(BwdParams p)
     __shared__ float4 s_gpix[4][WAVE];
     __shared__ float4 s_gnrm[4][WAVE];
     int tile = (int)blockIdx.x;
-    if (p.order) { const uint32_t t = p.order[blockIdx.x]; if (t == 0xFFFFFFFFu) return; tile = (int)(t & ~ORDER_SPLIT_BIT); }
+    if (p.order && !ordered_tile(p.order, blockIdx.x, tile)) return;
     if (tile >= p.ntiles || !tile_is_risky(p.tile_risky, tile)) return;
     render_bwd_geo_body<4, ABS, true>(p, tile, 0, s_rec, s_gpix, s_gnrm);
 }

@@ -13,7 +13,8 @@
 //     Gaussian per 256 pixels.
 //   * Each quadrant is skipped with a wave-uniform branch when no lane passes the alpha test (ballot), which
 //     recovers 8x8 sub-tile culling.  What a lane holds per pixel is E = -log2(o G) (conic staged in exp2 units, the quadratic form
-//     started from -log2 o, common.h); the test is the one compare E <= log2(255): no exp for pairs that fail, and alpha is
+//     started from -log2 o, common.h; evaluated once per lane and shifted to its other pixels by quadrant_E, blend.h -- the one definition that
+//     the backward uses too); the test is the one compare E <= log2(255): no exp for pairs that fail, and alpha is
 //     min(0.99, exp2(-E)) without a multiply.  "Pixel still blending" is a
 //     64-bit lane mask kept in SGPRs (one per quadrant): masks are combined on the scalar unit and
 //     turned back into predicates with inverse_ballot, so the blend itself is branch-free VALU code and
@@ -22,7 +23,8 @@
 //   * CUDA layered textures do not exist on gfx950; source images are packed to RGBA float4 once per
 //     call and sampled with explicit bilinear gathers that follow the texture unit's addressing rules
 //     (unnormalised, clamp, linear).
-#include "common.h"
+// blend.h holds what this unit shares with render_bwd.hip: the exponent, the pixel mapping, quant8, wave_max_u32, the order-word decoding.
+#include "blend.h"
 
 namespace ibgs {
 
@@ -69,10 +71,8 @@ int launch_pack_rgba(hipStream_t s, const float* src, float4* dst, int W, int H,
     return 0;
 }
 
-__device__ __forceinline__ float quant8(float a, int quant) { return quant ? floorf(a * 256.0f + 0.5f) * (1.0f / 256.0f) : a; }
-
 // Linear-filtered, clamp-addressed fetch at unnormalised texture coordinate (x, y) -- texel centres
-// at i + 0.5 (what tex2DLayered does with the descriptor of rasterizer_impl.cu:120-126).
+// at i + 0.5 (what tex2DLayered does with the descriptor of rasterizer_impl.cu:120-126).  (Not one function with render_bwd.hip's tex_rgba_b: that one is uncontracted, this one is not -- other bits.)
 __device__ __forceinline__ float4 tex_rgba(const float4* __restrict__ img, int W, int H, float x, float y, int quant)
 {
     const float xb = x - 0.5f, yb = y - 0.5f;
@@ -117,9 +117,8 @@ __device__ unsigned long long g_lanes_fwd[4];
 // The wave's work: `sub` of the 4 / PPL waves of `tile`.  s_rec: the caller's staging area (NQ x CHUNK float4; a kernel that holds two
 // instantiations of the body -- the hybrid colour kernel below -- hands both the same one).
 // TILE_Q >= 0 (PPL == 1, the hybrid kernel's quadrant waves; = sub, at compile time): the exponent E of the wave's pixels is formed exactly as a tile wave
-// forms it for that quadrant -- for the lane's quadrant-0 pixel, then shifted -- so that a pixel's colour does not depend, not by one bit, on which shape
-// walked its tile.  (With the quadrant as a run-time value the select between the four expressions became a chain of six scalar branches per list entry:
-// quadrant waves 0.35 -> 0.51 ms at 400 x 400.)
+// forms it for that quadrant (quadrant_E, blend.h).  (With the quadrant as a run-time value the select between the four expressions became a chain of six
+// scalar branches per list entry: quadrant waves 0.35 -> 0.51 ms at 400 x 400.)
 template <int MODE, int PPL, int MAXL, int TILE_Q = -1>
 __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int tile, const int sub,
                                                 float4 (&s_rec)[(MODE == MODE_GEO) ? 4 : 3][(MODE == MODE_GEO) ? 16 : WAVE])
@@ -156,15 +155,14 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
         const int qq = quad0 + q;
-        px[q] = tx0 + (qq & 1) * 8 + (lane & 7);
-        py[q] = ty0 + (qq >> 1) * 8 + (lane >> 3);
+        px[q] = quadrant_x(tx0, qq, lane); py[q] = quadrant_y(ty0, qq, lane);
         pxf[q] = (float)px[q]; pyf[q] = (float)py[q];
         inside[q] = px[q] < W && py[q] < H;
         live[q] = __builtin_amdgcn_ballot_w64(inside[q]);
         recm[q] = live[q];
         T[q] = 1.0f; C[q][0] = C[q][1] = C[q][2] = 0.f; lastc[q] = 0;
     }
-    const float pxf_t0 = (float)(tx0 + (lane & 7)), pyf_t0 = (float)(ty0 + (lane >> 3));          // the lane's pixel in quadrant 0 of the tile (TILE_Q)
+    const float pxf_t0 = (float)quadrant_x(tx0, 0, lane), pyf_t0 = (float)quadrant_y(ty0, 0, lane);          // the lane's pixel in quadrant 0 of the tile (TILE_Q)
     const float fx = (DEPTH && p.n_views > 1) ? p.fxv[view] : p.cam.fx, fy = (DEPTH && p.n_views > 1) ? p.fyv[view] : p.cam.fy;
     const float cx = (float)(W * 0.5f), cy = (float)(H * 0.5f);
     const float eps = 1.0e-8f;
@@ -247,7 +245,7 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
         __syncthreads();
         int count = min(CHUNK, n - base);
         // Colour, a plain round: the entry loop below for the colour pass alone, without the near-singular branch (riskm == 0) and with alpha = exp2(-E) unclamped --
-        // min(0.99, .) is the identity there (common.h), so the same bits.  Every other line is the loop below's, operation by operation: a change there belongs here too
+        // min(0.99, .) is the identity there (common.h), so the same bits.  E is quadrant_E's in both loops (blend.h); the blend itself is the loop below's, operation by operation
         // (tests/test_gpu_plain_chunks.py holds the two to the same bits).  The two loops run in SEQUENCE, one of them with no trips, not as `if (plain) ... else ...`:
         // the alternative came out of hipcc as a flag-and-join shape in which both loops' copies of the blend state (T, C, last contributor: 20 registers) are live at once --
         // 68 VGPRs and 40-60 moves per round; in sequence each loop works on the state in place (48 VGPRs as before, no scratch) for one scalar compare per loop and round.
@@ -262,21 +260,8 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
 #endif
                 uint32_t e1v = (uint32_t)(base + j + 1);
                 asm volatile("" : "+v"(e1v));
-                const float dx0 = q0.x - (TILE_Q >= 0 ? pxf_t0 : pxf[0]), dy0 = q0.y - (TILE_Q >= 0 ? pyf_t0 : pyf[0]);
-                const float lx0 = q1.x * dx0 + q1.y * dy0, ly0 = q1.y * dx0 + q1.z * dy0;
-                const float P0 = fmaf(dx0, lx0, fmaf(dy0, ly0, q0.z));
                 float p2q[PPL];
-                p2q[0] = P0;
-                if constexpr (PPL >= 2) p2q[1] = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
-                if constexpr (PPL == 4) {
-                    p2q[2] = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
-                    p2q[3] = fmaf(128.0f, q1.y, p2q[2] + (p2q[1] - P0));
-                }
-                if constexpr (TILE_Q >= 1 && PPL == 1) {
-                    const float E1 = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
-                    const float E2 = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
-                    p2q[0] = TILE_Q == 1 ? E1 : (TILE_Q == 2 ? E2 : fmaf(128.0f, q1.y, E2 + (E1 - P0)));
-                }
+                quadrant_E<PPL, TILE_Q>(p2q, q0, q1, TILE_Q >= 0 ? pxf_t0 : pxf[0], TILE_Q >= 0 ? pyf_t0 : pyf[0]);
 #pragma unroll
                 for (int q = 0; q < PPL; q++) {
                     if (live[q] == 0ull) continue;
@@ -324,24 +309,8 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
             // the scalar -> vector move inside every quadrant's branch)
             uint32_t e1v = (uint32_t)(e + 1);
             asm volatile("" : "+v"(e1v));
-            // p2 = d^T conic d = -2 * power.  With 4 pixels per lane the quadratic form is evaluated once for the
-            // lane's pixel in quadrant 0 and shifted to the other three (pixel offsets (8,0), (0,8), (8,8)):
-            // p2(d - s) = p2(d) - 2 s^T conic d + s^T conic s -- 14 VALU ops for four pixels instead of 32.
-            const float dx0 = q0.x - (TILE_Q >= 0 ? pxf_t0 : pxf[0]), dy0 = q0.y - (TILE_Q >= 0 ? pyf_t0 : pyf[0]);
-            const float lx0 = q1.x * dx0 + q1.y * dy0, ly0 = q1.y * dx0 + q1.z * dy0;
-            const float P0 = fmaf(dx0, lx0, fmaf(dy0, ly0, q0.z));          // E = -log2(o G) of the lane's quadrant-0 pixel (common.h)
-            float p2q[PPL];
-            p2q[0] = P0;
-            if (PPL >= 2) p2q[1] = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
-            if (PPL == 4) {
-                p2q[2] = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
-                p2q[3] = fmaf(128.0f, q1.y, p2q[2] + (p2q[1] - P0));          // E(d - (8,8)) = E2 + (E1 - E0) + 128 b: three instructions instead of four
-            }
-            if constexpr (TILE_Q >= 1 && PPL == 1) {          // the tile wave's expressions for this quadrant, operation by operation
-                const float E1 = fmaf(-16.0f, lx0, P0 + 64.0f * q1.x);
-                const float E2 = fmaf(-16.0f, ly0, P0 + 64.0f * q1.z);
-                p2q[0] = TILE_Q == 1 ? E1 : (TILE_Q == 2 ? E2 : fmaf(128.0f, q1.y, E2 + (E1 - P0)));
-            }
+            float p2q[PPL];          // E = -log2(o G) of the lane's pixels (blend.h)
+            quadrant_E<PPL, TILE_Q>(p2q, q0, q1, TILE_Q >= 0 ? pxf_t0 : pxf[0], TILE_Q >= 0 ? pyf_t0 : pyf[0]);
             if ((riskm >> (GEO ? 4 * j + 1 : j)) & 1ull) {          // wave-uniform and rare: the record as preprocess wrote it, the reference's expression per pixel
                 const uint32_t gid = p.point_list[r0 + e];
                 const float4 g0 = p.rec[(size_t)gid * 4], g1 = p.rec[(size_t)gid * 4 + 1];
@@ -460,8 +429,7 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
         uint32_t m = 0;
 #pragma unroll
         for (int q = 0; q < PPL; q++) m = max(m, inside[q] ? lastc[q] : 0u);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, WAVE));
+        m = wave_max_u32(m);
         if (p.hybrid) {
             // hybrid colour kernel: four words per tile whichever shape walked it (a tile wave leaves the other three at zero)
             if (IPT == 1) { if (lane < 4) p.walked[(size_t)tile * 4 + lane] = lane == 0 ? m : 0u; }
@@ -482,8 +450,7 @@ __device__ __forceinline__ void render_fwd_body(const FwdParams& p, const int ti
 #pragma clang fp contract(off)
 #pragma unroll 1
         for (int q = 0; q < PPL; q++) {
-            const int qq = quad0 + q;
-            const int pxq = tx0 + (qq & 1) * 8 + (lane & 7), pyq = ty0 + (qq >> 1) * 8 + (lane >> 3);
+            const int pxq = quadrant_x(tx0, quad0 + q, lane), pyq = quadrant_y(ty0, quad0 + q, lane);
             if (!(pxq < W && pyq < H)) continue;
             const size_t pix = vbase + (size_t)pyq * W + pxq;
             const float pxfq = (float)pxq, pyfq = (float)pyq;
@@ -623,7 +590,7 @@ __global__ void __launch_bounds__(64, (MODE == 2 && PPL == 4 && MAXL == 4) ? 5 :
         // launched over the slots of a tile order (ibgs_forward_args::tile_order_hint), IPT consecutive workgroups per slot: the hinted tile when the
         // hint was found valid, else tile = slot
         uint32_t t = blockIdx.x / IPT;
-        if (p.meta[11] == 1u) { t = p.order[t]; if (t != 0xFFFFFFFFu) t &= ~ORDER_SPLIT_BIT; }
+        if (p.meta[11] == 1u) t = ordered_tile(p.order, t, tile) ? (uint32_t)tile : 0xFFFFFFFFu;
         if (t >= (uint32_t)p.ntiles) return;          // (0xFFFFFFFF: an empty slot)
         tile = (int)t; sub = (int)(blockIdx.x % IPT);
     } else if (!tile_map_item(p.tmap, blockIdx.x, p.cam.gx, p.ntiles / p.cam.gx, IPT, tile, sub)) return;
