@@ -206,6 +206,12 @@ CAGG_MAX_SIDE = 65536
 CAGG_FEATURES = 32
 CAGG_MEAN, CAGG_MAX = 0, 1
 
+# every symbol include/ibgs_hourglass.h declares (tests/test_hourglass_host.py compares the two)
+HG_EXPORTS = ["ibgs_hg_required_scratch", "ibgs_hg_forward"]
+HG_CHANNELS = 38
+HG_MIN_SIDE = 4
+HG_MAX_SIDE = 8192
+
 
 _lib = None
 
@@ -420,6 +426,13 @@ def load():
     lib.ibgs_cagg_forward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 10
     lib.ibgs_cagg_backward.restype = i32
     lib.ibgs_cagg_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 16 + [sz]
+    for name in HG_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_hg_required_scratch.restype = sz
+    lib.ibgs_hg_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_hg_forward.restype = i32
+    lib.ibgs_hg_forward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, sz]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

@@ -1,6 +1,7 @@
 """The per-view front end of the reference's colour aggregation network (color_aggregation_network.py:102-133, 156-198, 229-233; train.py:347-357,
 render.py:137-147): from the rasterizer's planes to the (1, 38, H, W) tensor `ColorFusionResidualNet.forward` hands to its `conv_decoder`, as one kernel
-forward and one backward (C ABI include/ibgs_color_agg.h, csrc/coloragg.hip).  The hourglass CNN behind it stays with torch.
+forward and one backward (C ABI include/ibgs_color_agg.h, csrc/coloragg.hip).  In training the hourglass CNN behind it stays with torch; at test time
+ibgs_amd/hourglass.py runs it.
 
   levels  = min(slots of warped_image whose colours are not all zero, nb_visible_src_frames, S), formed and read ON THE DEVICE: nothing waits for the host
   slot k  : v = (cam_feat[4k] + .. + cam_feat[4k + 3] > 0);  x = [(warped[3k + c] - render[c]) v, cam_feat[4k .. 4k + 3]];  h2 = relu(W2 relu(W1 x + b1) + b2)

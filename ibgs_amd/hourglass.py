@@ -1,0 +1,193 @@
+"""The hourglass CNN of the reference's colour aggregation network for test-time rendering (color_aggregation_network.py:6-68, 229-250; render.py:137-147):
+from the (1, 38, H, W) tensor of `coloragg.fuse_color_inputs` to `residual` and `image_pred`, as seven launches of one matrix-core kernel (C ABI
+include/ibgs_hourglass.h, csrc/hourglass.hip).  With `ColorAggregationNet` and `fuse_color` the whole test-time tail -- rasterizer outputs in, image_pred
+out -- runs on this library's kernels, and a `ColorFusionResidualNet` checkpoint loads unchanged.
+
+  e1 = relu(conv3(x; enc1 38 -> 38));  e2 = relu(conv3(pool(e1); enc2 38 -> 19));  b = relu(conv3(pool(e2); enc3 19 -> 9))
+  u2 = relu(conv3(up(b); up2_conv 9 -> 19));  d2 = relu(conv3([u2, e2]; dec2 38 -> 19));  u1 = relu(conv3(up(d2); up1_conv 19 -> 38))
+  d1 = relu(conv3([u1, e1]; dec1 76 -> 38));  f = relu(conv1([d1, x]; fuse_input 76 -> 38));  residual = conv1(f; final 38 -> 3)
+  image_pred = burned_in_gauss * render + residual          (render = channels 35 .. 37 of x)
+
+FORWARD ONLY (inference, under torch.no_grad()), float32, hidden_dim 38.  Training keeps torch's CNN behind `coloragg.fuse_color_inputs`.
+The contract is a tolerance against a float64 restatement (tests/hourglass_ref.py).
+
+HIP only: raises when the library or a GPU tensor is missing (no torch fallback in the product path)."""
+import torch
+from torch import nn
+
+from . import _device, _lib
+from .coloragg import PerViewFrontEnd, _f32
+
+C = _lib.HG_CHANNELS
+# the nine convolutions in the order of the C ABI: (name, Cout, Cin, kernel side)
+LAYERS = (("enc1", C, C, 3), ("enc2", C // 2, C, 3), ("enc3", C // 4, C // 2, 3), ("up2_conv", C // 2, C // 4, 3), ("dec2", C // 2, 2 * (C // 2), 3),
+          ("up1_conv", C, C // 2, 3), ("dec1", C, 2 * C, 3), ("fuse_input", C, 2 * C, 1), ("final", 3, C, 1))
+# the reference's names of the eighteen parameters inside ConvDecoderAE -> this module's
+REFERENCE_KEYS = {}
+for _name, _, _, _ in LAYERS:
+    _theirs = _name if _name == "final" else _name + ".0"
+    REFERENCE_KEYS[_theirs + ".weight"] = _name + "_w"
+    REFERENCE_KEYS[_theirs + ".bias"] = _name + "_b"
+# the intermediates of the arena (include/ibgs_hourglass.h), in its order: (name, channels, resolution level)
+STAGES = (("e1", C, 0), ("e2", C // 2, 1), ("b", C // 4, 2), ("u2", C // 2, 1), ("d2", C // 2, 1), ("u1", C, 0))
+
+
+def _stage_views(arena, h, w):
+    sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
+    out, at = {}, 0
+    for name, ch, level in STAGES:
+        hh, ww = sides[level]
+        at = (at + 127) // 128 * 128
+        n = ch * hh * ww * 4
+        out[name] = arena[at:at + n].view(torch.float32).view(ch, hh, ww)
+        at += n
+    return out
+
+
+def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False):
+    """cnn_input: (1, 38, H, W) or (38, H, W), any strides, 4 <= H, W <= 8192; params: a `HourglassCNN`.  -> residual (3, H, W) float32.
+
+    With `render_scale=float` (the reference's burned_in_gauss) -> (residual, image_pred) with image_pred = render_scale * cnn_input[35:38] + residual,
+    formed in the last kernel: bit for bit what torch gives for that expression on the returned residual.
+    With `return_stages` a dict of the intermediates e1, e2, b, u2, d2, u1 is returned last: VIEWS into the call's arena, (channels, h, w) each, valid until
+    the next call on that device (a caller who keeps one longer clones it).
+
+    Forward only: with grad mode enabled and an input or parameter that requires grad this raises -- call it under torch.no_grad(); training keeps
+    torch's CNN behind coloragg.fuse_color_inputs.  Nothing waits for the host."""
+    name = "hourglass_forward"
+    if not isinstance(params, HourglassCNN):
+        raise TypeError("%s: params must be a HourglassCNN, got %s" % (name, type(params).__name__))
+    if not torch.is_tensor(cnn_input):
+        raise TypeError("%s: cnn_input must be a tensor" % name)
+    x = cnn_input
+    if x.dim() == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() != 3:
+        raise ValueError("%s: cnn_input must be (1, %d, H, W) or (%d, H, W), got %s" % (name, C, C, tuple(cnn_input.shape)))
+    if x.shape[0] != C:
+        raise ValueError("%s: cnn_input has %d channels, which implies hidden_dim = %d; the kernels have hidden_dim = %d only (32 per-view features + ray + colour)"
+                         % (name, x.shape[0], x.shape[0], C))
+    h, w = int(x.shape[1]), int(x.shape[2])
+    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d: the bottleneck is a quarter of the frame)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    tensors = []
+    for layer, cout, cin, k in LAYERS:
+        wt, bt = getattr(params, layer + "_w"), getattr(params, layer + "_b")
+        if tuple(wt.shape) != (cout, cin, k, k):
+            raise ValueError("%s: %s_w must be %s, got %s" % (name, layer, (cout, cin, k, k), tuple(wt.shape)))
+        if tuple(bt.shape) != (cout,):
+            raise ValueError("%s: %s_b must be %s, got %s" % (name, layer, (cout,), tuple(bt.shape)))
+        tensors += [(layer + "_w", wt), (layer + "_b", bt)]
+    if render_scale is not None:
+        render_scale = float(render_scale)
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for _, t in tensors)):
+        raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
+                           "torch's CNN behind coloragg.fuse_color_inputs" % name)
+    _device.refuse_cpu("hourglass", "%s's cnn_input" % name, x)
+    for what, t in tensors:
+        _device.refuse_cpu("hourglass", "%s's %s" % (name, what), t)
+    dev = x.device
+    for what, t in tensors:
+        if t.device != dev:
+            raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, dev, what, t.device))
+    x = _f32(x)
+    flat = [_f32(t) for _, t in tensors]
+    with torch.cuda.device(dev):
+        residual = torch.empty((3, h, w), dtype=torch.float32, device=dev)
+        image_pred = torch.empty((3, h, w), dtype=torch.float32, device=dev) if render_scale is not None else None
+    arena = _device.scratch(dev, _lib.load().ibgs_hg_required_scratch(h, w))
+    _device.call(dev, "ibgs_hg_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if render_scale is None else render_scale, residual.data_ptr(),
+                 None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
+    out = (residual,) if image_pred is None else (residual, image_pred)
+    if return_stages:
+        out += (_stage_views(arena, h, w),)
+    return out[0] if len(out) == 1 else out
+
+
+class HourglassCNN(nn.Module):
+    """The eighteen parameters of the reference's `ConvDecoderAE(38)` (nn.Conv2d's default initialisation), named <layer>_w / <layer>_b for the layers enc1,
+    enc2, enc3, up2_conv, dec2, up1_conv, dec1, fuse_input, final.  `load_state_dict` takes this module's keys or the reference's (enc1.0.weight,
+    up2_conv.0.bias, fuse_input.0.weight, final.weight, ...), so the `conv_decoder.` part of a ColorFusionResidualNet checkpoint loads unchanged."""
+
+    def __init__(self):
+        super().__init__()
+        for layer, cout, cin, k in LAYERS:
+            conv = nn.Conv2d(cin, cout, kernel_size=k)
+            setattr(self, layer + "_w", nn.Parameter(conv.weight.detach().clone()))
+            setattr(self, layer + "_b", nn.Parameter(conv.bias.detach().clone()))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for theirs, mine in REFERENCE_KEYS.items():
+            if prefix + theirs in state_dict:
+                if prefix + mine in state_dict:
+                    raise ValueError("HourglassCNN.load_state_dict: both %r and %r are given" % (prefix + theirs, prefix + mine))
+                state_dict[prefix + mine] = state_dict.pop(prefix + theirs)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, cnn_input, render_scale=None, return_stages=False):
+        """`hourglass_forward` with this module's parameters."""
+        return hourglass_forward(cnn_input, self, render_scale, return_stages)
+
+
+class ColorAggregationNet(nn.Module):
+    """The reference's `ColorFusionResidualNet` for test-time rendering: `front_end` (its per_view_mlp) and `cnn` (its conv_decoder).  `load_state_dict` takes
+    a whole checkpoint of the reference unchanged (per_view_mlp.* and conv_decoder.*, as its training script saves `color_aggregation_network.state_dict()`),
+    or this module's own keys (front_end.*, cnn.*)."""
+
+    def __init__(self, mode="mean"):
+        super().__init__()
+        self.front_end = PerViewFrontEnd(mode)
+        self.cnn = HourglassCNN()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for key in list(state_dict):
+            for theirs, mine in (("per_view_mlp.", "front_end.per_view_mlp."), ("conv_decoder.", "cnn.")):
+                if key.startswith(prefix + theirs):
+                    state_dict[prefix + mine + key[len(prefix + theirs):]] = state_dict.pop(key)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False):
+        """`fuse_color` with this network."""
+        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level)
+
+
+def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False):
+    """The reference's test-time fuse_color (no exposure correction, residual_resolution_scale 1) on the `render()` dictionary (keys "render",
+    "warped_image", "cam_feat", "camera_ray", "min_depth_diff") with a `ColorAggregationNet`: the per-view front end, then the hourglass.  -> a dictionary
+    with the reference's keys:
+      image_pred, residual    (3, H, W)
+      valid_warp_mask         (min_depth_diff < 0.999) as float
+      burned_in_gauss         the float that was passed
+      nb_valid_warp_level     a 0-d int32 DEVICE tensor (the reference's Python int is `int(...)` of it: one synchronisation, the caller's choice)
+      warped_image_list       the first min(nb_visible_src_frames, S) slots as an (H, W, k, 3) view of warped_image; NOT trimmed to nb_valid_warp_level, which
+                              the host does not know -- slots from that level on are all zero or unused
+    The reference returns None when no slot level carries a colour.  With `none_if_no_level` the count is read back (ONE synchronisation, the only one) and
+    None is returned then; without it nothing waits, the aggregated features are exactly zero and image_pred is the network's output on them.
+    Forward only: call it under torch.no_grad()."""
+    name = "fuse_color"
+    if not isinstance(net, ColorAggregationNet):
+        raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
+    for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
+        if key not in render_pkg:
+            raise KeyError("%s: render_pkg lacks %r" % (name, key))
+    render = render_pkg["render"]
+    if not torch.is_tensor(render) or render.dim() != 3 or render.shape[0] != 3:
+        raise ValueError("%s: render_pkg['render'] must be a (3, H, W) tensor" % name)
+    h, w = int(render.shape[1]), int(render.shape[2])
+    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    if torch.is_grad_enabled() and (any(torch.is_tensor(v) and v.requires_grad for v in render_pkg.values()) or any(p.requires_grad for p in net.parameters())):
+        raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
+                           "torch's CNN behind coloragg.fuse_color_inputs" % name)
+    camera_ray = render_pkg["camera_ray"]
+    if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
+        camera_ray = camera_ray.view(3, h, w)
+    warped = render_pkg["warped_image"]
+    cnn_input, levels = net.front_end(render, warped, render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
+    if none_if_no_level and int(levels.item()) == 0:
+        return None
+    residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss))
+    slots = warped.reshape(-1, 3, h, w)
+    slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
+    return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),
+            "burned_in_gauss": float(burned_in_gauss), "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1)}

@@ -1,0 +1,194 @@
+"""The hourglass CNN on the matrix cores (ibgs_amd/hourglass.py `hourglass_forward`; csrc/hourglass.hip) against its torch composition -- nine
+F.conv2d, two max_pool2d, two nearest interpolate, three cat, ReLUs and the image_pred expression, written from the definition --
+in ONE process on one MI355X, at (38, 1080, 1920) and (38, 720, 1280), under no_grad.  Output: profiles/hourglass.txt.
+
+    python tools/bench_hourglass.py [--out profiles/hourglass.txt] [--iters 5] [--repeats 9] [--warmup 12]
+
+Per size, alternating:
+  hip                the seven launches
+  torch float32      the composition in float32 (MIOpen's convolutions): THE YARDSTICK
+  torch autocast     the same under torch.autocast(float16), for the record: another precision, not a competitor on equal terms
+and then the whole test-time tail from the rasterizer's planes: coloragg.fuse_color_inputs + hourglass (`hourglass.fuse_color`) against the fused front end
+followed by the torch float32 CNN and the image_pred expression.
+Timing: hipEvents around `iters` back-to-back calls on the current stream, after `warmup` calls of each (MIOpen chooses its kernels on the first uses of
+a shape); the median over `repeats` such windows, and their minimum and maximum.  Floors quoted beside the hip forward: 52 218 multiply-adds per pixel at the
+157.3 TFLOP/s f32 matrix peak, and the minimum traffic of the seven-launch split (x, e1 and u1 written once and read once or twice, the half- and
+quarter-resolution stages, the outputs) at 8 TB/s.  Also printed: the padding efficiency of the 16-wide matrix instruction per layer and hipcc's register
+and spill report per instantiation of the kernel.  A measurement needs the GPU: without one this script fails."""
+import argparse
+import os
+import re
+import statistics
+import subprocess
+import sys
+import tempfile
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ibgs_amd import _build, coloragg, hourglass  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+FP32_FLOPS = 157.3e12
+# (layer, Cout, Cin, taps, resolution level): the multiply-adds per full-resolution pixel
+MACS = sum(cout * cin * k * k / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS, (0, 1, 2, 1, 1, 0, 0, 0, 0)))
+
+
+def composed(x, p, burned):
+    """x: (1, 38, H, W); p: the HourglassCNN.  -> (residual (3, H, W), image_pred)"""
+    conv = lambda t, name, pad: F.conv2d(t, getattr(p, name + "_w"), getattr(p, name + "_b"), padding=pad)
+    e1 = F.relu(conv(x, "enc1", 1))
+    e2 = F.relu(conv(F.max_pool2d(e1, 2), "enc2", 1))
+    b = F.relu(conv(F.max_pool2d(e2, 2), "enc3", 1))
+    u2 = F.relu(conv(F.interpolate(b, size=e2.shape[-2:], mode="nearest"), "up2_conv", 1))
+    d2 = F.relu(conv(torch.cat([u2, e2], 1), "dec2", 1))
+    u1 = F.relu(conv(F.interpolate(d2, size=e1.shape[-2:], mode="nearest"), "up1_conv", 1))
+    d1 = F.relu(conv(torch.cat([u1, e1], 1), "dec1", 1))
+    f = F.relu(conv(torch.cat([d1, x], 1), "fuse_input", 0))
+    residual = conv(f, "final", 0)[0]
+    return residual, burned * x[0, 35:38] + residual
+
+
+def window_ms(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def compare(fns, iters, repeats, warmup):
+    """fns: {name: callable}.  Warm-up, then `repeats` windows of each, alternating.  -> {name: (median, min, max) ms per call}"""
+    for k, fn in fns.items():
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        print("  (warmed up: %s)" % k, flush=True)
+    t = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            t[k].append(window_ms(fn, iters))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in t.items()}
+
+
+def min_bytes(h, w):
+    p1, p2, p4 = h * w, (h // 2) * (w // 2), (h // 4) * (w // 4)
+    # x: read by enc1 and by the last launch; e1: written, read by enc2 (pooled) and the last launch; e2: written, read by enc3 and dec2; b, u2, d2: written and read
+    # once; u1: written and read; the six output planes and the three colour planes read again
+    return 4 * (2 * 38 * p1 + 3 * 38 * p1 + 3 * 19 * p2 + 2 * 9 * p4 + 2 * 19 * p2 + 2 * 19 * p2 + 2 * 38 * p1 + 9 * p1)
+
+
+def resource_report(say):
+    """hipcc's own report for hourglass.hip with the build's flags (compiled to a scratch file)."""
+    src = os.path.join(_build.CSRC, "hourglass.hip")
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([_build._hipcc()] + _build.compile_flags("hourglass") + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hg.o")],
+                           capture_output=True, text=True)
+    if r.returncode != 0:
+        say("hipcc's resource report could not be produced (exit %d)" % r.returncode)
+        return
+    rows, cur = [], None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+(?:Function Name: (\S+)|\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+))", line)
+        if not m:
+            continue
+        if m.group(1):
+            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", m.group(1))
+            cur = {"name": "hg_conv3_kernel<%s, %s, %s, %s, %s>" % (t.group(1), t.group(2), t.group(3), ("plain", "pool", "up")[int(t.group(4))], "fused" if t.group(5) == "1" else "-")
+                   if t else m.group(1)}
+            rows.append(cur)
+        elif cur is not None:
+            cur[m.group(2).strip()] = int(m.group(3))
+    say("hipcc's report per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):")
+    for c in rows:
+        say("  %-48s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
+            % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hourglass.txt"))
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=12)
+    ap.add_argument("--sizes", default="1080x1920,720x1280")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_hourglass.py measures on the GPU; there is none here")
+    dev = torch.device("cuda")
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/bench_hourglass.py on one %s: the hourglass CNN on the matrix cores (seven launches) against its torch composition (9 conv2d, 2 max_pool2d, 2 interpolate, 3 cat)," % torch.cuda.get_device_name(0))
+    say("# one process, no_grad, hipEvents around %d back-to-back calls, median [min .. max] of %d windows after %d warm-up calls each, the candidates alternating" % (args.iters, args.repeats, args.warmup))
+    torch.manual_seed(0)
+    net = hourglass.ColorAggregationNet().to(dev).requires_grad_(False)
+    cnn = net.cnn
+    useful = sum(cout * cin * k * k / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS[:7], (0, 1, 2, 1, 1, 0, 0)))
+    issued = sum((cout + 15) // 16 * 16 * ((cin * k * k + 3) // 4 * 4) / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS[:7], (0, 1, 2, 1, 1, 0, 0)))
+    say("# %d multiply-adds per pixel; padding of the 16-wide instruction (Cout 38 -> 48, 19 -> 32, 9 -> 16; K to a multiple of 4): %.1f %% of the 3 x 3 layers' issued products are useful"
+        % (round(MACS), 100.0 * useful / issued) + " (the 32-wide form, 38 -> 64: %.1f %%)"
+        % (100.0 * useful / sum((cout + 31) // 32 * 32 * ((cin * k * k + 1) // 2 * 2) / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS[:7], (0, 1, 2, 1, 1, 0, 0)))))
+    verdict = {}
+    with torch.no_grad():
+        for size in args.sizes.split(","):
+            h, w = (int(v) for v in size.split("x"))
+            g = torch.Generator().manual_seed(h)
+            s = 3
+            render = torch.rand((3, h, w), generator=g).to(dev)
+            warped = (render[None] + 0.1 * torch.randn((s, 3, h, w), generator=g).to(dev)).clamp(0, 1).reshape(3 * s, h, w).contiguous()
+            mask = (torch.rand((s, 1, h, w), generator=g) < 0.6).to(dev)
+            feat = ((torch.rand((s, 4, h, w), generator=g).to(dev) + 0.1) * mask).reshape(4 * s, h, w).contiguous()
+            ray = F.normalize(torch.randn((3, h, w), generator=g), dim=0).to(dev)
+            pkg = {"render": render, "warped_image": warped, "cam_feat": feat, "camera_ray": ray, "min_depth_diff": torch.rand((1, h, w), generator=g).to(dev)}
+            x, _ = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
+            say()
+            say("== (38, %d, %d)" % (h, w))
+            r_hip, ip_hip = hourglass.hourglass_forward(x, cnn, render_scale=1.0)
+            r_t, ip_t = composed(x, cnn, 1.0)
+            say("same results: max |d residual| %.2e of max |residual| %.2e; image_pred is torch's expression on the hip residual bit for bit: %s"
+                % (float((r_hip - r_t).abs().max()), float(r_t.abs().max()), bool(torch.equal(ip_hip, 1.0 * x[0, 35:38] + r_hip))))
+            del r_hip, ip_hip, r_t, ip_t
+
+            def autocast():
+                with torch.autocast("cuda", dtype=torch.float16):
+                    return composed(x, cnn, 1.0)
+            r = compare({"hip": lambda: hourglass.hourglass_forward(x, cnn, render_scale=1.0), "torch float32": lambda: composed(x, cnn, 1.0), "torch autocast": autocast},
+                        args.iters, args.repeats, args.warmup)
+            flop_ms = 2 * MACS * h * w / FP32_FLOPS * 1e3
+            byte_ms = min_bytes(h, w) / HBM_BYTES_PER_S * 1e3
+            for k in ("hip", "torch float32", "torch autocast"):
+                say("%-16s %8.3f ms [%7.3f .. %7.3f]" % (k, r[k][0], r[k][1], r[k][2]))
+            faster = r["hip"][0] < r["torch float32"][0]
+            verdict[size] = faster
+            say("torch float32 / hip %5.2f x   hip faster than torch float32: %s   (torch autocast / hip %5.2f x)" % (r["torch float32"][0] / r["hip"][0], faster, r["torch autocast"][0] / r["hip"][0]))
+            say("floors of the hip forward: arithmetic (%d fma per pixel at 157.3 TFLOP/s) %.3f ms = %.0f %% of its time reached; bytes (%.2f GB at 8 TB/s) %.3f ms = %.0f %%; arena %.2f GB"
+                % (round(MACS), flop_ms, 100.0 * flop_ms / r["hip"][0], min_bytes(h, w) / 1e9, byte_ms, 100.0 * byte_ms / r["hip"][0], hourglass._lib.load().ibgs_hg_required_scratch(h, w) / 1e9))
+
+            def tail_torch():
+                xi, m = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
+                return composed(xi, cnn, 1.0)
+            r = compare({"fuse_color": lambda: hourglass.fuse_color(pkg, net, 3), "front end + torch CNN": tail_torch}, args.iters, args.repeats, 3)
+            say("the test-time tail from the rasterizer's planes: fuse_color (front end + hip hourglass) %8.3f ms [%7.3f .. %7.3f]   front end + torch float32 CNN %8.3f ms [%7.3f .. %7.3f]   ratio %5.2f x"
+                % (r["fuse_color"] + r["front end + torch CNN"] + (r["front end + torch CNN"][0] / r["fuse_color"][0],)))
+            del x, pkg, render, warped, feat, ray, mask
+            torch.cuda.empty_cache()
+    say()
+    say("the hip hourglass faster than the torch float32 composition: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
+    say()
+    resource_report(say)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
