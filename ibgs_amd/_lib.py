@@ -212,6 +212,9 @@ HG_CHANNELS = 38
 HG_MIN_SIDE = 4
 HG_MAX_SIDE = 8192
 
+# every symbol include/ibgs_hg_train.h declares (tests/test_hourglass_train_host.py compares the two)
+HGB_EXPORTS = ["ibgs_hgb_required_scratch", "ibgs_hgb_backward"]
+
 
 _lib = None
 
@@ -433,6 +436,14 @@ def load():
     lib.ibgs_hg_required_scratch.argtypes = [i64, i64]
     lib.ibgs_hg_forward.restype = i32
     lib.ibgs_hg_forward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, sz]
+    for name in HGB_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_hgb_required_scratch.restype = sz
+    lib.ibgs_hgb_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_hgb_backward.restype = i32
+    # (stream, H, W, x, 18 parameters, burned, stages arena, grad_residual, grad_image_pred, grad_x, 18 gradients, scratch, bytes)
+    lib.ibgs_hgb_backward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, vp] + [vp] * 18 + [vp, sz]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

@@ -191,3 +191,190 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
     return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),
             "burned_in_gauss": float(burned_in_gauss), "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1)}
+
+
+# ---- training: the backward (C ABI include/ibgs_hg_train.h, csrc/hgtrain.hip) --------------------------------------------------------------------------------
+def _checked(name, cnn_input, params):
+    """The argument checks of `hourglass_forward`, for the training entry points.  -> (x (38, H, W), h, w, [(name, parameter)] in the C ABI's order)"""
+    if not isinstance(params, HourglassCNN):
+        raise TypeError("%s: params must be a HourglassCNN, got %s" % (name, type(params).__name__))
+    if not torch.is_tensor(cnn_input):
+        raise TypeError("%s: cnn_input must be a tensor" % name)
+    x = cnn_input
+    if x.dim() == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() != 3:
+        raise ValueError("%s: cnn_input must be (1, %d, H, W) or (%d, H, W), got %s" % (name, C, C, tuple(cnn_input.shape)))
+    if x.shape[0] != C:
+        raise ValueError("%s: cnn_input has %d channels, which implies hidden_dim = %d; the kernels have hidden_dim = %d only (32 per-view features + ray + colour)"
+                         % (name, x.shape[0], x.shape[0], C))
+    h, w = int(x.shape[1]), int(x.shape[2])
+    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d: the bottleneck is a quarter of the frame)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    tensors = []
+    for layer, cout, cin, k in LAYERS:
+        wt, bt = getattr(params, layer + "_w"), getattr(params, layer + "_b")
+        if tuple(wt.shape) != (cout, cin, k, k):
+            raise ValueError("%s: %s_w must be %s, got %s" % (name, layer, (cout, cin, k, k), tuple(wt.shape)))
+        if tuple(bt.shape) != (cout,):
+            raise ValueError("%s: %s_b must be %s, got %s" % (name, layer, (cout,), tuple(bt.shape)))
+        tensors += [(layer + "_w", wt), (layer + "_b", bt)]
+    _device.refuse_cpu("hourglass", "%s's cnn_input" % name, x)
+    for what, t in tensors:
+        _device.refuse_cpu("hourglass", "%s's %s" % (name, what), t)
+    for what, t in tensors:
+        if t.device != x.device:
+            raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, x.device, what, t.device))
+    return x, h, w, tensors
+
+
+def _backward_call(dev, h, w, x, flat, burned, arena, g_res, g_ip, need_x, need_params):
+    """x, flat, g_res, g_ip: float32, contiguous, on dev; arena: the owned stages arena.  -> (grad_x (38, h, w) or None, [18 gradients] or None)"""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        grad_x = torch.empty((C, h, w), dtype=torch.float32, device=dev) if need_x else None
+        grads = [torch.empty_like(t) for t in flat] if need_params else None
+    sc = _device.scratch(dev, _lib.load().ibgs_hgb_required_scratch(h, w))
+    _device.call(dev, "ibgs_hgb_backward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], float(burned), arena.data_ptr(), ptr(g_res), ptr(g_ip), ptr(grad_x),
+                 *([g.data_ptr() for g in grads] if need_params else [None] * 18), sc.data_ptr(), sc.numel())
+    return grad_x, grads
+
+
+def _upstream(name, what, g, h, w, dev):
+    if g is None:
+        return None
+    if not torch.is_tensor(g) or g.numel() != 3 * h * w or tuple(g.shape[-2:]) != (h, w):
+        raise ValueError("%s: %s must be (3, %d, %d)" % (name, what, h, w))
+    _device.refuse_cpu("hourglass", "%s's %s" % (name, what), g)
+    if g.device != dev:
+        raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, dev, what, g.device))
+    return _f32(g).view(3, h, w)
+
+
+def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image_pred=None, render_scale=1.0, need_input_grad=True, need_param_grads=True):
+    """The raw backward of the hourglass: cnn_input and params as for `hourglass_forward`; `stages` the six intermediates of the forward on them -- either the
+    arena of ibgs_hg_forward as a uint8 tensor (what `hourglass_train` keeps) or a dict of the tensors e1, e2, b, u2, d2, u1 (packed into one here);
+    grad_residual and / or grad_image_pred (3, H, W): the upstream gradients (either may be None, not both); render_scale: the burned_in_gauss image_pred was
+    formed with.  -> (grad_x (38, H, W) or None, {"enc1_w": ..., ...} or None): a group that is not needed is not computed (no weight-gradient kernel runs
+    without need_param_grads; enc1's input gradient does not without need_input_grad).  d1 and f are recomputed.  Float32; the same arguments give the same
+    bits; nothing waits for the host and no argument is written.  It refuses what `hourglass_forward` refuses."""
+    name = "hourglass_backward"
+    x, h, w, tensors = _checked(name, cnn_input, params)
+    dev = x.device
+    if grad_residual is None and grad_image_pred is None:
+        raise ValueError("%s: grad_residual and grad_image_pred are both None" % name)
+    if not (need_input_grad or need_param_grads):
+        raise ValueError("%s: neither the input gradient nor the parameter gradients are asked for" % name)
+    g_res = _upstream(name, "grad_residual", grad_residual, h, w, dev)
+    g_ip = _upstream(name, "grad_image_pred", grad_image_pred, h, w, dev)
+    need = _lib.load().ibgs_hg_required_scratch(h, w)
+    if isinstance(stages, dict):
+        sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
+        arena = _device.scratch(dev, need)
+        views = _stage_views(arena, h, w)
+        for stage, ch, level in STAGES:
+            if stage not in stages or not torch.is_tensor(stages[stage]) or tuple(stages[stage].shape[-3:]) != (ch,) + sides[level] or stages[stage].numel() != views[stage].numel():
+                raise ValueError("%s: stages[%r] must be a (%d, %d, %d) tensor" % (name, stage, ch, sides[level][0], sides[level][1]))
+            _device.refuse_cpu("hourglass", "%s's stage %s" % (name, stage), stages[stage])
+            views[stage].copy_(stages[stage].detach().reshape(views[stage].shape))
+    else:
+        if not torch.is_tensor(stages) or stages.dtype != torch.uint8 or stages.dim() != 1 or stages.numel() < need or not stages.is_contiguous():
+            raise ValueError("%s: stages must be the arena of the forward (a contiguous uint8 tensor of %d bytes) or a dict of the six stages" % (name, need))
+        _device.refuse_cpu("hourglass", "%s's stages" % name, stages)
+        if stages.device != dev:
+            raise ValueError("%s: cnn_input is on %s, stages on %s" % (name, dev, stages.device))
+        arena = stages
+    flat = [_f32(t) for _, t in tensors]
+    grad_x, grads = _backward_call(dev, h, w, _f32(x), flat, float(render_scale), arena, g_res, g_ip, bool(need_input_grad), bool(need_param_grads))
+    return grad_x, (None if grads is None else {what: g for (what, _), g in zip(tensors, grads)})
+
+
+class _HourglassTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dims, burned, *params):
+        h, w = dims
+        dev = x.device
+        x32 = _f32(x).view(C, h, w)
+        flat = [_f32(t) for t in params]
+        with torch.cuda.device(dev):
+            residual = torch.empty((3, h, w), dtype=torch.float32, device=dev)
+            image_pred = torch.empty((3, h, w), dtype=torch.float32, device=dev) if burned is not None else None
+            arena = torch.empty(_lib.load().ibgs_hg_required_scratch(h, w), dtype=torch.uint8, device=dev)          # owned: the backward reads it
+        _device.call(dev, "ibgs_hg_forward", h, w, x32.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if burned is None else burned, residual.data_ptr(),
+                     None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
+        ctx.dims, ctx.burned, ctx.x_shape, ctx.x_dtype = dims, burned, x.shape, x.dtype
+        ctx.set_materialize_grads(False)          # an output nobody used arrives as None, not as a plane of zeros
+        ctx.save_for_backward(x32, arena, *flat)
+        if image_pred is None:
+            return residual
+        return residual, image_pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_res, g_ip=None):
+        need_x, need_params = ctx.needs_input_grad[0], any(ctx.needs_input_grad[3:])
+        if not (need_x or need_params) or (g_res is None and g_ip is None):
+            return (None,) * (3 + 18)
+        x32, arena = ctx.saved_tensors[:2]
+        flat = list(ctx.saved_tensors[2:])
+        h, w = ctx.dims
+        dev = x32.device
+        g_res = None if g_res is None else _f32(g_res.to(dev))
+        g_ip = None if g_ip is None else _f32(g_ip.to(dev))
+        grad_x, grads = _backward_call(dev, h, w, x32, flat, 1.0 if ctx.burned is None else ctx.burned, arena, g_res, g_ip, need_x, need_params)
+        if grad_x is not None:
+            grad_x = grad_x.view(ctx.x_shape).to(ctx.x_dtype)
+        if grads is None:
+            grads = [None] * 18
+        else:
+            grads = [g if k else None for g, k in zip(grads, ctx.needs_input_grad[3:])]
+        return (grad_x, None, None) + tuple(grads)
+
+
+def hourglass_train(cnn_input, params, render_scale=None):
+    """`hourglass_forward` for training: differentiable in cnn_input and the eighteen parameters.  -> residual, or (residual, image_pred) with
+    `render_scale=float`; both bit for bit what `hourglass_forward` returns.  The forward runs ibgs_hg_forward on an arena this node owns (the six stages are
+    the kept activations; d1 and f are recomputed by the backward); the backward is `hourglass_backward` and computes only the groups autograd needs (a frozen
+    CNN: no weight gradient runs; a detached input: no enc1 input gradient).  Double backward raises.  Nothing waits for the host."""
+    name = "hourglass_train"
+    x, h, w, tensors = _checked(name, cnn_input, params)
+    if render_scale is not None:
+        render_scale = float(render_scale)
+    return _HourglassTrain.apply(cnn_input, (h, w), render_scale, *[t for _, t in tensors])
+
+
+def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, burn_start=None, burn_end=None, none_if_no_level=False):
+    """The reference's TRAINING fuse_color (color_aggregation_network.py:156-250; residual_resolution_scale 1, no exposure correction) with a
+    `ColorAggregationNet`, differentiable end to end: the per-view front end (`PerViewFrontEnd`, forward and backward kernels), then `hourglass_train`.
+    burned_in_gauss = (clamp((iter_count - burn_start) / (burn_end - burn_start), 0, 1) + 1) / 2, or 1.0 when one of the three is None; while it is below 1
+    the five tensors of render_pkg are detached (no gradient reaches the rasterizer; the networks' parameters still train).  -> the dictionary of
+    `fuse_color`.  Nothing waits for the host unless `none_if_no_level` (which reads the level count back and returns None when it is 0)."""
+    name = "fuse_color_train"
+    if not isinstance(net, ColorAggregationNet):
+        raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
+    for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
+        if key not in render_pkg:
+            raise KeyError("%s: render_pkg lacks %r" % (name, key))
+    render = render_pkg["render"]
+    if not torch.is_tensor(render) or render.dim() != 3 or render.shape[0] != 3:
+        raise ValueError("%s: render_pkg['render'] must be a (3, H, W) tensor" % name)
+    h, w = int(render.shape[1]), int(render.shape[2])
+    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    if iter_count is None or burn_start is None or burn_end is None:
+        burned = 1.0
+    else:
+        burned = (max(0.0, min(1.0, (iter_count - burn_start) / (burn_end - burn_start))) + 1) / 2
+    warped, cam_feat, camera_ray, min_depth_diff = render_pkg["warped_image"], render_pkg["cam_feat"], render_pkg["camera_ray"], render_pkg["min_depth_diff"]
+    if burned < 1.0:          # the gradients to the Gaussians are blocked while the residual is not fully used
+        render, warped, cam_feat, camera_ray, min_depth_diff = (t.detach() for t in (render, warped, cam_feat, camera_ray, min_depth_diff))
+    if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
+        camera_ray = camera_ray.view(3, h, w)
+    cnn_input, levels = net.front_end(render, warped, cam_feat, camera_ray, nb_visible_src_frames)
+    if none_if_no_level and int(levels.item()) == 0:
+        return None
+    residual, image_pred = hourglass_train(cnn_input, net.cnn, render_scale=burned)
+    slots = warped.reshape(-1, 3, h, w)
+    slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
+    return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (min_depth_diff < 0.999).float(), "burned_in_gauss": burned,
+            "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1)}

@@ -14,7 +14,14 @@ Timing: hipEvents around `iters` back-to-back calls on the current stream, after
 a shape); the median over `repeats` such windows, and their minimum and maximum.  Floors quoted beside the hip forward: 52 218 multiply-adds per pixel at the
 157.3 TFLOP/s f32 matrix peak, and the minimum traffic of the seven-launch split (x, e1 and u1 written once and read once or twice, the half- and
 quarter-resolution stages, the outputs) at 8 TB/s.  Also printed: the padding efficiency of the 16-wide matrix instruction per layer and hipcc's register
-and spill report per instantiation of the kernel.  A measurement needs the GPU: without one this script fails."""
+and spill report per instantiation of the kernel.  A measurement needs the GPU: without one this script fails.
+
+    python tools/bench_hourglass.py --train [--out profiles/hourglass.txt] ...
+
+measures TRAINING by the same method, grad mode on: `hourglass_train` + backward (csrc/hgtrain.hip) against the torch float32 composition + autograd
+(MIOpen) in the same process, with all nineteen gradients, with the parameter gradients only (a detached input) and with the input gradient only (a frozen
+CNN); then the whole training tail, `fuse_color_train` + backward against front end + torch CNN + backward.  Its report REPLACES the part of --out from the
+line "# --train" on and leaves the forward's report above it as it is."""
 import argparse
 import os
 import re
@@ -110,6 +117,140 @@ def resource_report(say):
             % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
 
 
+TRAIN_MARK = "# --train"
+# the backward's products per pixel: two per forward product of the 3 x 3 layers and of the 1 x 1 head (input and weight gradient), the recomputed dec1 and
+# fuse_input, less enc1's input gradient when the input is detached
+BWD_MACS = 2 * MACS + (38 * 76 * 9 + 38 * 76)
+
+
+def train_resource_report(say):
+    src = os.path.join(_build.CSRC, "hgtrain.hip")
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([_build._hipcc()] + _build.compile_flags("hgtrain") + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hgb.o")],
+                           capture_output=True, text=True)
+    if r.returncode != 0:
+        say("hipcc's resource report could not be produced (exit %d)" % r.returncode)
+        return
+    rows, cur = [], None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+(?:Function Name: (\S+)|\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+))", line)
+        if not m:
+            continue
+        if m.group(1):
+            name = m.group(1)
+            k = re.search(r"(hgb_[a-z_]+)", name)
+            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EL[ib]([0-9]+)E", name)
+            cur = {"name": (k.group(1) if k else name) + ("<%s>" % ", ".join(t.groups()) if t else "")}
+            rows.append(cur)
+        elif cur is not None:
+            cur[m.group(2).strip()] = int(m.group(3))
+    say("hipcc's report per instantiation of hgtrain.hip (hgb_conv_kernel<channels of A, of B, Cout, taps, transposed>; hgb_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
+    for c in rows:
+        say("  %-44s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
+            % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
+
+
+def main_train(args):
+    dev = torch.device("cuda")
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(TRAIN_MARK + ": tools/bench_hourglass.py --train on one %s: forward + backward of the hourglass (hourglass_train; csrc/hgtrain.hip) against the torch float32 composition + autograd (MIOpen)," % torch.cuda.get_device_name(0))
+    say("# one process, grad mode on, hipEvents around %d back-to-back calls, median [min .. max] of %d windows after %d warm-up calls each, the candidates alternating" % (args.iters, args.repeats, args.warmup))
+    say("# arithmetic: %d multiply-adds per pixel forward, %d backward (two per forward product, and the recomputed dec1 and fuse_input)" % (round(MACS), round(BWD_MACS)))
+    torch.manual_seed(0)
+    net = hourglass.ColorAggregationNet().to(dev)
+    cnn = net.cnn
+    params = list(cnn.parameters())
+    verdict = {}
+    for size in args.sizes.split(","):
+        h, w = (int(v) for v in size.split("x"))
+        g = torch.Generator().manual_seed(h)
+        s = 3
+        render = torch.rand((3, h, w), generator=g).to(dev)
+        warped = (render[None] + 0.1 * torch.randn((s, 3, h, w), generator=g).to(dev)).clamp(0, 1).reshape(3 * s, h, w).contiguous()
+        mask = (torch.rand((s, 1, h, w), generator=g) < 0.6).to(dev)
+        feat = ((torch.rand((s, 4, h, w), generator=g).to(dev) + 0.1) * mask).reshape(4 * s, h, w).contiguous()
+        ray = F.normalize(torch.randn((3, h, w), generator=g), dim=0).to(dev)
+        pkg = {"render": render.requires_grad_(True), "warped_image": warped.requires_grad_(True), "cam_feat": feat, "camera_ray": ray,
+               "min_depth_diff": torch.rand((1, h, w), generator=g).to(dev)}
+        with torch.no_grad():
+            x0, _ = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
+        up = torch.randn((3, h, w), generator=g).to(dev)
+        say()
+        say("== (38, %d, %d)" % (h, w))
+
+        def step(forward, x_grad, p_grad):
+            def run():
+                x = x0.detach().requires_grad_(x_grad)
+                for q in params:
+                    q.requires_grad_(p_grad)
+                    q.grad = None
+                _, ip = forward(x)
+                (ip * up).sum().backward()
+                return x.grad, [q.grad for q in params]
+            return run
+        hip = lambda x: hourglass.hourglass_train(x, cnn, render_scale=1.0)
+        tor = lambda x: composed(x, cnn, 1.0)
+        gx_h, gp_h = step(hip, True, True)()
+        gx_t, gp_t = step(tor, True, True)()
+        say("same gradients: max |d grad_x| %.2e of max %.2e; worst parameter gradient %.2e of its max"
+            % (float((gx_h - gx_t).abs().max()), float(gx_t.abs().max()), max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(gp_h, gp_t))))
+        del gx_h, gp_h, gx_t, gp_t
+        r = compare({"hip all": step(hip, True, True), "torch all": step(tor, True, True), "hip params only": step(hip, False, True), "torch params only": step(tor, False, True),
+                     "hip input only": step(hip, True, False), "torch input only": step(tor, True, False)}, args.iters, args.repeats, args.warmup)
+        for k in r:
+            say("%-20s %8.3f ms [%7.3f .. %7.3f]" % (k, r[k][0], r[k][1], r[k][2]))
+        for what in ("all", "params only", "input only"):
+            faster = r["hip " + what][0] < r["torch " + what][0]
+            verdict["%s %s" % (size, what)] = faster
+            say("forward + backward, %-11s torch float32 / hip %5.2f x   hip faster: %s" % (what + ":", r["torch " + what][0] / r["hip " + what][0], faster))
+        lib = hourglass._lib.load()
+        floor_ms = 2 * (MACS + BWD_MACS) * h * w / FP32_FLOPS * 1e3
+        say("arithmetic floor, forward + backward (%d fma per pixel at 157.3 TFLOP/s) %.3f ms = %.0f %% of the hip time reached; kept activations (the forward's arena) %.2f GB, "
+            "the backward's arena %.2f GB" % (round(MACS + BWD_MACS), floor_ms, 100.0 * floor_ms / r["hip all"][0], lib.ibgs_hg_required_scratch(h, w) / 1e9,
+                                               lib.ibgs_hgb_required_scratch(h, w) / 1e9))
+
+        def tail(cnn_forward):
+            def run():
+                for q in net.parameters():
+                    q.requires_grad_(True)
+                    q.grad = None
+                render.grad = warped.grad = None
+                if cnn_forward is None:
+                    ip = hourglass.fuse_color_train(pkg, net, 3)["image_pred"]
+                else:
+                    xi, _ = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
+                    ip = cnn_forward(xi)[1]
+                (ip * up).sum().backward()
+            return run
+        r = compare({"fuse_color_train": tail(None), "front end + torch CNN": tail(tor)}, args.iters, args.repeats, 3)
+        say("the training tail from the rasterizer's planes, forward + backward: fuse_color_train %8.3f ms [%7.3f .. %7.3f]   front end + torch float32 CNN %8.3f ms [%7.3f .. %7.3f]   ratio %5.2f x"
+            % (r["fuse_color_train"] + r["front end + torch CNN"] + (r["front end + torch CNN"][0] / r["fuse_color_train"][0],)))
+        del x0, pkg, render, warped, feat, ray, mask, up
+        for q in net.parameters():
+            q.grad = None
+        torch.cuda.empty_cache()
+    say()
+    say("hourglass_train + backward faster than the torch float32 composition + autograd: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
+    say()
+    train_resource_report(say)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    kept = []
+    if os.path.exists(args.out):
+        for line in open(args.out).read().split("\n"):
+            if line.startswith(TRAIN_MARK):
+                break
+            kept.append(line)
+        while kept and not kept[-1].strip():
+            kept.pop()
+    with open(args.out, "w") as f:
+        f.write("\n".join(kept + [""] + lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hourglass.txt"))
@@ -117,9 +258,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--sizes", default="1080x1920,720x1280")
+    ap.add_argument("--train", action="store_true", help="measure forward + backward (training) instead; replaces the '# --train' part of --out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_hourglass.py measures on the GPU; there is none here")
+    if args.train:
+        return main_train(args)
     dev = torch.device("cuda")
     lines = []
 
