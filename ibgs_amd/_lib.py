@@ -215,6 +215,10 @@ HG_MAX_SIDE = 8192
 # every symbol include/ibgs_hg_train.h declares (tests/test_hourglass_train_host.py compares the two)
 HGB_EXPORTS = ["ibgs_hgb_required_scratch", "ibgs_hgb_backward"]
 
+# every symbol include/ibgs_hg_half.h declares (tests/test_hghalf_host.py compares the two)
+HGH_EXPORTS = ["ibgs_hgh_required_scratch", "ibgs_hgh_forward"]
+HGH_PACKED_WEIGHT_BYTES = 281600
+
 
 _lib = None
 
@@ -444,6 +448,13 @@ def load():
     lib.ibgs_hgb_backward.restype = i32
     # (stream, H, W, x, 18 parameters, burned, stages arena, grad_residual, grad_image_pred, grad_x, 18 gradients, scratch, bytes)
     lib.ibgs_hgb_backward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, vp] + [vp] * 18 + [vp, sz]
+    for name in HGH_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_hgh_required_scratch.restype = sz
+    lib.ibgs_hgh_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_hgh_forward.restype = i32
+    lib.ibgs_hgh_forward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, sz]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

@@ -8,8 +8,9 @@ out -- runs on this library's kernels, and a `ColorFusionResidualNet` checkpoint
   d1 = relu(conv3([u1, e1]; dec1 76 -> 38));  f = relu(conv1([d1, x]; fuse_input 76 -> 38));  residual = conv1(f; final 38 -> 3)
   image_pred = burned_in_gauss * render + residual          (render = channels 35 .. 37 of x)
 
-FORWARD ONLY (inference, under torch.no_grad()), float32, hidden_dim 38.  Training keeps torch's CNN behind `coloragg.fuse_color_inputs`.
-The contract is a tolerance against a float64 restatement (tests/hourglass_ref.py).
+FORWARD ONLY (inference, under torch.no_grad()), hidden_dim 38, float32 by default.  `precision="float16"` selects the half-precision forward (C ABI
+include/ibgs_hg_half.h, csrc/hghalf.hip): the roundings of the reference's test-time run under torch.autocast(float16), on the f16 matrix-core instruction.
+Training keeps torch's CNN behind `coloragg.fuse_color_inputs`.  The contract is a tolerance against a float64 restatement (tests/hourglass_ref.py).
 
 HIP only: raises when the library or a GPU tensor is missing (no torch fallback in the product path)."""
 import torch
@@ -44,17 +45,44 @@ def _stage_views(arena, h, w):
     return out
 
 
-def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False):
+PRECISIONS = ("float32", "float16")
+
+
+def _check_precision(name, precision):
+    if precision not in PRECISIONS:
+        raise ValueError("%s: precision must be \"float32\" or \"float16\", got %r" % (name, precision))
+
+
+def _stage_views_half(arena, h, w):
+    """The half-precision arena (include/ibgs_hg_half.h): h(x), then the six stages, pixel-major binary16 with the channels padded to a multiple of 8."""
+    sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
+    out, at = {}, 0
+    for name, ch, level in (("xh", C, 0),) + STAGES:
+        hh, ww = sides[level]
+        at = (at + 127) // 128 * 128
+        cp = (ch + 7) // 8 * 8
+        n = cp * hh * ww * 2
+        out[name] = arena[at:at + n].view(torch.float16).view(hh, ww, cp).permute(2, 0, 1)[:ch]
+        at += n
+    del out["xh"]
+    return out
+
+
+def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False, precision="float32"):
     """cnn_input: (1, 38, H, W) or (38, H, W), any strides, 4 <= H, W <= 8192; params: a `HourglassCNN`.  -> residual (3, H, W) float32.
 
     With `render_scale=float` (the reference's burned_in_gauss) -> (residual, image_pred) with image_pred = render_scale * cnn_input[35:38] + residual,
     formed in the last kernel: bit for bit what torch gives for that expression on the returned residual.
     With `return_stages` a dict of the intermediates e1, e2, b, u2, d2, u1 is returned last: VIEWS into the call's arena, (channels, h, w) each, valid until
     the next call on that device (a caller who keeps one longer clones it).
+    `precision`: "float32" (every call without the keyword keeps its bits) or "float16": x, the weights, the biases and the eight ReLU stages rounded to
+    binary16, float32 accumulation on the f16 matrix-core instruction, the residual left in float32 and image_pred formed from the unrounded input -- the
+    roundings of the reference's autocast run but for the last.  The outputs are float32 either way; the stages are then float16 views (any strides).
 
     Forward only: with grad mode enabled and an input or parameter that requires grad this raises -- call it under torch.no_grad(); training keeps
     torch's CNN behind coloragg.fuse_color_inputs.  Nothing waits for the host."""
     name = "hourglass_forward"
+    _check_precision(name, precision)
     if not isinstance(params, HourglassCNN):
         raise TypeError("%s: params must be a HourglassCNN, got %s" % (name, type(params).__name__))
     if not torch.is_tensor(cnn_input):
@@ -95,12 +123,13 @@ def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False)
     with torch.cuda.device(dev):
         residual = torch.empty((3, h, w), dtype=torch.float32, device=dev)
         image_pred = torch.empty((3, h, w), dtype=torch.float32, device=dev) if render_scale is not None else None
-    arena = _device.scratch(dev, _lib.load().ibgs_hg_required_scratch(h, w))
-    _device.call(dev, "ibgs_hg_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if render_scale is None else render_scale, residual.data_ptr(),
+    half = precision == "float16"
+    arena = _device.scratch(dev, (_lib.load().ibgs_hgh_required_scratch if half else _lib.load().ibgs_hg_required_scratch)(h, w))
+    _device.call(dev, "ibgs_hgh_forward" if half else "ibgs_hg_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if render_scale is None else render_scale, residual.data_ptr(),
                  None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
     out = (residual,) if image_pred is None else (residual, image_pred)
     if return_stages:
-        out += (_stage_views(arena, h, w),)
+        out += ((_stage_views_half if half else _stage_views)(arena, h, w),)
     return out[0] if len(out) == 1 else out
 
 
@@ -124,9 +153,9 @@ class HourglassCNN(nn.Module):
                 state_dict[prefix + mine] = state_dict.pop(prefix + theirs)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def forward(self, cnn_input, render_scale=None, return_stages=False):
+    def forward(self, cnn_input, render_scale=None, return_stages=False, precision="float32"):
         """`hourglass_forward` with this module's parameters."""
-        return hourglass_forward(cnn_input, self, render_scale, return_stages)
+        return hourglass_forward(cnn_input, self, render_scale, return_stages, precision)
 
 
 class ColorAggregationNet(nn.Module):
@@ -146,12 +175,12 @@ class ColorAggregationNet(nn.Module):
                     state_dict[prefix + mine + key[len(prefix + theirs):]] = state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False):
+    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32"):
         """`fuse_color` with this network."""
-        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level)
+        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level, precision)
 
 
-def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False):
+def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32"):
     """The reference's test-time fuse_color (no exposure correction, residual_resolution_scale 1) on the `render()` dictionary (keys "render",
     "warped_image", "cam_feat", "camera_ray", "min_depth_diff") with a `ColorAggregationNet`: the per-view front end, then the hourglass.  -> a dictionary
     with the reference's keys:
@@ -163,8 +192,12 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
                               the host does not know -- slots from that level on are all zero or unused
     The reference returns None when no slot level carries a colour.  With `none_if_no_level` the count is read back (ONE synchronisation, the only one) and
     None is returned then; without it nothing waits, the aggregated features are exactly zero and image_pred is the network's output on them.
+    `precision="float16"` runs the hourglass in half precision (`hourglass_forward`), as the reference renders by default (autocast).  The per-view front
+    end still runs its float32 kernels: its 32 features reach the hourglass unrounded by a half-precision MLP, which is closer to float64 than the
+    reference's autocast run (that one runs the two Linear layers in half too).  Without the keyword every bit is what it was.
     Forward only: call it under torch.no_grad()."""
     name = "fuse_color"
+    _check_precision(name, precision)
     if not isinstance(net, ColorAggregationNet):
         raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
     for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
@@ -186,7 +219,7 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     cnn_input, levels = net.front_end(render, warped, render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
     if none_if_no_level and int(levels.item()) == 0:
         return None
-    residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss))
+    residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss), precision=precision)
     slots = warped.reshape(-1, 3, h, w)
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
     return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),

@@ -2,14 +2,17 @@
 F.conv2d, two max_pool2d, two nearest interpolate, three cat, ReLUs and the image_pred expression, written from the definition --
 in ONE process on one MI355X, at (38, 1080, 1920) and (38, 720, 1280), under no_grad.  Output: profiles/hourglass.txt.
 
-    python tools/bench_hourglass.py [--out profiles/hourglass.txt] [--iters 5] [--repeats 9] [--warmup 12]
+    python tools/bench_hourglass.py [--out profiles/hourglass.txt] [--iters 5] [--repeats 9] [--warmup 12] [--append]
 
 Per size, alternating:
   hip                the seven launches
+  hip float16        `hourglass_forward(..., precision="float16")` (csrc/hghalf.hip): the packing launch and seven launches on the f16 matrix-core instruction;
+                     its yardsticks are BOTH hip (the float32 kernel) and torch autocast (the precision the reference renders with)
   torch float32      the composition in float32 (MIOpen's convolutions): THE YARDSTICK
   torch autocast     the same under torch.autocast(float16), for the record: another precision, not a competitor on equal terms
 and then the whole test-time tail from the rasterizer's planes: coloragg.fuse_color_inputs + hourglass (`hourglass.fuse_color`) against the fused front end
-followed by the torch float32 CNN and the image_pred expression.
+followed by the torch float32 CNN and the image_pred expression, and `hourglass.fuse_color(..., precision="float16")` beside them.  With --append the report
+is written after the forward reports --out already holds (in front of the "# --train" part) instead of replacing them.
 Timing: hipEvents around `iters` back-to-back calls on the current stream, after `warmup` calls of each (MIOpen chooses its kernels on the first uses of
 a shape); the median over `repeats` such windows, and their minimum and maximum.  Floors quoted beside the hip forward: 52 218 multiply-adds per pixel at the
 157.3 TFLOP/s f32 matrix peak, and the minimum traffic of the seven-launch split (x, e1 and u1 written once and read once or twice, the half- and
@@ -40,6 +43,7 @@ from ibgs_amd import _build, coloragg, hourglass  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 FP32_FLOPS = 157.3e12
+FP16_FLOPS = 2.5e15
 # (layer, Cout, Cin, taps, resolution level): the multiply-adds per full-resolution pixel
 MACS = sum(cout * cin * k * k / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS, (0, 1, 2, 1, 1, 0, 0, 0, 0)))
 
@@ -90,11 +94,18 @@ def min_bytes(h, w):
     return 4 * (2 * 38 * p1 + 3 * 38 * p1 + 3 * 19 * p2 + 2 * 9 * p4 + 2 * 19 * p2 + 2 * 19 * p2 + 2 * 38 * p1 + 9 * p1)
 
 
-def resource_report(say):
-    """hipcc's own report for hourglass.hip with the build's flags (compiled to a scratch file)."""
-    src = os.path.join(_build.CSRC, "hourglass.hip")
+def min_bytes_half(h, w):
+    p1, p2, p4 = h * w, (h // 2) * (w // 2), (h // 4) * (w // 4)
+    # x (float32) read by the packing launch and h(x) (40 binary16 per pixel) written, then read by enc1 and by the last launch; the stages as in min_bytes at
+    # 40 / 24 / 16 binary16 per pixel; the six output planes and the three colour planes read again
+    return 4 * 38 * p1 + 2 * (3 * 40 * p1 + 3 * 40 * p1 + 3 * 24 * p2 + 2 * 16 * p4 + 2 * 24 * p2 + 2 * 24 * p2 + 2 * 40 * p1) + 4 * 9 * p1
+
+
+def resource_report(say, unit="hourglass", kernel="hg_conv3_kernel"):
+    """hipcc's own report for hourglass.hip (or hghalf.hip) with the build's flags (compiled to a scratch file)."""
+    src = os.path.join(_build.CSRC, unit + ".hip")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([_build._hipcc()] + _build.compile_flags("hourglass") + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hg.o")],
+        r = subprocess.run([_build._hipcc()] + _build.compile_flags(unit) + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hg.o")],
                            capture_output=True, text=True)
     if r.returncode != 0:
         say("hipcc's resource report could not be produced (exit %d)" % r.returncode)
@@ -106,12 +117,13 @@ def resource_report(say):
             continue
         if m.group(1):
             t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", m.group(1))
-            cur = {"name": "hg_conv3_kernel<%s, %s, %s, %s, %s>" % (t.group(1), t.group(2), t.group(3), ("plain", "pool", "up")[int(t.group(4))], "fused" if t.group(5) == "1" else "-")
-                   if t else m.group(1)}
+            k = re.search(r"(hgh?_[a-z0-9_]+?)(?:I|E)", m.group(1))
+            cur = {"name": "%s<%s, %s, %s, %s, %s>" % (kernel, t.group(1), t.group(2), t.group(3), ("plain", "pool", "up")[int(t.group(4))], "fused" if t.group(5) == "1" else "-")
+                   if t else (k.group(1) if k else m.group(1))}
             rows.append(cur)
         elif cur is not None:
             cur[m.group(2).strip()] = int(m.group(3))
-    say("hipcc's report per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):")
+    say("hipcc's report for %s.hip per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):" % unit)
     for c in rows:
         say("  %-48s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
             % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
@@ -258,6 +270,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--sizes", default="1080x1920,720x1280")
+    ap.add_argument("--append", action="store_true", help="write the forward's report after the forward reports --out holds instead of replacing them")
     ap.add_argument("--train", action="store_true", help="measure forward + backward (training) instead; replaces the '# --train' part of --out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -281,7 +294,12 @@ def main():
     say("# %d multiply-adds per pixel; padding of the 16-wide instruction (Cout 38 -> 48, 19 -> 32, 9 -> 16; K to a multiple of 4): %.1f %% of the 3 x 3 layers' issued products are useful"
         % (round(MACS), 100.0 * useful / issued) + " (the 32-wide form, 38 -> 64: %.1f %%)"
         % (100.0 * useful / sum((cout + 31) // 32 * 32 * ((cin * k * k + 1) // 2 * 2) / 4 ** level for (_, cout, cin, k), level in zip(hourglass.LAYERS[:7], (0, 1, 2, 1, 1, 0, 0)))))
-    verdict = {}
+    # the half-precision kernel: the same M padding; K is 9 taps x the input's octets (channels padded to 8 per input of a concatenation) in chunks of four
+    octets = lambda name, cin: 2 * ((cin // 2 + 7) // 8) if name in ("dec2", "dec1") else (cin + 7) // 8
+    issued16 = sum((cout + 15) // 16 * 16 * 9 * 32 * ((octets(name, cin) + 3) // 4) / 4 ** level for (name, cout, cin, k), level in zip(hourglass.LAYERS[:7], (0, 1, 2, 1, 1, 0, 0)))
+    say("# hip float16 (v_mfma_f32_16x16x32_f16; K in chunks of 32 channels, one tap per instruction: 38 channels run as 64, [38 | 38] as 96, 19 and 9 as 32): %.1f %% of the 3 x 3 layers' issued products are useful"
+        % (100.0 * useful / issued16))
+    verdict, verdict16 = {}, {}
     with torch.no_grad():
         for size in args.sizes.split(","):
             h, w = (int(v) for v in size.split("x"))
@@ -305,11 +323,19 @@ def main():
             def autocast():
                 with torch.autocast("cuda", dtype=torch.float16):
                     return composed(x, cnn, 1.0)
-            r = compare({"hip": lambda: hourglass.hourglass_forward(x, cnn, render_scale=1.0), "torch float32": lambda: composed(x, cnn, 1.0), "torch autocast": autocast},
-                        args.iters, args.repeats, args.warmup)
+            r_h, ip_h = hourglass.hourglass_forward(x, cnn, render_scale=1.0, precision="float16")
+            with torch.autocast("cuda", dtype=torch.float16):
+                r_a, _ = composed(x, cnn, 1.0)
+            r_t, _ = composed(x, cnn, 1.0)
+            say("hip float16: max |residual - torch float32's| %.2e (torch autocast's: %.2e); image_pred is torch's expression on its residual bit for bit: %s"
+                % (float((r_h - r_t).abs().max()), float((r_a.float() - r_t).abs().max()), bool(torch.equal(ip_h, 1.0 * x[0, 35:38] + r_h))))
+            del r_h, ip_h, r_a, r_t
+            r = compare({"hip": lambda: hourglass.hourglass_forward(x, cnn, render_scale=1.0),
+                         "hip float16": lambda: hourglass.hourglass_forward(x, cnn, render_scale=1.0, precision="float16"),
+                         "torch float32": lambda: composed(x, cnn, 1.0), "torch autocast": autocast}, args.iters, args.repeats, args.warmup)
             flop_ms = 2 * MACS * h * w / FP32_FLOPS * 1e3
             byte_ms = min_bytes(h, w) / HBM_BYTES_PER_S * 1e3
-            for k in ("hip", "torch float32", "torch autocast"):
+            for k in ("hip", "hip float16", "torch float32", "torch autocast"):
                 say("%-16s %8.3f ms [%7.3f .. %7.3f]" % (k, r[k][0], r[k][1], r[k][2]))
             faster = r["hip"][0] < r["torch float32"][0]
             verdict[size] = faster
@@ -317,21 +343,45 @@ def main():
             say("floors of the hip forward: arithmetic (%d fma per pixel at 157.3 TFLOP/s) %.3f ms = %.0f %% of its time reached; bytes (%.2f GB at 8 TB/s) %.3f ms = %.0f %%; arena %.2f GB"
                 % (round(MACS), flop_ms, 100.0 * flop_ms / r["hip"][0], min_bytes(h, w) / 1e9, byte_ms, 100.0 * byte_ms / r["hip"][0], hourglass._lib.load().ibgs_hg_required_scratch(h, w) / 1e9))
 
+            half = r["hip float16"][0]
+            flop16_ms, byte16_ms = 2 * MACS * h * w / FP16_FLOPS * 1e3, min_bytes_half(h, w) / HBM_BYTES_PER_S * 1e3
+            ok = half < 0.95 * r["hip"][0] and half < 0.95 * r["torch autocast"][0]
+            verdict16[size] = ok
+            say("hip / hip float16 %5.2f x   torch autocast / hip float16 %5.2f x   hip float16 faster than both by more than 5 %%: %s" % (r["hip"][0] / half, r["torch autocast"][0] / half, ok))
+            say("floors of hip float16: arithmetic (at 2.5 PFLOP/s) %.3f ms = %.0f %% of its time reached; bytes (%.2f GB at 8 TB/s) %.3f ms = %.0f %%; the float32 split's byte floor %.3f ms = %.0f %%; arena %.2f GB"
+                % (flop16_ms, 100.0 * flop16_ms / half, min_bytes_half(h, w) / 1e9, byte16_ms, 100.0 * byte16_ms / half, byte_ms, 100.0 * byte_ms / half,
+                   hourglass._lib.load().ibgs_hgh_required_scratch(h, w) / 1e9))
+
             def tail_torch():
                 xi, m = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
                 return composed(xi, cnn, 1.0)
-            r = compare({"fuse_color": lambda: hourglass.fuse_color(pkg, net, 3), "front end + torch CNN": tail_torch}, args.iters, args.repeats, 3)
+            r = compare({"fuse_color": lambda: hourglass.fuse_color(pkg, net, 3), "fuse_color float16": lambda: hourglass.fuse_color(pkg, net, 3, precision="float16"),
+                         "front end + torch CNN": tail_torch}, args.iters, args.repeats, 3)
             say("the test-time tail from the rasterizer's planes: fuse_color (front end + hip hourglass) %8.3f ms [%7.3f .. %7.3f]   front end + torch float32 CNN %8.3f ms [%7.3f .. %7.3f]   ratio %5.2f x"
                 % (r["fuse_color"] + r["front end + torch CNN"] + (r["front end + torch CNN"][0] / r["fuse_color"][0],)))
+            say("the same tail with fuse_color(..., precision=\"float16\") %8.3f ms [%7.3f .. %7.3f]   fuse_color / fuse_color float16 %5.2f x"
+                % (r["fuse_color float16"] + (r["fuse_color"][0] / r["fuse_color float16"][0],)))
             del x, pkg, render, warped, feat, ray, mask
             torch.cuda.empty_cache()
     say()
     say("the hip hourglass faster than the torch float32 composition: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
+    say("hip float16 faster than both the float32 kernel and torch autocast by more than 5 %%: %s" % ", ".join("%s %s" % kv for kv in verdict16.items()))
     say()
     resource_report(say)
+    resource_report(say, "hghalf", "hgh_conv3_kernel")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    head, rest = [], []
+    if args.append and os.path.exists(args.out):          # after the forward reports the file holds, in front of the training report
+        head = open(args.out).read().split("\n")
+        at = next((i for i, line in enumerate(head) if line.startswith(TRAIN_MARK)), len(head))
+        head, rest = head[:at], head[at:]
+        while head and not head[-1].strip():
+            head.pop()
+        while rest and not rest[-1].strip():
+            rest.pop()
+        head.append("")
     with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write("\n".join(head + lines + ([""] + rest if rest else [])) + "\n")
 
 
 if __name__ == "__main__":
