@@ -219,6 +219,17 @@ HGB_EXPORTS = ["ibgs_hgb_required_scratch", "ibgs_hgb_backward"]
 HGH_EXPORTS = ["ibgs_hgh_required_scratch", "ibgs_hgh_forward"]
 HGH_PACKED_WEIGHT_BYTES = 281600
 
+# every symbol include/ibgs_lpips.h declares (tests/test_lpips_host.py compares the two)
+LPIPS_EXPORTS = ["ibgs_lpips_required_scratch", "ibgs_lpips_conv3", "ibgs_lpips_forward"]
+LPIPS_MIN_SIDE = 16
+LPIPS_MAX_SIDE = 4096
+LPIPS_CONVS = 13
+LPIPS_TAPS = 5
+# channels in and out of the thirteen convolutions, the resolution level (number of pools in front) of each one's output, and the convolution whose ReLU is tap k
+LPIPS_CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+LPIPS_LEVEL = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)
+LPIPS_TAP_CONV = (1, 3, 6, 9, 12)
+
 
 _lib = None
 
@@ -455,6 +466,17 @@ def load():
     lib.ibgs_hgh_required_scratch.argtypes = [i64, i64]
     lib.ibgs_hgh_forward.restype = i32
     lib.ibgs_hgh_forward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, sz]
+    for name in LPIPS_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_lpips_required_scratch.restype = sz
+    lib.ibgs_lpips_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_lpips_conv3.restype = i32
+    # (stream, hs, ws, cin, cout, pool, zscore, in_x, in_y, weight, bias, out)
+    lib.ibgs_lpips_conv3.argtypes = [vp] + [i32] * 6 + [vp] * 5
+    lib.ibgs_lpips_forward.restype = i32
+    # (stream, H, W, x, y, conv_w[13], conv_b[13], lin_w[5], lpips, tap_values, maps[5], scratch, bytes): the three tables and maps are host arrays of pointers
+    lib.ibgs_lpips_forward.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, ctypes.POINTER(vp), vp, sz]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

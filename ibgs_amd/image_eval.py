@@ -1,20 +1,25 @@
-"""The image side of the reference's evaluation (metrics.py:75-98) on the device: SSIM and PSNR per test view, and their means.
+"""The image side of the reference's evaluation (metrics.py:75-98) on the device: SSIM, PSNR and LPIPS per test view, and their means.
 
 `image_metrics` is one launch of the fused SSIM forward (csrc/ssim.hip, C ABI include/ibgs_ssim.h) with no per-pixel output: the same pass over the two
 images that sums the SSIM map also sums (x - y)^2 and |x - y|, so SSIM, PSNR (utils/image_utils.py:18-20) and L1 of every image of a batch cost one read of
 the batch.  `evaluate_images` stacks views of the same size into such launches and reads the numbers back once.
 
-LPIPS, the third column of the reference's table, is NOT computed: it needs the VGG weights of the `lpips` package, which this library does not ship.
+LPIPS, the third column of the reference's table, is computed when the caller hands over an `ibgs_amd.lpips.LPIPSNet` (the keyword `lpips_net`): the
+network runs on this library's kernels (csrc/lpips.hip), but the library does not ship the VGG16 and `lpips` weights -- `LPIPSNet.from_files` loads them
+from the two files of the caller's own LPIPS install, and nothing is downloaded.  Without the keyword both functions return exactly what they returned
+before it existed.
 
 HIP only: raises for CPU tensors (there is no CPU path)."""
 import torch
 
 from . import losses
+from . import lpips as _lpips
 
 
-def image_metrics(renders, gts):
+def image_metrics(renders, gts, lpips_net=None):
     """renders, gts: (N, C, H, W) (or (C, H, W): one image).  -> {"ssim": (N,), "psnr": (N,), "l1": (N,)} float32 on the device, nothing waits for it.
-    ssim = `ssim(render, gt)` per image, psnr = 20 log10(1 / sqrt(mse)) per image, l1 = mean |render - gt| per image."""
+    ssim = `ssim(render, gt)` per image, psnr = 20 log10(1 / sqrt(mse)) per image, l1 = mean |render - gt| per image.
+    With `lpips_net` (an `LPIPSNet`; C = 3, sides 16 .. 4096) also "lpips": (N,), `lpips.lpips(renders, gts, lpips_net)`."""
     dims = losses._ssim_check("image_metrics", renders, gts, 11, (3, 4))
     x = renders.detach().float().contiguous()
     y = gts.detach().float().contiguous()
@@ -23,14 +28,17 @@ def image_metrics(renders, gts):
         per, mse, l1 = (torch.empty(n, dtype=torch.float32, device=x.device) for _ in range(3))
     losses._ssim_forward(dims, x, y, per_image=per, mse=mse, l1_per_image=l1)
     psnr = 20.0 * torch.log10(1.0 / torch.sqrt(mse))
-    return {"ssim": per, "psnr": psnr, "l1": l1}
+    out = {"ssim": per, "psnr": psnr, "l1": l1}
+    if lpips_net is not None:
+        out["lpips"] = _lpips.lpips(renders, gts, lpips_net)
+    return out
 
 
-def evaluate_images(renders, gts, names=None):
-    """What metrics.py:75-98 computes for SSIM and PSNR.  renders, gts: a 4-D tensor each, or lists of (3, H, W) / (1, 3, H, W) tensors whose sizes may differ
+def evaluate_images(renders, gts, names=None, lpips_net=None):
+    """What metrics.py:75-98 computes for SSIM and PSNR, and with `lpips_net` (an `LPIPSNet`) for LPIPS too.  renders, gts: a 4-D tensor each, or lists of (3, H, W) / (1, 3, H, W) tensors whose sizes may differ
     from view to view (views of one size go into one launch).  names: one per view (default "00000", "00001", ..).
     -> {"SSIM": mean, "PSNR": mean, "per_view": {"SSIM": {name: value}, "PSNR": {name: value}}}, Python floats, after ONE device-to-host copy.
-    LPIPS is not computed (see the module's docstring)."""
+    With `lpips_net` the dictionary also holds "LPIPS": mean and per_view["LPIPS"]: {name: value} -- still after ONE copy; without it, neither."""
     def views(t, what):
         if torch.is_tensor(t):
             if t.dim() != 4:
@@ -56,9 +64,9 @@ def evaluate_images(renders, gts, names=None):
         groups.setdefault((tuple(a.shape), a.device), []).append(i)
     order, parts = [], []
     for idx in groups.values():
-        m = image_metrics(torch.stack([r[i] for i in idx]), torch.stack([g[i] for i in idx]))
+        m = image_metrics(torch.stack([r[i] for i in idx]), torch.stack([g[i] for i in idx]), lpips_net)
         order += idx
-        parts.append(torch.stack([m["ssim"], m["psnr"]]).to(parts[0].device if parts else m["ssim"].device))
+        parts.append(torch.stack([m["ssim"], m["psnr"]] + ([m["lpips"]] if lpips_net is not None else [])).to(parts[0].device if parts else m["ssim"].device))
     table = torch.cat(parts, dim=1)
     rows = torch.cat([table, table.mean(dim=1, keepdim=True)], dim=1).tolist()          # the one copy to the host
     per = {"SSIM": {}, "PSNR": {}}
@@ -66,4 +74,8 @@ def evaluate_images(renders, gts, names=None):
     for i, name in enumerate(names):
         per["SSIM"][name] = rows[0][pos[i]]
         per["PSNR"][name] = rows[1][pos[i]]
-    return {"SSIM": rows[0][-1], "PSNR": rows[1][-1], "per_view": per}
+    out = {"SSIM": rows[0][-1], "PSNR": rows[1][-1], "per_view": per}
+    if lpips_net is not None:
+        out["LPIPS"] = rows[2][-1]
+        per["LPIPS"] = {name: rows[2][pos[i]] for i, name in enumerate(names)}
+    return out
