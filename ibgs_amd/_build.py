@@ -10,7 +10,8 @@ ssim.hip takes no such flag: its contract is a tolerance, its filter passes are 
 themselves (#pragma clang fp contract(off)); geoloss.hip, which carries its own copy of those passes and forms, is built the same way, and so is coloragg.hip
 (the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains), and hourglass.hip (the CNN behind it, forward only: the same), and hgtrain.hip (that CNN's backward: the same),
 and hghalf.hip (that CNN's forward in half precision: the same), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
-are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted).
+are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
+the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -23,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "lpips", "hgtrain", "hghalf", "hourglass"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "lpips", "hgtrain", "hghalf", "hourglass"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -54,7 +55,8 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "hourglass": [os.path.join(HERE, "..", "include", "ibgs_hourglass.h")],
                 "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h")],
                 "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h")],
-                "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")]}
+                "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")],
+                "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")]}
 
 
 def _hipcc():
@@ -97,8 +99,8 @@ def csrc_sha():
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning; "dtu_" before "mesh_" and "scan_":
 # a dtu_emit_mesh_* or dtu_scan_* would otherwise go to those units; "lpips_" ahead of every entry that could claim one of its kernels by substring -- all but
-# "meval_", which no lpips_* name holds)
-KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel)
+KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))

@@ -230,6 +230,16 @@ LPIPS_CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 5
 LPIPS_LEVEL = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)
 LPIPS_TAP_CONV = (1, 3, 6, 9, 12)
 
+# every symbol include/ibgs_exposure.h declares (tests/test_exposure_host.py compares the two)
+EXPO_EXPORTS = ["ibgs_expo_required_scratch", "ibgs_expo_fit", "ibgs_expo_apply", "ibgs_expo_apply_backward"]
+EXPO_MAX_SIDE = 65536
+EXPO_SUMS = 22
+EXPO_THREADS = 256
+EXPO_MAX_GROUPS = 256
+EXPO_PIXELS_PER_THREAD = 4
+EXPO_MOMENTS, EXPO_SOLVE, EXPO_FIT = 1, 2, 3
+EXPO_PIVOT_MIN = 1e-11
+
 
 _lib = None
 
@@ -477,6 +487,17 @@ def load():
     lib.ibgs_lpips_forward.restype = i32
     # (stream, H, W, x, y, conv_w[13], conv_b[13], lin_w[5], lpips, tap_values, maps[5], scratch, bytes): the three tables and maps are host arrays of pointers
     lib.ibgs_lpips_forward.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, ctypes.POINTER(vp), vp, sz]
+    for name in EXPO_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_expo_required_scratch.restype = sz
+    lib.ibgs_expo_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_expo_fit.restype = i32
+    # (stream, H, W, render, warped, mask, affine_out, status_out, scratch, bytes, phases)
+    lib.ibgs_expo_fit.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, i32]
+    for f in (lib.ibgs_expo_apply, lib.ibgs_expo_apply_backward):          # (stream, H, W, affine, status, image, out)
+        f.restype = i32
+        f.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

@@ -191,9 +191,12 @@ class PerViewFrontEnd(nn.Module):
         return per_view_features(render, warped_image, cam_feat, camera_ray, self.w1, self.b1, self.w2, self.b2, nb_visible_src_frames, self.mode, levels)
 
 
-def fuse_color_inputs(render_pkg, front_end, nb_visible_src_frames=3, none_if_no_level=False):
+def fuse_color_inputs(render_pkg, front_end, nb_visible_src_frames=3, none_if_no_level=False, enable_exposure_correction=False):
     """What the reference's fuse_color builds for the hourglass CNN, from the `render()` dictionary (keys "render", "warped_image", "cam_feat", "camera_ray",
-    "min_depth_diff"; no exposure correction, residual_resolution_scale 1).  -> (cnn_input (1, 38, H, W), valid_warp_mask = (min_depth_diff < 0.999) as float).
+    "min_depth_diff"; residual_resolution_scale 1).  -> (cnn_input (1, 38, H, W), valid_warp_mask = (min_depth_diff < 0.999) as float).
+    `enable_exposure_correction` (the reference's option; render_pkg must also hold "use_first_src_frame_mask"): `exposure.exposure_correct` fits the affine
+    colour map and the corrected image takes the place of "render" -- it is channels 35 .. 37 of cnn_input; a caller who wants the map itself calls
+    exposure_correct.  Without the keyword every bit is what it was.
     During the reference's burn-in pass "render" and "warped_image" detached: only the front end's parameters then receive a gradient.
 
     The reference returns None when no slot level carries a colour.  That needs the count on the host: with `none_if_no_level` this function reads it back
@@ -209,6 +212,9 @@ def fuse_color_inputs(render_pkg, front_end, nb_visible_src_frames=3, none_if_no
     camera_ray = render_pkg["camera_ray"]
     if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
         camera_ray = camera_ray.view(3, h, w)
+    if enable_exposure_correction:
+        from .exposure import correct_package          # (exposure.py takes its argument checks from this module)
+        render = correct_package(name, render_pkg, render, render_pkg["warped_image"])[0]
     cnn_input, levels = front_end(render, render_pkg["warped_image"], render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
     if none_if_no_level and int(levels.item()) == 0:
         return None

@@ -18,6 +18,7 @@ from torch import nn
 
 from . import _device, _lib
 from .coloragg import PerViewFrontEnd, _f32
+from .exposure import correct_package
 
 C = _lib.HG_CHANNELS
 # the nine convolutions in the order of the C ABI: (name, Cout, Cin, kernel side)
@@ -175,15 +176,14 @@ class ColorAggregationNet(nn.Module):
                     state_dict[prefix + mine + key[len(prefix + theirs):]] = state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32"):
+    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", enable_exposure_correction=False):
         """`fuse_color` with this network."""
-        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level, precision)
+        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level, precision, enable_exposure_correction)
 
 
-def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32"):
-    """The reference's test-time fuse_color (no exposure correction, residual_resolution_scale 1) on the `render()` dictionary (keys "render",
-    "warped_image", "cam_feat", "camera_ray", "min_depth_diff") with a `ColorAggregationNet`: the per-view front end, then the hourglass.  -> a dictionary
-    with the reference's keys:
+def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", enable_exposure_correction=False):
+    """The reference's test-time fuse_color (residual_resolution_scale 1) on the `render()` dictionary (keys "render", "warped_image", "cam_feat",
+    "camera_ray", "min_depth_diff") with a `ColorAggregationNet`: the per-view front end, then the hourglass.  -> a dictionary with the reference's keys:
       image_pred, residual    (3, H, W)
       valid_warp_mask         (min_depth_diff < 0.999) as float
       burned_in_gauss         the float that was passed
@@ -195,6 +195,12 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     `precision="float16"` runs the hourglass in half precision (`hourglass_forward`), as the reference renders by default (autocast).  The per-view front
     end still runs its float32 kernels: its 32 features reach the hourglass unrounded by a half-precision MLP, which is closer to float64 than the
     reference's autocast run (that one runs the two Linear layers in half too).  Without the keyword every bit is what it was.
+    `enable_exposure_correction` (the reference's option of that name): render_pkg must also hold "use_first_src_frame_mask"; `exposure.exposure_correct`
+    fits the affine colour map on the device, and the corrected image takes the place of "render" in the residual features, in the CNN's colour channels
+    and in image_pred = burned_in_gauss * corrected + residual.  The correction is float32 whatever `precision`.  The dictionary then also holds
+      exposure_affine         (3, 4) float32
+      exposure_fit_ok         a 0-d int32 DEVICE tensor: 0 when the fit was undetermined and the image went through unchanged
+    Without the keyword every bit and every key is what it was.
     Forward only: call it under torch.no_grad()."""
     name = "fuse_color"
     _check_precision(name, precision)
@@ -216,6 +222,9 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
         camera_ray = camera_ray.view(3, h, w)
     warped = render_pkg["warped_image"]
+    exposure = {}
+    if enable_exposure_correction:
+        render, exposure["exposure_affine"], exposure["exposure_fit_ok"] = correct_package(name, render_pkg, render, warped)
     cnn_input, levels = net.front_end(render, warped, render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
     if none_if_no_level and int(levels.item()) == 0:
         return None
@@ -223,7 +232,7 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     slots = warped.reshape(-1, 3, h, w)
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
     return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),
-            "burned_in_gauss": float(burned_in_gauss), "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1)}
+            "burned_in_gauss": float(burned_in_gauss), "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1), **exposure}
 
 
 # ---- training: the backward (C ABI include/ibgs_hg_train.h, csrc/hgtrain.hip) --------------------------------------------------------------------------------
@@ -376,12 +385,14 @@ def hourglass_train(cnn_input, params, render_scale=None):
     return _HourglassTrain.apply(cnn_input, (h, w), render_scale, *[t for _, t in tensors])
 
 
-def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, burn_start=None, burn_end=None, none_if_no_level=False):
-    """The reference's TRAINING fuse_color (color_aggregation_network.py:156-250; residual_resolution_scale 1, no exposure correction) with a
+def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, burn_start=None, burn_end=None, none_if_no_level=False, enable_exposure_correction=False):
+    """The reference's TRAINING fuse_color (color_aggregation_network.py:156-250; residual_resolution_scale 1) with a
     `ColorAggregationNet`, differentiable end to end: the per-view front end (`PerViewFrontEnd`, forward and backward kernels), then `hourglass_train`.
     burned_in_gauss = (clamp((iter_count - burn_start) / (burn_end - burn_start), 0, 1) + 1) / 2, or 1.0 when one of the three is None; while it is below 1
     the five tensors of render_pkg are detached (no gradient reaches the rasterizer; the networks' parameters still train).  -> the dictionary of
-    `fuse_color`.  Nothing waits for the host unless `none_if_no_level` (which reads the level count back and returns None when it is 0)."""
+    `fuse_color`.  Nothing waits for the host unless `none_if_no_level` (which reads the level count back and returns None when it is 0).
+    `enable_exposure_correction`: as in `fuse_color`, after the detaching, in the reference's order; "render" receives its gradient through the correction
+    (the affine map is a constant of the backward), "warped_image" only the front end's.  Without the keyword every bit and every key is what it was."""
     name = "fuse_color_train"
     if not isinstance(net, ColorAggregationNet):
         raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
@@ -403,6 +414,9 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
         render, warped, cam_feat, camera_ray, min_depth_diff = (t.detach() for t in (render, warped, cam_feat, camera_ray, min_depth_diff))
     if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
         camera_ray = camera_ray.view(3, h, w)
+    exposure = {}
+    if enable_exposure_correction:
+        render, exposure["exposure_affine"], exposure["exposure_fit_ok"] = correct_package(name, render_pkg, render, warped)
     cnn_input, levels = net.front_end(render, warped, cam_feat, camera_ray, nb_visible_src_frames)
     if none_if_no_level and int(levels.item()) == 0:
         return None
@@ -410,4 +424,4 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
     slots = warped.reshape(-1, 3, h, w)
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
     return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (min_depth_diff < 0.999).float(), "burned_in_gauss": burned,
-            "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1)}
+            "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1), **exposure}
