@@ -5,7 +5,8 @@ CUDA rasterizer; every C function cites the reference file:line it follows).  On
 ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 this package; the product path (``ibgs_amd``) never does.
 
-PARITY STATUS: "parity unpinned" -- see the header of ``ibgs_oracle.c`` and DESIGN.md.
+PARITY STATUS: pinned stage by stage by the reference's own code compiled for the CPU (``oracle/reference.py``,
+``tests/test_reference_pins_oracle.py``) -- see the header of ``ibgs_oracle.c`` and DESIGN.md section 5.
 
 The front-end mirrors the stage order of ``CudaRasterizer::Rasterizer::forward/backward``
 (cuda_rasterizer/rasterizer_impl.cu:320-515, 519-666) and the tensor allocation of
@@ -145,21 +146,14 @@ def forward(inp, tex_quant=False, cull=False):
     gx, gy = tile_grid(W, H)
     shs = _f32(inp.get("shs")); colors_precomp = _f32(inp.get("colors_precomp"))
     scales = _f32(inp.get("scales")); rotations = _f32(inp.get("rotations"))
-    cov3D_precomp = _f32(inp.get("cov3D_precomp")); all_map = _f32(inp.get("all_map"))
+    cov3D_precomp = _f32(inp.get("cov3D_precomp"))
     opac = np.ascontiguousarray(np.asarray(inp["opacities"], dtype=_RT)).reshape(-1)
     vm = _f32(inp["viewmatrix"]).reshape(-1); pm = _f32(inp["projmatrix"]).reshape(-1)
-    campos = _f32(inp["campos"]).reshape(-1); bg = _f32(inp["bg"]).reshape(-1)
+    campos = _f32(inp["campos"]).reshape(-1)
     D = int(inp.get("sh_degree", 0)); M = 0 if shs is None else int(shs.shape[1])
     mod = float(inp.get("scale_modifier", 1.0))
     tanx, tany = float(inp["tanfovx"]), float(inp["tanfovy"])
-    render_geo = bool(inp.get("render_geo", False)); depth_only = bool(inp.get("render_depth_only", False))
-    n_src = int(inp.get("n_src", 1)); Lbuf = int(inp.get("buffer_length", 4)); thr = float(inp.get("depth_thr", 0.01))
-    ref_to_src = _f32(inp.get("ref_to_src")); src_cam_pos = _f32(inp.get("src_cam_pos"))
-    src_images = _f32(inp.get("src_images")); src_depths = _f32(inp.get("src_depths"))
-    if ref_to_src is None: ref_to_src = np.zeros((n_src, 16), _RT)
-    if src_cam_pos is None: src_cam_pos = np.zeros((n_src, 3), _RT)
-    if src_images is None: src_images = np.zeros((n_src, 3, H, W), _RT)
-    if src_depths is None: src_depths = np.zeros((n_src, 1, H, W), _RT)
+    depth_only = bool(inp.get("render_depth_only", False))
 
     st = {}
     st["radii"] = np.zeros(P, np.int32); st["means2D"] = np.zeros((P, 2), _RT)
@@ -194,6 +188,27 @@ def forward(inp, tex_quant=False, cull=False):
                    _p(st["means2D"]), _p(st["conic_opacity"]), _ci(W), _ci(H),
                    _p(st["keys"]), _p(st["point_list"]), _p(st["ranges"]))
     assert rc == 0, "oracle binning failed (%d)" % rc
+    _render_forward_into(inp, st, out, tex_quant)
+    out.update(st)
+    out["num_rendered"] = R
+    return out
+
+
+def _render_forward_into(inp, st, out, tex_quant):
+    """orc_render_forward on the per-Gaussian state and lists of `st` (radii ... conic_opacity, ranges, point_list); fills st's image state and `out`."""
+    L = lib()
+    W, H = int(inp["W"]), int(inp["H"])
+    colors_precomp = _f32(inp.get("colors_precomp")); all_map = _f32(inp.get("all_map"))
+    vm = _f32(inp["viewmatrix"]).reshape(-1); campos = _f32(inp["campos"]).reshape(-1); bg = _f32(inp["bg"]).reshape(-1)
+    tanx, tany = float(inp["tanfovx"]), float(inp["tanfovy"])
+    render_geo = bool(inp.get("render_geo", False)); depth_only = bool(inp.get("render_depth_only", False))
+    n_src = int(inp.get("n_src", 1)); Lbuf = int(inp.get("buffer_length", 4)); thr = float(inp.get("depth_thr", 0.01))
+    ref_to_src = _f32(inp.get("ref_to_src")); src_cam_pos = _f32(inp.get("src_cam_pos"))
+    src_images = _f32(inp.get("src_images")); src_depths = _f32(inp.get("src_depths"))
+    if ref_to_src is None: ref_to_src = np.zeros((n_src, 16), _RT)
+    if src_cam_pos is None: src_cam_pos = np.zeros((n_src, 3), _RT)
+    if src_images is None: src_images = np.zeros((n_src, 3, H, W), _RT)
+    if src_depths is None: src_depths = np.zeros((n_src, 1, H, W), _RT)
     feats = colors_precomp if colors_precomp is not None else st["rgb"]
     L.orc_render_forward(_ci(W), _ci(H), _p(st["ranges"]), _p(st["point_list"]), _p(st["means2D"]), _p(feats),
                          _p(all_map), _p(st["conic_opacity"]), _p(vm), _p(campos), _p(bg), _cf(tanx), _cf(tany),
@@ -205,12 +220,30 @@ def forward(inp, tex_quant=False, cull=False):
                          _p(out["color"]), _p(out["normal_map"]), _p(out["median_depth"]), _p(out["cam_feat"]),
                          _p(out["warped_image"]), _p(out["min_depth_diff"]), _p(out["camera_ray"]),
                          _p(out["use_first_src_frame_mask"]))
+
+
+def render_forward(inp, fwd, tex_quant=False):
+    """The blend stage alone (orc_render_forward) on the per-Gaussian state and sorted lists of `fwd` -- a forward result of this oracle or of
+    oracle.reference: means2D, rgb, conic_opacity, ranges, point_list are taken as given.  Returns the public outputs and the image state."""
+    W, H = int(inp["W"]), int(inp["H"]); HW = W * H
+    st = {"ranges": np.ascontiguousarray(fwd["ranges"], np.uint32), "point_list": np.ascontiguousarray(fwd["point_list"], np.uint32)}
+    for k in ("means2D", "rgb", "conic_opacity"):
+        st[k] = np.ascontiguousarray(np.asarray(fwd[k], dtype=_RT))
+    out = {
+        "color": np.zeros((3, H, W), _RT), "normal_map": np.zeros((3, H, W), _RT),
+        "median_depth": np.zeros((1, H, W), _RT), "cam_feat": np.zeros((4 * MAX_SRC, H, W), _RT),
+        "warped_image": np.zeros((3 * MAX_SRC, H, W), _RT), "min_depth_diff": np.zeros((1, H, W), _RT),
+        "camera_ray": np.zeros((3, H, W), _RT), "use_first_src_frame_mask": np.zeros((1, H, W), np.int32),
+    }
+    st["final_T"] = np.zeros(HW, _RT); st["n_contrib"] = np.zeros(HW, np.uint32)
+    st["cache_sum_w"] = np.zeros(HW, _RT); st["cache_low"] = np.zeros(HW, np.uint32); st["cache_high"] = np.zeros(HW, np.uint32)
+    st["valid_src_idx"] = np.full((MAX_SRC, HW), -1, np.int32); st["valid_src_w"] = np.zeros((MAX_SRC, HW), _RT)
+    _render_forward_into(inp, st, out, tex_quant)
     out.update(st)
-    out["num_rendered"] = R
     return out
 
 
-def backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=None, tex_quant=False):
+def backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=None, tex_quant=False, _with_preprocess=True):
     """Full backward given ``forward``'s result.  Returns the reference's 10 gradients
     (rasterize_points.cu:209-219, 270) plus dL_dconic."""
     L = lib()
@@ -259,10 +292,18 @@ def backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=No
     res["dL_dmeans2D"][:, :2] = acc_m; res["dL_dmeans2D_abs"][:, :2] = acc_ma
     res["dL_dconic"][:, 0] = acc_c[:, 0]; res["dL_dconic"][:, 1] = acc_c[:, 1]; res["dL_dconic"][:, 3] = acc_c[:, 2]
     res["dL_dopacity"][:, 0] = acc_o; res["dL_dcolors"][:] = acc_col; res["dL_dall_map"][:] = acc_am
+    if not _with_preprocess:
+        return {k: res[k] for k in ("dL_dmeans2D", "dL_dmeans2D_abs", "dL_dconic", "dL_dopacity", "dL_dcolors", "dL_dall_map")}
     pre = preprocess_backward(inp, fwd["radii"], fwd["clamped"], cov3D_precomp if cov3D_precomp is not None else fwd["cov3D"],
                               res["dL_dmeans2D"], res["dL_dconic"], res["dL_dcolors"])
     res.update(pre)
     return res
+
+
+def render_backward(inp, fwd, dL_dcolor, dL_dnormal=None, dL_ddepth=None, dL_dwarped=None, tex_quant=False):
+    """The blend stage of the backward alone (orc_render_backward) on the state and outputs of `fwd` -- a forward result of this oracle or of
+    oracle.reference: the six per-Gaussian sums dL_dmeans2D, dL_dmeans2D_abs, dL_dconic, dL_dopacity, dL_dcolors, dL_dall_map."""
+    return backward(inp, fwd, dL_dcolor, dL_dnormal, dL_ddepth, dL_dwarped, tex_quant=tex_quant, _with_preprocess=False)
 
 
 def preprocess_backward(inp, radii, clamped, cov3D, dL_dmean2D, dL_dconic, dL_dcolors):

@@ -7,9 +7,12 @@
  * It must only ever be used by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
  * leg -- never by the product path.
  *
- * PARITY STATUS: "parity unpinned" -- the reference ships no tests, golden vectors or
- * known-answer fixtures for this path and its CUDA sources cannot be
- * built here (no nvcc, CUDA textures, CUB). The oracle is pinned only indirectly:
+ * PARITY STATUS: pinned, stage by stage, by the reference's own code.  The reference's CUDA sources compile for the CPU with g++
+ * against stand-in headers (oracle/ref_cpu; the libraries land in oracle/_ref/, outside git) and
+ * tests/test_reference_pins_oracle.py holds this file to them: integer state and decisions exact, every float outside an
+ * atomic sum bit-identical between the uncontracted builds, the atomic sums within the reference's own block-order scatter
+ * (DESIGN.md section 5 has the measured tables and what stays unpinned: nvcc's contraction pattern, the hardware __expf and
+ * texture interpolation, the real interleaving of atomics).  Older, indirect pins remain:
  *   - SH evaluation / camera matrices against values produced by the reference's importable
  *     python helpers (tests/golden/make_golden.py -> tests/golden/ npz files),
  *   - hand-computable micro scenes (tests/test_oracle_kat.py),

@@ -30,10 +30,9 @@ def test_oracle_reproduces_its_frozen_c1_answer():
 REFERENCE = os.path.join(os.path.dirname(__file__), "golden", "reference_c1.npz")
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE), reason="tests/golden/reference_c1.npz absent: the reference's CUDA operator has not been run "
-                    "(tests/golden/make_reference_snapshot.py, on a CUDA machine) -- the oracle stays 'parity unpinned' (DESIGN.md section 4)")
 def test_oracle_against_the_reference_snapshot():
-    """The pin proper: the reference's own CUDA output for the seeded C1 inputs against the oracle (BASELINE's bars)."""
+    """The pin proper: the reference's own output for the seeded C1 inputs -- its CUDA sources compiled for the CPU and run by
+    tests/golden/make_reference_snapshot.py -- against the oracle (BASELINE's bars)."""
     ref = np.load(REFERENCE)
     inp, g = snap.build()
     now = snap.snapshot(inp, g)
