@@ -11,7 +11,9 @@ themselves (#pragma clang fp contract(off)); geoloss.hip, which carries its own 
 (the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains), and hourglass.hip (the CNN behind it, forward only: the same), and hgtrain.hip (that CNN's backward: the same),
 and hghalf.hip (that CNN's forward in half precision: the same), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
 are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
-the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain).
+the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
+(the reduced-resolution colour tail: a tolerance contract; its blends are written as fmaf, its MLP is coloragg's matrix-core chain, and the expressions that
+must not be contracted say so themselves).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -24,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "lpips", "hgtrain", "hghalf", "hourglass"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "resample", "lpips", "hgtrain", "hghalf", "hourglass"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -56,7 +58,8 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h")],
                 "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h")],
                 "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")],
-                "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")]}
+                "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
+                "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h")]}
 
 
 def _hipcc():
@@ -99,8 +102,8 @@ def csrc_sha():
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning; "dtu_" before "mesh_" and "scan_":
 # a dtu_emit_mesh_* or dtu_scan_* would otherwise go to those units; "lpips_" ahead of every entry that could claim one of its kernels by substring -- all but
-# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel)
-KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel; the same holds for "rsz_")
+KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("rsz_", "resample"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))

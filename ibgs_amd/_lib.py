@@ -240,6 +240,13 @@ EXPO_PIXELS_PER_THREAD = 4
 EXPO_MOMENTS, EXPO_SOLVE, EXPO_FIT = 1, 2, 3
 EXPO_PIVOT_MIN = 1e-11
 
+# every symbol include/ibgs_resample.h declares (tests/test_resample_host.py compares the two)
+RSZ_EXPORTS = ["ibgs_rsz_features_forward", "ibgs_rsz_residual_upsample"]
+RSZ_MAX_SRC = 5
+RSZ_MAX_SIDE = 65536
+RSZ_FEATURES = 32
+RSZ_MEAN, RSZ_MAX = 0, 1
+
 
 _lib = None
 
@@ -498,6 +505,15 @@ def load():
     for f in (lib.ibgs_expo_apply, lib.ibgs_expo_apply_backward):          # (stream, H, W, affine, status, image, out)
         f.restype = i32
         f.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    for name in RSZ_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_rsz_features_forward.restype = i32
+    # (stream, S, H, W, Hr, Wr, mode, render, warped, cam_feat, camera_ray, w1, b1, w2, b2, levels, out)
+    lib.ibgs_rsz_features_forward.argtypes = [vp, i32, i32, i32, i32, i32, i32] + [vp] * 10
+    lib.ibgs_rsz_residual_upsample.restype = i32
+    # (stream, H, W, Hr, Wr, residual_r, render, render_scale, residual_out, image_pred_out)
+    lib.ibgs_rsz_residual_upsample.argtypes = [vp, i32, i32, i32, i32, vp, vp, f32, vp, vp]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

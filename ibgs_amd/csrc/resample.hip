@@ -1,0 +1,311 @@
+// The reduced-resolution colour tail on the device (C ABI: include/ibgs_resample.h; Python: ibgs_amd/resample.py): the two resampling steps of the reference's
+// fuse_color under residual_resolution_scale != 1 (color_aggregation_network.py:200-239) for test-time rendering.  The reference builds the masked 7-channel
+// features of every source at full resolution, runs three F.interpolate over 21 + 3 + 3 planes, hands the result to the network, and interpolates the
+// residual back.  Here the first three become one kernel that gathers the four full-resolution taps of a reduced pixel, masks each tap, blends, and runs the
+// per-view MLP on the matrix cores without the full-resolution features ever existing; the last becomes one kernel that also forms image_pred.
+//
+// CONTRACT (the header states it in full)
+//   taps       align_corners = True; y0 = (i (in - 1)) / (out - 1) and the remainder in integers, t = (float)rem / (float)(out - 1); columns alike.
+//   value      top = fma(tx, b, (1 - tx) a); bottom = fma(tx, d, (1 - tx) c); value = fma(ty, bottom, (1 - ty) top).
+//   features   x(q, k) = value of x_full(., k) over the taps, x_full the slot of ibgs_color_agg.h at the full-resolution tap with its own mask; then the two
+//              Linear + ReLU layers, the mean or maximum over k < levels, the normalised ray and the colour.
+//   upsample   residual_out = value of residual_r; image_pred_out = render_scale * render + residual_out (product and sum rounded one after the other).
+//
+// THE 32 x 32 PRODUCTS are coloragg.hip's: v_mfma_f32_32x32x2_f32, a wave holds 32 pixels, lane l = (pixel l & 31, half l >> 5), register r of a 16-register
+// tile belongs to channel ch(r, h) = (r & 3) + 8 (r >> 2) + 4 h, so a layer's result is the next product's B operand as it stands.  This unit carries its
+// own copy of that chain (as geoloss.hip carries its SSIM passes): no header is shared, coloragg.hip is not touched.
+//
+// KERNELS
+//   rsz_features_kernel  256 threads = 4 waves of 32 reduced pixels, one block of pixels per wave (the grid is not capped); per slot 4 x 7 gathered loads,
+//                        21 blends and 20 MFMA.
+//   rsz_upsample_kernel  a thread per 4 consecutive output columns of a row: 12 gathered loads per pixel from the small residual, 16-byte loads of render and
+//                        16-byte stores of both outputs where the row allows (W % 4 == 0, aligned pointers), 4-byte ones otherwise.
+// What bounds them: DESIGN.md section 19.
+#include "common.h"
+#include "../../include/ibgs_resample.h"
+
+namespace ibgs {
+
+typedef float rsz_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int RT = 256;                              // threads per workgroup
+constexpr int RWAVES = RT / 64;
+constexpr int RB = 32;                               // reduced pixels per wave
+constexpr int RCHUNK = RWAVES * RB;                  // reduced pixels per workgroup
+constexpr int RF = IBGS_RSZ_FEATURES;                // feature width
+constexpr int RIN = 7, RINP = 8;                     // inputs of the first layer, and the row they are kept in
+constexpr int RQ = 4;                                // output columns per thread of the upsampling
+static_assert(RF == 32 && RB == 32, "the lane maps below");
+
+// the channel of register r of a tile in half h
+__device__ __forceinline__ constexpr int rsz_ch(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+__device__ __forceinline__ rsz_f32x16 rsz_mfma(float a, float b, rsz_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+
+// A lane's share of the weights, loaded once: the A operands of the two layers (row = this lane's l & 31, k-step kk = the inputs 2 kk + h of the first
+// layer and the channels ch(kk, h) of the second).
+struct RszFrag {
+    float a1[4], a2[16];
+    __device__ __forceinline__ RszFrag(const float* __restrict__ w1, const float* __restrict__ w2, int row, int h)
+    {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) a1[kk] = 2 * kk + h < RIN ? w1[row * RIN + 2 * kk + h] : 0.0f;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) a2[kk] = w2[row * RF + rsz_ch(kk, h)];
+    }
+};
+
+// The biases as the tiles the chains start from: [layer][half][register], read from LDS as broadcasts.  Ends with a barrier.
+struct __attribute__((aligned(16))) RszBias { float t[2][2][16]; };
+__device__ __forceinline__ void rsz_stage_bias(RszBias& s, const float* __restrict__ b1, const float* __restrict__ b2)
+{
+    if (threadIdx.x < 64) {
+        const int layer = threadIdx.x >> 5, hh = (threadIdx.x >> 4) & 1, r = threadIdx.x & 15;
+        s.t[layer][hh][r] = (layer ? b2 : b1)[rsz_ch(r, hh)];
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ rsz_f32x16 rsz_bias_tile(const RszBias& s, int layer, int h)
+{
+    rsz_f32x16 z;
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(&s.t[layer][h][i]);
+        z[i] = v.x; z[i + 1] = v.y; z[i + 2] = v.z; z[i + 3] = v.w;
+    }
+    return z;
+}
+
+// both layers of the lane's pixel: its 16 channels of h2
+__device__ __forceinline__ rsz_f32x16 rsz_mlp(const RszFrag& f, const RszBias& bias, const float (&x)[RINP], int h)
+{
+    rsz_f32x16 z = rsz_bias_tile(bias, 0, h), h1;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) z = rsz_mfma(f.a1[kk], h ? x[2 * kk + 1] : x[2 * kk], z);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) h1[r] = z[r] > 0.0f ? z[r] : 0.0f;
+    z = rsz_bias_tile(bias, 1, h);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) z = rsz_mfma(f.a2[kk], h1[kk], z);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = z[r] > 0.0f ? z[r] : 0.0f;
+    return z;
+}
+
+// One axis of the coordinate rule: the two taps of output index i of an `out`-long axis made of an `in`-long one, t and 1 - t.  (i (in - 1) < 2^32: both
+// sides are at most 65536.)
+struct RszTap { uint32_t i0, i1; float t, u; };
+__device__ __forceinline__ RszTap rsz_tap(uint32_t i, uint32_t in, uint32_t out)
+{
+    const uint32_t den = out > 1u ? out - 1u : 1u, num = out > 1u ? i * (in - 1u) : 0u;
+    RszTap r;
+    r.i0 = num / den;
+    r.i1 = min(r.i0 + 1u, in - 1u);
+    r.t = (float)(num - r.i0 * den) / (float)den;
+    r.u = 1.0f - r.t;
+    return r;
+}
+
+// the value rule on the taps a, b (row y0) and c, d (row y1)
+__device__ __forceinline__ float rsz_blend(float a, float b, float c, float d, const RszTap& ty, const RszTap& tx)
+{
+    const float top = fmaf(tx.t, b, tx.u * a), bottom = fmaf(tx.t, d, tx.u * c);
+    return fmaf(ty.t, bottom, ty.u * top);
+}
+
+// the features of slot k at the full-resolution pixel p (ibgs_color_agg.h): the mask is this pixel's own
+__device__ __forceinline__ void rsz_slot(const float* __restrict__ warped, const float* __restrict__ feat, const float (&r)[3], size_t plane, size_t p, int k, float (&x)[RIN])
+{
+#pragma clang fp contract(off)
+    const float* const f = feat + (size_t)k * 4 * plane + p;
+    const float* const w = warped + (size_t)k * 3 * plane + p;
+    x[3] = f[0]; x[4] = f[plane]; x[5] = f[2 * plane]; x[6] = f[3 * plane];
+    const float v = (((x[3] + x[4]) + x[5]) + x[6]) > 0.0f ? 1.0f : 0.0f;          // the sum's order is the contract
+    x[0] = (w[0] - r[0]) * v; x[1] = (w[plane] - r[1]) * v; x[2] = (w[2 * plane] - r[2]) * v;
+}
+
+__device__ __forceinline__ float rsz_norm3(float a, float b, float c)
+{
+#pragma clang fp contract(off)
+    return sqrtf((a * a + b * b) + c * c);
+}
+
+// a wave per block of 32 reduced pixels (wave-uniform bounds: the matrix instructions run with every lane on; a lane past the frame recomputes the last pixel)
+template <int MODE>
+__global__ void __launch_bounds__(RT) rsz_features_kernel(const float* __restrict__ render, const float* __restrict__ warped, const float* __restrict__ feat,
+                                                          const float* __restrict__ ray, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                          const float* __restrict__ w2, const float* __restrict__ b2, const int32_t* __restrict__ levels, int S, uint32_t H,
+                                                          uint32_t W, uint32_t Hr, uint32_t Wr, float* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+    const RszFrag f(w1, w2, c, h);
+    __shared__ RszBias bias;
+    rsz_stage_bias(bias, b1, b2);
+    const int lv = *levels;          // (wave-uniform)
+    const int L = lv < 0 ? 0 : (lv > S ? S : lv);
+    const size_t plane = (size_t)H * W, plane_r = (size_t)Hr * Wr;
+    const size_t first = ((size_t)blockIdx.x * RWAVES + wave) * RB;
+    if (first >= plane_r) return;          // (the whole wave; after the only barrier)
+    const bool in = first + c < plane_r;
+    const size_t q = in ? first + c : plane_r - 1;
+    const uint32_t i = (uint32_t)(q / Wr), j = (uint32_t)(q - (size_t)i * Wr);
+    const RszTap ty = rsz_tap(i, H, Hr), tx = rsz_tap(j, W, Wr);
+    const size_t p[4] = {(size_t)ty.i0 * W + tx.i0, (size_t)ty.i0 * W + tx.i1, (size_t)ty.i1 * W + tx.i0, (size_t)ty.i1 * W + tx.i1};
+    float r[4][3];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        r[n][0] = render[p[n]]; r[n][1] = render[plane + p[n]]; r[n][2] = render[2 * plane + p[n]];
+    }
+    rsz_f32x16 agg;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) agg[m] = 0.0f;
+    for (int k = 0; k < L; ++k) {
+        float xf[4][RIN], x[RINP];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) rsz_slot(warped, feat, r[n], plane, p[n], k, xf[n]);
+#pragma unroll
+        for (int e = 0; e < RIN; ++e) x[e] = rsz_blend(xf[0][e], xf[1][e], xf[2][e], xf[3][e], ty, tx);
+        x[7] = 0.0f;          // the eighth input of the first layer's four k-steps
+        const rsz_f32x16 h2 = rsz_mlp(f, bias, x, h);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) agg[m] = MODE == IBGS_RSZ_MEAN ? agg[m] + h2[m] : fmaxf(agg[m], h2[m]);          // (h2 >= 0: the maximum may start from 0)
+    }
+    if (MODE == IBGS_RSZ_MEAN && L > 1) {
+        const float n = (float)L;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) agg[m] = agg[m] / n;
+    }
+    if (!in) return;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) out[(size_t)rsz_ch(m, h) * plane_r + q] = agg[m];
+    float v[3];
+    if (h == 0) {          // half 0 writes the ray, half 1 the colour
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float* const src = ray + (size_t)ch * plane;
+            v[ch] = rsz_blend(src[p[0]], src[p[1]], src[p[2]], src[p[3]], ty, tx);
+        }
+        const float len = rsz_norm3(v[0], v[1], v[2]) + 1e-10f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) v[ch] = v[ch] / len;
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) v[ch] = rsz_blend(r[0][ch], r[1][ch], r[2][ch], r[3][ch], ty, tx);
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[(size_t)(RF + 3 * h + ch) * plane_r + q] = v[ch];
+}
+
+// VEC: W % 4 == 0 and render, residual_out, image_pred_out are 16-byte aligned.  Item = (row, quad of 4 columns); the same arithmetic per element either way.
+template <bool VEC>
+__global__ void __launch_bounds__(RT) rsz_upsample_kernel(const float* __restrict__ res, const float* __restrict__ render, float scale, uint32_t H, uint32_t W, uint32_t Hr,
+                                                          uint32_t Wr, uint32_t quads_per_row, uint32_t items, float* __restrict__ out, float* __restrict__ pred)
+{
+#pragma clang fp contract(off)
+    const uint32_t item = blockIdx.x * (uint32_t)RT + threadIdx.x;
+    if (item >= items) return;
+    const uint32_t i = item / quads_per_row, j0 = (item - i * quads_per_row) * RQ;
+    const size_t plane = (size_t)H * W, plane_r = (size_t)Hr * Wr;
+    const RszTap ty = rsz_tap(i, Hr, H);
+    const float* const row0 = res + (size_t)ty.i0 * Wr;
+    const float* const row1 = res + (size_t)ty.i1 * Wr;
+    float up[3][RQ];
+#pragma unroll
+    for (int e = 0; e < RQ; ++e) {
+        const RszTap tx = rsz_tap(min(j0 + e, W - 1u), Wr, W);          // (a column past the row's end repeats the last one and is not stored)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float* const a = row0 + (size_t)ch * plane_r;
+            const float* const b = row1 + (size_t)ch * plane_r;
+            up[ch][e] = rsz_blend(a[tx.i0], a[tx.i1], b[tx.i0], b[tx.i1], ty, tx);
+        }
+    }
+    const size_t at = (size_t)i * W + j0;
+    if (VEC) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float4 g = *reinterpret_cast<const float4*>(render + (size_t)ch * plane + at);
+            *reinterpret_cast<float4*>(out + (size_t)ch * plane + at) = make_float4(up[ch][0], up[ch][1], up[ch][2], up[ch][3]);
+            *reinterpret_cast<float4*>(pred + (size_t)ch * plane + at) = make_float4(scale * g.x + up[ch][0], scale * g.y + up[ch][1], scale * g.z + up[ch][2], scale * g.w + up[ch][3]);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < RQ; ++e) {
+            if (j0 + e >= W) break;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const size_t o = (size_t)ch * plane + at + e;
+                out[o] = up[ch][e];
+                pred[o] = scale * render[o] + up[ch][e];
+            }
+        }
+    }
+}
+
+static bool rsz_sides_ok(const char* who, int64_t H, int64_t W, int64_t Hr, int64_t Wr)
+{
+    if (H < 1 || W < 1 || H > IBGS_RSZ_MAX_SIDE || W > IBGS_RSZ_MAX_SIDE) {
+        set_error("%s: a frame of %lld x %lld is out of range (sides 1 .. %d)", who, (long long)H, (long long)W, IBGS_RSZ_MAX_SIDE);
+        return false;
+    }
+    if (Hr < 1 || Wr < 1 || Hr > IBGS_RSZ_MAX_SIDE || Wr > IBGS_RSZ_MAX_SIDE) {
+        set_error("%s: a reduced frame of %lld x %lld is out of range (sides 1 .. %d)", who, (long long)Hr, (long long)Wr, IBGS_RSZ_MAX_SIDE);
+        return false;
+    }
+    return true;
+}
+
+static bool rsz_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace ibgs
+
+using namespace ibgs;
+
+extern "C" {
+
+int32_t ibgs_rsz_features_forward(void* stream, int32_t S, int32_t H, int32_t W, int32_t Hr, int32_t Wr, int32_t mode, const float* render, const float* warped,
+                                  const float* cam_feat, const float* camera_ray, const float* w1, const float* b1, const float* w2, const float* b2,
+                                  const int32_t* levels, float* out)
+{
+    const char* const who = "rsz_features_forward";
+    if (S < 1 || S > IBGS_RSZ_MAX_SRC) { set_error("%s: %d sources out of range (1 .. %d)", who, S, IBGS_RSZ_MAX_SRC); return -IBGS_ERR_INVALID; }
+    if (!rsz_sides_ok(who, H, W, Hr, Wr)) return -IBGS_ERR_INVALID;
+    if (mode != IBGS_RSZ_MEAN && mode != IBGS_RSZ_MAX) { set_error("%s: mode %d is neither IBGS_RSZ_MEAN nor IBGS_RSZ_MAX", who, mode); return -IBGS_ERR_INVALID; }
+    if (!render || !warped || !cam_feat || !camera_ray) { set_error("%s: null image", who); return -IBGS_ERR_INVALID; }
+    if (!w1 || !b1 || !w2 || !b2) { set_error("%s: null parameters", who); return -IBGS_ERR_INVALID; }
+    if (!levels) { set_error("%s: null levels: the device word of cagg_levels is required", who); return -IBGS_ERR_INVALID; }
+    if (!out) { set_error("%s: null outputs: out is required", who); return -IBGS_ERR_INVALID; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t plane_r = (size_t)Hr * (size_t)Wr;
+    const unsigned groups = (unsigned)((plane_r + RCHUNK - 1) / RCHUNK);          // (at most 2^25)
+    if (mode == IBGS_RSZ_MEAN)
+        hipLaunchKernelGGL((rsz_features_kernel<IBGS_RSZ_MEAN>), dim3(groups), dim3(RT), 0, st, render, warped, cam_feat, camera_ray, w1, b1, w2, b2, levels, (int)S, (uint32_t)H,
+                           (uint32_t)W, (uint32_t)Hr, (uint32_t)Wr, out);
+    else
+        hipLaunchKernelGGL((rsz_features_kernel<IBGS_RSZ_MAX>), dim3(groups), dim3(RT), 0, st, render, warped, cam_feat, camera_ray, w1, b1, w2, b2, levels, (int)S, (uint32_t)H,
+                           (uint32_t)W, (uint32_t)Hr, (uint32_t)Wr, out);
+    IBGS_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t ibgs_rsz_residual_upsample(void* stream, int32_t H, int32_t W, int32_t Hr, int32_t Wr, const float* residual_r, const float* render, float render_scale,
+                                   float* residual_out, float* image_pred_out)
+{
+    const char* const who = "rsz_residual_upsample";
+    if (!rsz_sides_ok(who, H, W, Hr, Wr)) return -IBGS_ERR_INVALID;
+    if (!residual_r || !render) { set_error("%s: null image", who); return -IBGS_ERR_INVALID; }
+    if (!residual_out || !image_pred_out) { set_error("%s: null outputs: residual_out and image_pred_out are required", who); return -IBGS_ERR_INVALID; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t quads_per_row = ((uint32_t)W + RQ - 1) / RQ, items = (uint32_t)H * quads_per_row;          // (at most 2^30)
+    const unsigned groups = (items + RT - 1) / RT;
+    if (W % RQ == 0 && rsz_aligned16(render) && rsz_aligned16(residual_out) && rsz_aligned16(image_pred_out))
+        hipLaunchKernelGGL((rsz_upsample_kernel<true>), dim3(groups), dim3(RT), 0, st, residual_r, render, render_scale, (uint32_t)H, (uint32_t)W, (uint32_t)Hr, (uint32_t)Wr,
+                           quads_per_row, items, residual_out, image_pred_out);
+    else
+        hipLaunchKernelGGL((rsz_upsample_kernel<false>), dim3(groups), dim3(RT), 0, st, residual_r, render, render_scale, (uint32_t)H, (uint32_t)W, (uint32_t)Hr, (uint32_t)Wr,
+                           quads_per_row, items, residual_out, image_pred_out);
+    IBGS_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@ from torch import nn
 from . import _device, _lib
 from .coloragg import PerViewFrontEnd, _f32
 from .exposure import correct_package
+from .resample import count_levels, resized_features, scaled_size, upsample_residual
 
 C = _lib.HG_CHANNELS
 # the nine convolutions in the order of the C ABI: (name, Cout, Cin, kernel side)
@@ -176,13 +177,16 @@ class ColorAggregationNet(nn.Module):
                     state_dict[prefix + mine + key[len(prefix + theirs):]] = state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", enable_exposure_correction=False):
+    def forward(self, render_pkg, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", *, residual_resolution_scale=1.0,
+                enable_exposure_correction=False):
         """`fuse_color` with this network."""
-        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level, precision, enable_exposure_correction)
+        return fuse_color(render_pkg, self, nb_visible_src_frames, burned_in_gauss, none_if_no_level, precision, residual_resolution_scale=residual_resolution_scale,
+                          enable_exposure_correction=enable_exposure_correction)
 
 
-def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", enable_exposure_correction=False):
-    """The reference's test-time fuse_color (residual_resolution_scale 1) on the `render()` dictionary (keys "render", "warped_image", "cam_feat",
+def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, none_if_no_level=False, precision="float32", *, residual_resolution_scale=1.0,
+               enable_exposure_correction=False):
+    """The reference's test-time fuse_color on the `render()` dictionary (keys "render", "warped_image", "cam_feat",
     "camera_ray", "min_depth_diff") with a `ColorAggregationNet`: the per-view front end, then the hourglass.  -> a dictionary with the reference's keys:
       image_pred, residual    (3, H, W)
       valid_warp_mask         (min_depth_diff < 0.999) as float
@@ -201,6 +205,13 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
       exposure_affine         (3, 4) float32
       exposure_fit_ok         a 0-d int32 DEVICE tensor: 0 when the fit was undetermined and the image went through unchanged
     Without the keyword every bit and every key is what it was.
+    `residual_resolution_scale` (the reference's option of that name; keyword only, like `enable_exposure_correction` beside it): with a value other than 1 the
+    CNN runs at Hr x Wr = int(H s) x int(W s) (`resample.scaled_size`; both must lie in the hourglass's range, else ValueError): the exposure correction
+    if asked for, the level count at FULL resolution, `resample.resized_features` (the masked features interpolated, align_corners=True, not the images),
+    `hourglass_forward` there in the given `precision`, and `resample.upsample_residual`, which also forms image_pred = burned_in_gauss * render (or the
+    corrected image) + residual at H x W.  The dictionary is the same: residual is the upsampled (3, H, W) one, valid_warp_mask and warped_image_list stay
+    at full resolution.  With a value == 1 the code above runs and every bit and every key is what it was.  Training at a reduced resolution is not
+    covered: `fuse_color_train` and `coloragg.fuse_color_inputs` have no such keyword.
     Forward only: call it under torch.no_grad()."""
     name = "fuse_color"
     _check_precision(name, precision)
@@ -215,6 +226,12 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     h, w = int(render.shape[1]), int(render.shape[2])
     if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
         raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    reduced = None
+    if residual_resolution_scale != 1:
+        reduced = scaled_size(h, w, residual_resolution_scale)
+        if min(reduced) < _lib.HG_MIN_SIDE or max(reduced) > _lib.HG_MAX_SIDE:
+            raise ValueError("%s: residual_resolution_scale %r turns the frame of %d x %d into %d x %d, which is out of the hourglass's range (sides %d .. %d)"
+                             % (name, residual_resolution_scale, h, w, reduced[0], reduced[1], _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
     if torch.is_grad_enabled() and (any(torch.is_tensor(v) and v.requires_grad for v in render_pkg.values()) or any(p.requires_grad for p in net.parameters())):
         raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
                            "torch's CNN behind coloragg.fuse_color_inputs" % name)
@@ -225,10 +242,18 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     exposure = {}
     if enable_exposure_correction:
         render, exposure["exposure_affine"], exposure["exposure_fit_ok"] = correct_package(name, render_pkg, render, warped)
-    cnn_input, levels = net.front_end(render, warped, render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
+    if reduced is None:
+        cnn_input, levels = net.front_end(render, warped, render_pkg["cam_feat"], camera_ray, nb_visible_src_frames)
+    else:
+        levels = count_levels(warped, nb_visible_src_frames)
+        front = net.front_end
+        cnn_input = resized_features(render, warped, render_pkg["cam_feat"], camera_ray, front.w1, front.b1, front.w2, front.b2, reduced, levels, front.mode)
     if none_if_no_level and int(levels.item()) == 0:
         return None
-    residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss), precision=precision)
+    if reduced is None:
+        residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss), precision=precision)
+    else:
+        residual, image_pred = upsample_residual(hourglass_forward(cnn_input, net.cnn, precision=precision), render, float(burned_in_gauss))
     slots = warped.reshape(-1, 3, h, w)
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
     return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),
