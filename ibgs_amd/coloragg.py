@@ -114,6 +114,66 @@ def _count(name, what, n, least):
     return int(n)
 
 
+def _front_end_arguments(unit, name, render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, modes, mode, levels, own, before_device=None, levels_optional=False):
+    """The argument checks of the two front ends, `per_view_features` and `resample.resized_features`, in the order both make them: the shapes, the source
+    counts, the parameters, `own()` (the caller's check of the argument only it has; its value is handed back), the mode, `levels` (an int >= 0 or a 0-d int32 tensor; None
+    is left alone where `levels_optional`), `before_device(tensors)` if given, the refusal of CPU tensors under `unit`'s name, one device for all.
+    -> (S, H, W, own's value, levels, [render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2])"""
+    h, w = _image3(name, "render", render)
+    if _image3(name, "camera_ray", camera_ray) != (h, w):
+        raise ValueError("%s: camera_ray is %s, render %s" % (name, tuple(camera_ray.shape), tuple(render.shape)))
+    s, s_feat = _planes(name, "warped_image", warped_image, 3, h, w), _planes(name, "cam_feat", cam_feat, 4, h, w)
+    if s_feat != s:
+        raise ValueError("%s: warped_image holds %d sources, cam_feat %d" % (name, s, s_feat))
+    _parameters(name, w1, b1, w2, b2)
+    mine = own()
+    if mode not in modes:
+        raise ValueError("%s: mode must be 'mean' or 'max', got %r" % (name, mode))
+    named = [("render", render), ("warped_image", warped_image), ("cam_feat", cam_feat), ("camera_ray", camera_ray), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)]
+    if torch.is_tensor(levels):
+        if levels.dim() != 0 or levels.dtype != torch.int32:
+            raise ValueError("%s: levels must be an int or a 0-d int32 tensor, got %s %s" % (name, tuple(levels.shape), levels.dtype))
+        named.append(("levels", levels))
+    elif levels is not None or not levels_optional:
+        levels = _count(name, "levels", levels, 0)
+    if before_device is not None:
+        before_device([t for _, t in named])
+    for what, t in named:
+        _device.refuse_cpu(unit, "%s's %s" % (name, what), t)
+    dev = render.device
+    for what, t in named[1:]:
+        if t.device != dev:
+            raise ValueError("%s: render is on %s, %s on %s" % (name, dev, what, t.device))
+    return s, h, w, mine, levels, [t for _, t in named[:8]]
+
+
+def _levels_of(warped_image, s, h, w, nb):
+    """min(slots of warped_image whose colours are not all zero, nb, s) as a 0-d int32 DEVICE tensor (ibgs_cagg_levels); the arguments are checked already."""
+    dev = warped_image.device
+    x = _f32(warped_image)
+    with torch.cuda.device(dev):
+        levels = torch.empty((), dtype=torch.int32, device=dev)
+    sc = _device.scratch(dev, _lib.load().ibgs_cagg_required_scratch(s, h, w))
+    _device.call(dev, "ibgs_cagg_levels", s, h, w, x.data_ptr(), min(nb, s), levels.data_ptr(), sc.data_ptr(), sc.numel())
+    return levels
+
+
+def count_levels(warped_image, nb_visible_src_frames=3):
+    """warped_image (3 S, H, W) or (S, 3, H, W) at FULL resolution -> the 0-d int32 DEVICE tensor min(slots whose colours are not all zero,
+    nb_visible_src_frames, S): the level count of `per_view_features` without its forward (ibgs_cagg_levels).  Nothing waits for the host.
+    `resample.count_levels` is this function: the reduced-resolution tail is its caller, and its refusal of a CPU tensor names that module."""
+    name = "count_levels"
+    if not torch.is_tensor(warped_image) or warped_image.dim() not in (3, 4):
+        raise ValueError("%s: warped_image must be a (3 S, H, W) or (S, 3, H, W) tensor" % name)
+    h, w = int(warped_image.shape[-2]), int(warped_image.shape[-1])
+    if h * w == 0 or h > _lib.CAGG_MAX_SIDE or w > _lib.CAGG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides 1 .. %d)" % (name, h, w, _lib.CAGG_MAX_SIDE))
+    s = _planes(name, "warped_image", warped_image, 3, h, w)
+    nb = _count(name, "nb_visible_src_frames", nb_visible_src_frames, 1)
+    _device.refuse_cpu("resample", "%s's warped_image" % name, warped_image)
+    return _levels_of(warped_image, s, h, w, nb)
+
+
 def per_view_features(render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, nb_visible_src_frames=3, mode="mean", levels=None):
     """The front end on the rasterizer's outputs taken whole: render (3, H, W) (or the exposure-corrected image made of it); warped_image (3 S, H, W) or
     (S, 3, H, W); cam_feat (4 S, H, W) or (S, 4, H, W); camera_ray (3, H, W); the four parameters of `per_view_mlp` in nn.Linear layout (32, 7), (32,),
@@ -128,38 +188,13 @@ def per_view_features(render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2
     camera_ray get NO gradient: the rasterizer's backward has no input for either, so they are treated as data.  With render and warped_image detached
     only the parameter gradients are computed."""
     name = "per_view_features"
-    h, w = _image3(name, "render", render)
-    if _image3(name, "camera_ray", camera_ray) != (h, w):
-        raise ValueError("%s: camera_ray is %s, render %s" % (name, tuple(camera_ray.shape), tuple(render.shape)))
-    s, s_feat = _planes(name, "warped_image", warped_image, 3, h, w), _planes(name, "cam_feat", cam_feat, 4, h, w)
-    if s_feat != s:
-        raise ValueError("%s: warped_image holds %d sources, cam_feat %d" % (name, s, s_feat))
-    _parameters(name, w1, b1, w2, b2)
-    nb = _count(name, "nb_visible_src_frames", nb_visible_src_frames, 1)
-    if mode not in MODES:
-        raise ValueError("%s: mode must be 'mean' or 'max', got %r" % (name, mode))
-    if levels is not None and not torch.is_tensor(levels):
-        levels = _count(name, "levels", levels, 0)
-    named = [("render", render), ("warped_image", warped_image), ("cam_feat", cam_feat), ("camera_ray", camera_ray), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)]
-    if torch.is_tensor(levels):
-        if levels.dim() != 0 or levels.dtype != torch.int32:
-            raise ValueError("%s: levels must be an int or a 0-d int32 tensor, got %s %s" % (name, tuple(levels.shape), levels.dtype))
-        named.append(("levels", levels))
-    for what, t in named:
-        _device.refuse_cpu("coloragg", "%s's %s" % (name, what), t)
-    dev = render.device
-    for what, t in named[1:]:
-        if t.device != dev:
-            raise ValueError("%s: render is on %s, %s on %s" % (name, dev, what, t.device))
+    s, h, w, nb, levels, _ = _front_end_arguments("coloragg", name, render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, MODES, mode, levels,
+                                                  lambda: _count(name, "nb_visible_src_frames", nb_visible_src_frames, 1), levels_optional=True)
     if levels is None:
-        x = _f32(warped_image)
-        with torch.cuda.device(dev):
-            levels = torch.empty((), dtype=torch.int32, device=dev)
-        sc = _device.scratch(dev, _lib.load().ibgs_cagg_required_scratch(s, h, w))
-        _device.call(dev, "ibgs_cagg_levels", s, h, w, x.data_ptr(), min(nb, s), levels.data_ptr(), sc.data_ptr(), sc.numel())
+        levels = _levels_of(warped_image, s, h, w, nb)
     elif not torch.is_tensor(levels):
-        with torch.cuda.device(dev):
-            levels = torch.full((), min(levels, nb, s), dtype=torch.int32, device=dev)
+        with torch.cuda.device(render.device):
+            levels = torch.full((), min(levels, nb, s), dtype=torch.int32, device=render.device)
     out = _PerView.apply(render, warped_image, w1, b1, w2, b2, cam_feat.detach(), camera_ray.detach(), levels, (s, h, w), MODES[mode])
     return out, levels
 

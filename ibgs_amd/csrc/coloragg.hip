@@ -8,8 +8,7 @@
 // CONTRACT
 //   levels     min(slots of `warped` with any value != 0, nb_visible_src_frames, S), in a device word; the first `levels` slots are used.
 //   slot k     v = (((f0 + f1) + f2) + f3) > 0 in float32, in that order (cam_feat is signed); x = [(warped - render) v, f0 .. f3];
-//              h1 = relu(w1 x + b1), h2 = relu(w2 h1 + b2): each element an f32 fma chain started from the bias (the order of the 32 terms of the second
-//              layer is the matrix cores': below).
+//              h1 = relu(w1 x + b1), h2 = relu(w2 h1 + b2): shared/pv_mlp.h, which resample.hip runs too, states the chain and what its bits rest on.
 //   agg        mean: ((h2_0 + h2_1) + ..) / levels; max: the maximum over k; zeros when levels == 0.  out = [agg, camera_ray, render].
 //   backward   recomputes h1 and h2 with the same instructions (the same bits), then dz2 = g (h2 > 0) with g = grad_out / levels (mean) or grad_out at the
 //              first slot attaining the maximum (max), dz1 = (w2^T dz2) (h1 > 0), dx = w1^T dz1; grad_warped[3k + c] = dx[c] v, grad_render[c] =
@@ -20,12 +19,10 @@
 //              scratch arena; cagg_final_kernel adds the workgroups: sixteen strided series per element, then those in order, one rounding to f32 at the
 //              end.  No float atomics.
 //
-// THE 32 x 32 PRODUCTS run on the matrix cores in exact f32 (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, at the vector fp32 rate).  A wave
-// holds 32 pixels: lane l = (pixel l & 31, half h = l >> 5), and register r of a 16-register tile belongs to channel ch(r, h) = (r & 3) + 8 (r >> 2) + 4 h:
-// the layout in which the instruction leaves a result whose rows are channels and whose columns are pixels.  That result is the NEXT product's B operand as
-// it stands -- k-step kk takes register kk, i.e. the channels ch(kk, 0) and ch(kk, 1) -- so the weights are loaded once per wave in that (permuted) k order, 16
-// registers per matrix, and h1, h2, dz2, dz1 never leave the registers.  Only the weight gradient, whose long dimension is the pixels, goes through LDS: each
-// lane stores its pixel's dz2, h1 and dz1 as rows and the wave reads them back a pixel pair per k-step.
+// THE 32 x 32 PRODUCTS run on the matrix cores in exact f32, in the lane and register map of shared/pv_mlp.h: a wave holds 32 pixels, a 16-register tile's
+// rows are channels and its columns pixels, and a product's result is the next one's B operand as it stands.  The backward's own products (w2^T dz2, the
+// weight gradient) use the same map, so h1, h2, dz2, dz1 never leave the registers.  Only the weight gradient, whose long dimension is the pixels, goes
+// through LDS: each lane stores its pixel's dz2, h1 and dz1 as rows and the wave reads them back a pixel pair per k-step.
 //
 // KERNELS
 //   cagg_levels_kernel   S x B workgroups scan the slots; a workgroup that found a value ORs its slot's bit into a word, takes a ticket, and the last one
@@ -35,100 +32,29 @@
 //   cagg_final_kernel    82 workgroups: 16 elements each.
 // What bounds them, storing against recomputing, and the matrix cores against the VALU: DESIGN.md section 14.
 #include "common.h"
+#include "shared/pv_mlp.h"
 #include "../../include/ibgs_color_agg.h"
 
 namespace ibgs {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CT = 256;                              // threads per workgroup
 constexpr int CWAVES = CT / 64;
 constexpr int CB = 32;                               // pixels per wave
 constexpr int CHUNK = CWAVES * CB;                   // pixels per workgroup and step
-constexpr int CF = IBGS_CAGG_FEATURES;               // feature width
-constexpr int CIN = 7, CINP = 8;                     // inputs of the first layer, and the row they are kept in
 constexpr int CROW = 33;                             // row stride of the staged rows: the 32 lanes of a half store one column into 32 banks
-constexpr int CAGG_PARTIAL = CF * CINP + CF * CF + CF;          // a workgroup's sums: [dW1 | db1] (32 x 8), dW2 (32 x 32), db2 (32)
+constexpr int CAGG_PARTIAL = PV_F * PV_INP + PV_F * PV_F + PV_F;          // a workgroup's sums: [dW1 | db1] (32 x 8), dW2 (32 x 32), db2 (32)
 constexpr int CAGG_MAX_GROUPS = 512;                 // workgroups of the backward (256 CUs x 2 resident): what bounds the arena
 constexpr int CAGG_FWD_MAX_GROUPS = 4096;
-constexpr int CAGG_WAVE_WORDS = CF * CF + CF * CINP + 2 * CF;   // a wave's accumulators as the cross-wave sum reads them
+constexpr int CAGG_WAVE_WORDS = PV_F * PV_F + PV_F * PV_INP + 2 * PV_F;   // a wave's accumulators as the cross-wave sum reads them
 constexpr int LV_THREADS = 256, LV_MAX_BLOCKS = 128; // level count: workgroups per slot
 constexpr int FIN_ELEMS = 16, FIN_SERIES = 16;       // final kernel: elements per workgroup, strided series per element
-static_assert(CF == 32 && CB == 32 && CAGG_PARTIAL % FIN_ELEMS == 0 && FIN_ELEMS * FIN_SERIES == CT, "the lane maps below");
+static_assert(PV_F == IBGS_CAGG_FEATURES && CB == PV_F && CAGG_PARTIAL % FIN_ELEMS == 0 && FIN_ELEMS * FIN_SERIES == CT, "the lane maps below");
 static_assert(CWAVES * CAGG_WAVE_WORDS * sizeof(double) <= CWAVES * 3 * CB * CROW * sizeof(float), "the cross-wave sum reuses the staged rows");
-
-// the channel of register r of a tile in half h
-__device__ __forceinline__ constexpr int cagg_ch(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ f32x16 cagg_mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-// A lane's share of the weights, loaded once: the A operands of the two layers (row = this lane's l & 31, k-step kk = the inputs 2 kk + h of the first
-// layer and the channels ch(kk, h) of the second).
-struct CaggFrag {
-    float a1[4], a2[16];
-    __device__ __forceinline__ CaggFrag(const float* __restrict__ w1, const float* __restrict__ w2, int row, int h)
-    {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) a1[kk] = 2 * kk + h < CIN ? w1[row * CIN + 2 * kk + h] : 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) a2[kk] = w2[row * CF + cagg_ch(kk, h)];
-    }
-};
-
-// The biases as the tiles the chains start from: [layer][half][register], the same for every pixel, so they live in LDS and are read as broadcasts
-// (32 registers per lane otherwise).  Ends with a barrier.
-struct __attribute__((aligned(16))) CaggBias { float t[2][2][16]; };
-__device__ __forceinline__ void cagg_stage_bias(CaggBias& s, const float* __restrict__ b1, const float* __restrict__ b2)
-{
-    if (threadIdx.x < 64) {
-        const int layer = threadIdx.x >> 5, hh = (threadIdx.x >> 4) & 1, r = threadIdx.x & 15;
-        s.t[layer][hh][r] = (layer ? b2 : b1)[cagg_ch(r, hh)];
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ f32x16 cagg_bias_tile(const CaggBias& s, int layer, int h)
-{
-    f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(&s.t[layer][h][i]);
-        z[i] = v.x; z[i + 1] = v.y; z[i + 2] = v.z; z[i + 3] = v.w;
-    }
-    return z;
-}
 
 __device__ __forceinline__ int cagg_levels_of(const int32_t* __restrict__ levels, int S)
 {
     const int l = *levels;          // (wave-uniform)
     return l < 0 ? 0 : (l > S ? S : l);
-}
-
-// the features of slot k of pixel p; x[7] = 0: the eighth input of the first layer's four k-steps.  -> v as a float
-__device__ __forceinline__ float cagg_slot(const float* __restrict__ warped, const float* __restrict__ feat, const float (&r)[3], size_t plane, size_t p, int k, float (&x)[CINP])
-{
-#pragma clang fp contract(off)
-    const float* const f = feat + (size_t)k * 4 * plane + p;
-    const float* const w = warped + (size_t)k * 3 * plane + p;
-    x[3] = f[0]; x[4] = f[plane]; x[5] = f[2 * plane]; x[6] = f[3 * plane];
-    const float v = (((x[3] + x[4]) + x[5]) + x[6]) > 0.0f ? 1.0f : 0.0f;          // the sum's order is the contract
-    x[0] = (w[0] - r[0]) * v; x[1] = (w[plane] - r[1]) * v; x[2] = (w[2 * plane] - r[2]) * v;
-    x[7] = 0.0f;
-    return v;
-}
-
-// both layers of the lane's pixel: its 16 channels of h1 and of h2 (the forward and the backward's recomputation run the same instructions: the same bits)
-__device__ __forceinline__ void cagg_mlp(const CaggFrag& f, const CaggBias& bias, const float (&x)[CINP], int h, f32x16& h1, f32x16& h2)
-{
-    f32x16 z = cagg_bias_tile(bias, 0, h);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) z = cagg_mfma(f.a1[kk], h ? x[2 * kk + 1] : x[2 * kk], z);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) h1[r] = z[r] > 0.0f ? z[r] : 0.0f;
-    z = cagg_bias_tile(bias, 1, h);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) z = cagg_mfma(f.a2[kk], h1[kk], z);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) h2[r] = z[r] > 0.0f ? z[r] : 0.0f;
 }
 
 // slot's grid: S x per_slot workgroups; state[0]: the slots that hold a value, state[1]: workgroups done (both zero on entry)
@@ -159,9 +85,9 @@ __global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ out)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const CaggFrag f(w1, w2, c, h);
-    __shared__ CaggBias bias;
-    cagg_stage_bias(bias, b1, b2);
+    const PvFrag f(w1, w2, c, h);
+    __shared__ PvBias bias;
+    pv_stage_bias(bias, b1, b2);
     const int L = cagg_levels_of(levels, S);
     const size_t blocks = (plane + CB - 1) / CB;
     for (size_t b = (size_t)blockIdx.x * CWAVES + wave; b < blocks; b += (size_t)gridDim.x * CWAVES) {
@@ -169,14 +95,14 @@ __global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ 
         const bool in = q < plane;
         const size_t p = in ? q : plane - 1;
         const float r[3] = {render[p], render[plane + p], render[2 * plane + p]};
-        f32x16 agg;
+        pv_f32x16 agg;
 #pragma unroll
         for (int j = 0; j < 16; ++j) agg[j] = 0.0f;
         for (int k = 0; k < L; ++k) {
-            float x[CINP];
-            f32x16 h1, h2;
-            cagg_slot(warped, feat, r, plane, p, k, x);
-            cagg_mlp(f, bias, x, h, h1, h2);
+            float x[PV_INP];
+            pv_f32x16 h1, h2;
+            pv_slot(warped, feat, r, plane, p, k, x);
+            pv_mlp(f, bias, x, h, h1, h2);
 #pragma unroll
             for (int j = 0; j < 16; ++j) agg[j] = MODE == IBGS_CAGG_MEAN ? agg[j] + h2[j] : fmaxf(agg[j], h2[j]);          // (h2 >= 0: the maximum may start from 0)
         }
@@ -187,11 +113,11 @@ __global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ 
         }
         if (in) {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) out[(size_t)cagg_ch(j, h) * plane + p] = agg[j];
+            for (int j = 0; j < 16; ++j) out[(size_t)pv_ch(j, h) * plane + p] = agg[j];
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {          // half 0 passes the ray on, half 1 the colour
                 const float* const src = h ? render : ray;
-                out[(size_t)(CF + 3 * h + ch) * plane + p] = src[(size_t)ch * plane + p];
+                out[(size_t)(PV_F + 3 * h + ch) * plane + p] = src[(size_t)ch * plane + p];
             }
         }
     }
@@ -205,23 +131,23 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
                                                       float* __restrict__ d_render, float* __restrict__ d_warped, double* __restrict__ partials)
 {
     __shared__ __attribute__((aligned(16))) float s_t[PG ? CWAVES : 1][PG ? 3 : 1][PG ? CB : 1][PG ? CROW : 1];          // per wave: its pixels' dz2, h1, dz1 as rows
-    __shared__ __attribute__((aligned(16))) float s_x[PG ? CWAVES : 1][PG ? CB : 1][CINP];  // ... and [x | 1]
+    __shared__ __attribute__((aligned(16))) float s_x[PG ? CWAVES : 1][PG ? CB : 1][PV_INP];  // ... and [x | 1]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const CaggFrag f(w1, w2, c, h);
-    __shared__ CaggBias bias;
-    cagg_stage_bias(bias, b1, b2);
+    const PvFrag f(w1, w2, c, h);
+    __shared__ PvBias bias;
+    pv_stage_bias(bias, b1, b2);
     float a2t[16];          // the A operand of w2^T dz2: row = this lane's input channel c, k-step kk = the output channels ch(kk, h)
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) a2t[kk] = w2[cagg_ch(kk, h) * CF + c];
+    for (int kk = 0; kk < 16; ++kk) a2t[kk] = w2[pv_ch(kk, h) * PV_F + c];
     __shared__ float4 s_w1c[2][16];          // w1's first three columns at the 16 channels of each half (the same for every pixel: read as a broadcast)
     if (IG && threadIdx.x < 32) {
         const int r = threadIdx.x & 15, hh = threadIdx.x >> 4;
-        s_w1c[hh][r] = make_float4(w1[cagg_ch(r, hh) * CIN], w1[cagg_ch(r, hh) * CIN + 1], w1[cagg_ch(r, hh) * CIN + 2], 0.0f);
+        s_w1c[hh][r] = make_float4(w1[pv_ch(r, hh) * PV_IN], w1[pv_ch(r, hh) * PV_IN + 1], w1[pv_ch(r, hh) * PV_IN + 2], 0.0f);
     }
     __syncthreads();
     const int L = cagg_levels_of(levels, S);
     const int r1 = lane >> 1, c0 = (lane & 1) * 4;          // this lane's elements of [dW1 | db1]: row r1 (dz1), columns c0 .. c0 + 3 (x, 1)
-    f32x16 acc2;          // dW2: register r = row ch(r, h) (dz2), column c (h1); the f32 chain of one chunk's pixels and slots, then added to acc2d
+    pv_f32x16 acc2;          // dW2: register r = row ch(r, h) (dz2), column c (h1); the f32 chain of one chunk's pixels and slots, then added to acc2d
     double acc2d[16], acc1[4] = {0.0, 0.0, 0.0, 0.0}, accb = 0.0;          // accb: db2 of channel c over the pixels 16 h .. 16 h + 15 of the wave
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc2[r] = 0.0f; acc2d[r] = 0.0; }
@@ -231,34 +157,34 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
         const bool in = q < plane;
         const size_t p = in ? q : plane - 1;          // a lane past the frame recomputes the last pixel under a zero gradient: it adds zeros
         const float r[3] = {render[p], render[plane + p], render[2 * plane + p]};
-        f32x16 g;
+        pv_f32x16 g;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) g[j] = in ? go[(size_t)cagg_ch(j, h) * plane + p] : 0.0f;
+        for (int j = 0; j < 16; ++j) g[j] = in ? go[(size_t)pv_ch(j, h) * plane + p] : 0.0f;
         if (MODE == IBGS_CAGG_MEAN && L > 1) {
             const float n = (float)L;
 #pragma unroll
             for (int j = 0; j < 16; ++j) g[j] = g[j] / n;
         }
-        f32x16 hmax;
+        pv_f32x16 hmax;
         uint32_t taken = 0u;          // max mode: the channels whose maximum an earlier slot attained
         if (MODE == IBGS_CAGG_MAX) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) hmax[j] = 0.0f;
             for (int k = 0; k < L; ++k) {
-                float x[CINP];
-                f32x16 h1, h2;
-                cagg_slot(warped, feat, r, plane, p, k, x);
-                cagg_mlp(f, bias, x, h, h1, h2);
+                float x[PV_INP];
+                pv_f32x16 h1, h2;
+                pv_slot(warped, feat, r, plane, p, k, x);
+                pv_mlp(f, bias, x, h, h1, h2);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) hmax[j] = fmaxf(hmax[j], h2[j]);
             }
         }
         float dr[3] = {0.0f, 0.0f, 0.0f};
         for (int k = 0; k < L; ++k) {
-            float x[CINP];
-            f32x16 h1, dz2, dz1;
-            const float v = cagg_slot(warped, feat, r, plane, p, k, x);
-            cagg_mlp(f, bias, x, h, h1, dz2);          // dz2 = h2 for now
+            float x[PV_INP];
+            pv_f32x16 h1, dz2, dz1;
+            const float v = pv_slot(warped, feat, r, plane, p, k, x);
+            pv_mlp(f, bias, x, h, h1, dz2);          // dz2 = h2 for now
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 bool on = dz2[j] > 0.0f;
@@ -271,7 +197,7 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
                 dz1[j] = 0.0f;
             }
 #pragma unroll
-            for (int kk = 0; kk < 16; ++kk) dz1 = cagg_mfma(a2t[kk], dz2[kk], dz1);
+            for (int kk = 0; kk < 16; ++kk) dz1 = pv_mfma(a2t[kk], dz2[kk], dz1);
 #pragma unroll
             for (int j = 0; j < 16; ++j) dz1[j] = h1[j] > 0.0f ? dz1[j] : 0.0f;
             if constexpr (IG) {
@@ -296,14 +222,14 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
                 __syncthreads();          // the rows of the slot before have been read
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    s_t[wave][0][c][cagg_ch(j, h)] = dz2[j];
-                    s_t[wave][1][c][cagg_ch(j, h)] = h1[j];
-                    s_t[wave][2][c][cagg_ch(j, h)] = dz1[j];
+                    s_t[wave][0][c][pv_ch(j, h)] = dz2[j];
+                    s_t[wave][1][c][pv_ch(j, h)] = h1[j];
+                    s_t[wave][2][c][pv_ch(j, h)] = dz1[j];
                 }
                 *reinterpret_cast<float4*>(&s_x[wave][c][4 * h]) = h ? make_float4(x[4], x[5], x[6], in ? 1.0f : 0.0f) : make_float4(x[0], x[1], x[2], x[3]);
                 __syncthreads();
 #pragma unroll
-                for (int kk = 0; kk < 16; ++kk) acc2 = cagg_mfma(s_t[wave][0][2 * kk + h][c], s_t[wave][1][2 * kk + h][c], acc2);          // pixels in order
+                for (int kk = 0; kk < 16; ++kk) acc2 = pv_mfma(s_t[wave][0][2 * kk + h][c], s_t[wave][1][2 * kk + h][c], acc2);          // pixels in order
 #pragma unroll 4
                 for (int t = 0; t < 16; ++t) accb += (double)s_t[wave][0][16 * h + t][c];
 #pragma unroll 4
@@ -321,7 +247,7 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
         if (IG && in && h == 0) {
             if (d_render) {
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) d_render[(size_t)ch * plane + p] = go[(size_t)(CF + 3 + ch) * plane + p] + dr[ch];
+                for (int ch = 0; ch < 3; ++ch) d_render[(size_t)ch * plane + p] = go[(size_t)(PV_F + 3 + ch) * plane + p] + dr[ch];
             }
             if (d_warped)
                 for (int k = L; k < S; ++k)
@@ -334,18 +260,18 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
         double* const mine = buf + wave * CAGG_WAVE_WORDS;          // [dW2 (32 x 32) | dW1, db1 (32 x 8) | db2 by half (2 x 32)]
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mine[cagg_ch(r, h) * CF + c] = acc2d[r];
+        for (int r = 0; r < 16; ++r) mine[pv_ch(r, h) * PV_F + c] = acc2d[r];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) mine[CF * CF + r1 * CINP + c0 + m] = acc1[m];
-        mine[CF * CF + CF * CINP + h * CF + c] = accb;
+        for (int m = 0; m < 4; ++m) mine[PV_F * PV_F + r1 * PV_INP + c0 + m] = acc1[m];
+        mine[PV_F * PV_F + PV_F * PV_INP + h * PV_F + c] = accb;
         __syncthreads();
         for (int e = threadIdx.x; e < CAGG_PARTIAL; e += CT) {          // the waves in order
             double sum = 0.0;
             for (int w = 0; w < CWAVES; ++w) {
                 const double* const src = buf + w * CAGG_WAVE_WORDS;
-                if (e < CF * CINP) sum += src[CF * CF + e];
-                else if (e < CF * CINP + CF * CF) sum += src[e - CF * CINP];
-                else sum += src[CF * CF + CF * CINP + (e - CF * CINP - CF * CF)] + src[CF * CF + CF * CINP + CF + (e - CF * CINP - CF * CF)];
+                if (e < PV_F * PV_INP) sum += src[PV_F * PV_F + e];
+                else if (e < PV_F * PV_INP + PV_F * PV_F) sum += src[e - PV_F * PV_INP];
+                else sum += src[PV_F * PV_F + PV_F * PV_INP + (e - PV_F * PV_INP - PV_F * PV_F)] + src[PV_F * PV_F + PV_F * PV_INP + PV_F + (e - PV_F * PV_INP - PV_F * PV_F)];
             }
             partials[(size_t)blockIdx.x * CAGG_PARTIAL + e] = sum;
         }
@@ -367,13 +293,13 @@ __global__ void __launch_bounds__(CT) cagg_final_kernel(const double* __restrict
         double t = s_sum[0][el];
         for (int k = 1; k < FIN_SERIES; ++k) t += s_sum[k][el];
         const float v = (float)t;
-        if (e < CF * CINP) {
+        if (e < PV_F * PV_INP) {
             const int i = e >> 3, c = e & 7;
-            if (c < CIN) { if (d_w1) d_w1[i * CIN + c] = v; }
+            if (c < PV_IN) { if (d_w1) d_w1[i * PV_IN + c] = v; }
             else if (d_b1) d_b1[i] = v;
-        } else if (e < CF * CINP + CF * CF) {
-            if (d_w2) d_w2[e - CF * CINP] = v;
-        } else if (d_b2) d_b2[e - CF * CINP - CF * CF] = v;
+        } else if (e < PV_F * PV_INP + PV_F * PV_F) {
+            if (d_w2) d_w2[e - PV_F * PV_INP] = v;
+        } else if (d_b2) d_b2[e - PV_F * PV_INP - PV_F * PV_F] = v;
     }
 }
 

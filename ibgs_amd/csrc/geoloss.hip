@@ -4,18 +4,17 @@
 // frame forward and one backward, and the normal-consistency term as one pass over its six planes.  Neither waits for the device: the number of valid
 // pixels Nv, on which the reference branches on the host, is formed, tested and divided by on the device.
 //
-// The window weights, the two filter passes and the per-pixel forms are COPIES of ssim.hip's (DESIGN.md section 13 says why the code is doubled);
-// tests/test_geoloss_host.py requires the weight literals of the two files to be the same text.  Like ssim.hip this unit is compiled without
-// -ffp-contract=off: the filter passes are fma chains, the per-pixel expressions say `fp contract(off)` themselves.
+// The window weights, the two filter passes over a tile and the per-pixel forms are shared/ssim_window.h's, the ones ssim.hip runs (DESIGN.md section 13 says
+// where that header lives and why); what their bits rest on is stated there.  Like ssim.hip this unit is compiled without -ffp-contract=off.
 //
 // CONTRACT (photometric)
 //   valid      valid[s, p] = (((f0 + f1) + f2) + f3) > 0 on the four feature planes of source s, float32, in that order (cam_feat is signed).
 //   masked     valid ? warped : gt, formed on the way into LDS: never in HBM.
-//   m          the map of (gt, masked[s]): ssim.hip's CONTRACT with x = gt, y = masked.
+//   m          the map of (gt, masked[s]): shared/ssim_window.h's with x = gt, y = masked.
 //   sums       per workgroup (one tile of one source) in f64: sum valid (1 - (m0 + m1 + m2) / 3), sum valid (|d0| + |d1| + |d2|) / 3 with d = gt - warped in
 //              f32, and sum valid.  geoloss_photo_final_kernel: thread t adds the partials t, t + 1024, .. in that order, block_reduce adds the threads; then
 //              Nv == 0 ? 0 : photo_weight ((1 - w_s) l1 / Nv + w_s ss / Nv).  No float atomics.
-//   derivative planes (when a gradient will be asked for): dm/dv, dm/dq, dm/dr -- ssim_pixel with the roles of (u, p) and (v, q) swapped -- times valid.
+//   derivative planes (when a gradient will be asked for): dm/dv, dm/dq, dm/dr -- ssimw_pixel with the roles of (u, p) and (v, q) swapped -- times valid.
 //   backward   grad_warped = valid ? k_s combine(w*D0, w*D1, w*D2; warped, gt) + k_1 sign(warped - gt) : 0, with k_s = -go w_p w_s / (3 Nv) and
 //              k_1 = go w_p (1 - w_s) / (3 Nv) formed in f64 from the device scalars go and Nv (both 0 when Nv == 0), sign(0) = 0.  The filter passes are
 //              f32 fma chains as in ssim.hip; from their results on the expression is evaluated in f64 and rounded once (on a frame of a few pixels the
@@ -28,87 +27,21 @@
 //
 // KERNELS
 //   geoloss_photo_fwd_kernel     one workgroup of 256 threads per 32 x 32 tile and source.  The validity of the 42 x 42 staged texels once; then per channel
-//                                ssim.hip's three steps (stage with halo, row pass, column pass) and the per-pixel forms.  44 KB of LDS.
+//                                ssim.hip's three steps (stage with halo, row pass, column pass) and the per-pixel form.  44 KB of LDS.
 //   geoloss_photo_bwd_kernel     the same tiling over the three derivative planes of each channel; 39 KB of LDS.
 //   geoloss_photo_final_kernel, geoloss_normal_kernel, geoloss_normal_final_kernel, geoloss_rescale_kernel
 // What bounds them: DESIGN.md section 13.
 #include "common.h"
 #include "block_ops.h"
+#include "shared/ssim_window.h"
 #include "../../include/ibgs_geo_loss.h"
 
 namespace ibgs {
 
-constexpr int GT_ = 256;                             // threads per workgroup of the two image kernels
 constexpr int GF = 1024;                             // threads of the final kernels' one workgroup
-constexpr int GEO_TH = 32, GEO_TW = 32;              // the tile of one workgroup
-constexpr int GTAPS = 11, GHALO = GTAPS / 2;
-constexpr int GSH = GEO_TH + 2 * GHALO, GSW = GEO_TW + 2 * GHALO;          // the staged tile
-constexpr int GSS = 45;                              // its row stride in LDS: 1 mod 4 (ssim.hip)
-constexpr int GOPT = 4;                              // outputs per thread along the filter direction
-constexpr int GNV = GOPT + GTAPS - 1;                // values those outputs read
-constexpr int GHGROUPS = GEO_TW / GOPT;
 constexpr int NC_THREADS = 256, NC_MAX_BLOCKS = 1024;
-static_assert(GEO_TW == 32 && (GT_ / GEO_TW) * GOPT == GEO_TH, "the vertical pass: a thread per column and group of GOPT rows");
-static_assert(GSS >= GSW && GSS % 4 == 1, "row stride");
 
-// gaussian(11, 1.5) of the reference (loss_utils.py:24-26) in float32: taps 0 .. 5 (the same text as ssim.hip's: tests/test_geoloss_host.py)
-constexpr float GEO_W[6] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f};
-constexpr float GEO_C1 = 0.01f * 0.01f, GEO_C2 = 0.03f * 0.03f;
-
-__device__ __forceinline__ constexpr float geo_w(int k) { return GEO_W[k <= GHALO ? k : GTAPS - 1 - k]; }
-
-// o[i] = sum_k w[k] v[i + k], k ascending, one fma per tap
-__device__ __forceinline__ void geo_conv(const float (&v)[GNV], float (&o)[GOPT])
-{
-#pragma unroll
-    for (int i = 0; i < GOPT; ++i) {
-        float a = geo_w(0) * v[i];
-#pragma unroll
-        for (int k = 1; k < GTAPS; ++k) a = fmaf(geo_w(k), v[i + k], a);
-        o[i] = a;
-    }
-}
-
-__device__ __forceinline__ void geo_hpass_row(const float* __restrict__ staged, float* __restrict__ out, int r, int c0)
-{
-    float v[GNV], o[GOPT];
-#pragma unroll
-    for (int j = 0; j < GNV; ++j) v[j] = staged[r * GSS + c0 + j];
-    geo_conv(v, o);
-    *reinterpret_cast<float4*>(out + r * GEO_TW + c0) = make_float4(o[0], o[1], o[2], o[3]);
-}
-
-__device__ __forceinline__ void geo_vpass_col(const float* __restrict__ hq, int r0, int col, float (&o)[GOPT])
-{
-    float v[GNV];
-#pragma unroll
-    for (int j = 0; j < GNV; ++j) v[j] = hq[(r0 + j) * GEO_TW + col];
-    geo_conv(v, o);
-}
-
-struct GeoPixel { float m, du, dp, dr; };
-
-// One rounding per operation (ssim.hip, CONTRACT): m is bit-symmetric in (u, p) <-> (v, q) and exactly 1 where the two images agree over the window.
-__device__ __forceinline__ GeoPixel geo_pixel(float u, float v, float p, float q, float r, bool derivatives)
-{
-#pragma clang fp contract(off)
-    GeoPixel o;
-    const float uv = u * v, uu = u * u, vv = v * v;
-    const float s1 = p - uu, s2 = q - vv, s12 = r - uv;
-    const float A = 2.0f * uv + GEO_C1, B = 2.0f * s12 + GEO_C2, C = (uu + vv) + GEO_C1, D = (s1 + s2) + GEO_C2;
-    const float CD = C * D;
-    o.m = (A * B) / CD;
-    o.du = o.dp = o.dr = 0.0f;
-    if (derivatives) {
-        const float t = 2.0f / CD;
-        o.dr = t * A;
-        o.dp = (-0.5f * o.dr) * (B / D);
-        o.du = t * (v * (B - A) + (u * o.m) * (C - D));
-    }
-    return o;
-}
-
-// ssim.hip's ssim_combine, evaluated in f64 from the f32 filtered planes: both products are exact there, so where x == y and cb == -cc / 2 (the two images agree
+// ssimw_combine, evaluated in f64 from the f32 filtered planes: both products are exact there, so where x == y and cb == -cc / 2 (the two images agree
 // over the window) the sum is exactly ca, as in the f32 form; what the f32 form rounds five times is rounded once, by the caller
 __device__ __forceinline__ double geo_combine(float ca, float cb, float cc, float x, float y)
 {
@@ -123,48 +56,36 @@ __device__ __forceinline__ bool geo_valid(const float* __restrict__ feat, size_t
     return (((feat[o] + feat[plane + o]) + feat[2 * plane + o]) + feat[3 * plane + o]) > 0.0f;
 }
 
-struct GeoTile {
-    int src, ty0, tx0;
-    __device__ __forceinline__ GeoTile(int tiles, int tiles_x)
-    {
-        src = (int)(blockIdx.x / (unsigned)tiles);
-        const int tile = (int)(blockIdx.x - (unsigned)src * (unsigned)tiles);
-        const int ty = tile / tiles_x;
-        ty0 = ty * GEO_TH;
-        tx0 = (tile - ty * tiles_x) * GEO_TW;
-    }
-};
-
 // gt: 3 planes; warped: S x 3 planes; feat: S x 4 planes; dplanes (or null): 3 x S x 3 planes; partials: (S x tiles) x 3
-__global__ void __launch_bounds__(GT_) geoloss_photo_fwd_kernel(const float* __restrict__ gt, const float* __restrict__ warped, const float* __restrict__ feat, int H, int W,
-                                                                int tiles_x, int tiles, size_t total, float* __restrict__ dplanes, double* __restrict__ partials)
+__global__ void __launch_bounds__(SSIMW_THREADS) geoloss_photo_fwd_kernel(const float* __restrict__ gt, const float* __restrict__ warped, const float* __restrict__ feat, int H, int W,
+                                                                          int tiles_x, int tiles, size_t total, float* __restrict__ dplanes, double* __restrict__ partials)
 {
-    __shared__ float sx[GSH * GSS], sy[GSH * GSS];
-    __shared__ __attribute__((aligned(16))) float hq[5][GSH * GEO_TW];
-    __shared__ unsigned char sv[GSH * GSW];
-    const GeoTile t(tiles, tiles_x);
+    __shared__ float sx[SSIMW_SH * SSIMW_SS], sy[SSIMW_SH * SSIMW_SS];
+    __shared__ __attribute__((aligned(16))) float hq[5][SSIMW_SH * SSIMW_TW];
+    __shared__ unsigned char sv[SSIMW_SH * SSIMW_SW];
+    const SsimwTile t(tiles, tiles_x);
     const size_t plane = (size_t)H * (size_t)W;
-    const float* const fs = feat + (size_t)t.src * 4 * plane;
+    const float* const fs = feat + (size_t)t.outer * 4 * plane;
 
-    for (int i = threadIdx.x; i < GSH * GSW; i += GT_) {
-        const int r = i / GSW, c = i - r * GSW;
-        const int gy = t.ty0 - GHALO + r, gx = t.tx0 - GHALO + c;
+    for (int i = threadIdx.x; i < SSIMW_SH * SSIMW_SW; i += SSIMW_THREADS) {
+        const int r = i / SSIMW_SW, c = i - r * SSIMW_SW;
+        const int gy = t.ty0 - SSIMW_HALO + r, gx = t.tx0 - SSIMW_HALO + c;
         bool v = false;
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = geo_valid(fs, plane, (size_t)gy * (size_t)W + (size_t)gx);
         sv[i] = v ? 1 : 0;
     }
     __syncthreads();
 
-    const int col = threadIdx.x & (GEO_TW - 1), r0 = (int)(threadIdx.x / GEO_TW) * GOPT;
+    const int col = threadIdx.x & (SSIMW_TW - 1), r0 = (int)(threadIdx.x / SSIMW_TW) * SSIMW_OPT;
     const int gx = t.tx0 + col;
-    double msum[GOPT] = {0.0, 0.0, 0.0, 0.0}, dsum[GOPT] = {0.0, 0.0, 0.0, 0.0};
+    double msum[SSIMW_OPT] = {0.0, 0.0, 0.0, 0.0}, dsum[SSIMW_OPT] = {0.0, 0.0, 0.0, 0.0};
 
     for (int ch = 0; ch < 3; ++ch) {
         const float* const xg = gt + (size_t)ch * plane;
-        const float* const yw = warped + ((size_t)t.src * 3 + ch) * plane;
-        for (int i = threadIdx.x; i < GSH * GSW; i += GT_) {
-            const int r = i / GSW, c = i - r * GSW;
-            const int gy = t.ty0 - GHALO + r, gxx = t.tx0 - GHALO + c;
+        const float* const yw = warped + ((size_t)t.outer * 3 + ch) * plane;
+        for (int i = threadIdx.x; i < SSIMW_SH * SSIMW_SW; i += SSIMW_THREADS) {
+            const int r = i / SSIMW_SW, c = i - r * SSIMW_SW;
+            const int gy = t.ty0 - SSIMW_HALO + r, gxx = t.tx0 - SSIMW_HALO + c;
             float a = 0.0f, b = 0.0f;
             if (gy >= 0 && gy < H && gxx >= 0 && gxx < W) {
                 const size_t o = (size_t)gy * (size_t)W + (size_t)gxx;
@@ -172,53 +93,34 @@ __global__ void __launch_bounds__(GT_) geoloss_photo_fwd_kernel(const float* __r
                 b = a;
                 if (sv[i]) b = yw[o];          // the warped colour is read at valid texels only
             }
-            sx[r * GSS + c] = a;
-            sy[r * GSS + c] = b;
+            sx[r * SSIMW_SS + c] = a;
+            sy[r * SSIMW_SS + c] = b;
         }
         __syncthreads();
 
-        for (int task = threadIdx.x; task < GSH * GHGROUPS; task += GT_) {
-            const int r = task / GHGROUPS, c0 = (task - r * GHGROUPS) * GOPT;
-            float xv[GNV], yv[GNV], tv[GNV], o[GOPT];
-#pragma unroll
-            for (int j = 0; j < GNV; ++j) { xv[j] = sx[r * GSS + c0 + j]; yv[j] = sy[r * GSS + c0 + j]; }
-            float* const dst = &hq[0][r * GEO_TW + c0];
-            geo_conv(xv, o);
-            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-            geo_conv(yv, o);
-            *reinterpret_cast<float4*>(dst + GSH * GEO_TW) = make_float4(o[0], o[1], o[2], o[3]);
-#pragma unroll
-            for (int j = 0; j < GNV; ++j) tv[j] = xv[j] * xv[j];
-            geo_conv(tv, o);
-            *reinterpret_cast<float4*>(dst + 2 * GSH * GEO_TW) = make_float4(o[0], o[1], o[2], o[3]);
-#pragma unroll
-            for (int j = 0; j < GNV; ++j) tv[j] = yv[j] * yv[j];
-            geo_conv(tv, o);
-            *reinterpret_cast<float4*>(dst + 3 * GSH * GEO_TW) = make_float4(o[0], o[1], o[2], o[3]);
-#pragma unroll
-            for (int j = 0; j < GNV; ++j) tv[j] = xv[j] * yv[j];
-            geo_conv(tv, o);
-            *reinterpret_cast<float4*>(dst + 4 * GSH * GEO_TW) = make_float4(o[0], o[1], o[2], o[3]);
+        for (int task = threadIdx.x; task < SSIMW_SH * SSIMW_HGROUPS; task += SSIMW_THREADS) {
+            const int r = task / SSIMW_HGROUPS, c0 = (task - r * SSIMW_HGROUPS) * SSIMW_OPT;
+            ssimw_hpass_row5(sx, sy, hq, r, c0);
         }
         __syncthreads();
 
-        float f[5][GOPT];
+        float f[5][SSIMW_OPT];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) geo_vpass_col(hq[k], r0, col, f[k]);
+        for (int k = 0; k < 5; ++k) ssimw_vpass_col(hq[k], r0, col, f[k]);
 #pragma unroll
-        for (int i = 0; i < GOPT; ++i) {
+        for (int i = 0; i < SSIMW_OPT; ++i) {
             const int gy = t.ty0 + r0 + i;
             if (gy < H && gx < W) {
                 // with respect to the masked side: the roles of (u, p) and (v, q) swapped; m itself does not notice
-                const GeoPixel px = geo_pixel(f[1][i], f[0][i], f[3][i], f[2][i], f[4][i], dplanes != nullptr);
-                const bool v = sv[(r0 + i + GHALO) * GSW + col + GHALO] != 0;
+                const SsimwPixel px = ssimw_pixel(f[1][i], f[0][i], f[3][i], f[2][i], f[4][i], dplanes != nullptr);
+                const bool v = sv[(r0 + i + SSIMW_HALO) * SSIMW_SW + col + SSIMW_HALO] != 0;
                 if (dplanes) {
-                    const size_t o = ((size_t)t.src * 3 + ch) * plane + (size_t)gy * (size_t)W + (size_t)gx;
+                    const size_t o = ((size_t)t.outer * 3 + ch) * plane + (size_t)gy * (size_t)W + (size_t)gx;
                     dplanes[o] = v ? px.du : 0.0f;
                     dplanes[total + o] = v ? px.dp : 0.0f;
                     dplanes[2 * total + o] = v ? px.dr : 0.0f;
                 }
-                const float d = sx[(r0 + i + GHALO) * GSS + col + GHALO] - sy[(r0 + i + GHALO) * GSS + col + GHALO];
+                const float d = sx[(r0 + i + SSIMW_HALO) * SSIMW_SS + col + SSIMW_HALO] - sy[(r0 + i + SSIMW_HALO) * SSIMW_SS + col + SSIMW_HALO];
                 msum[i] += (double)px.m;
                 dsum[i] += (double)fabsf(d);
             }
@@ -228,15 +130,15 @@ __global__ void __launch_bounds__(GT_) geoloss_photo_fwd_kernel(const float* __r
 
     double acc[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int i = 0; i < GOPT; ++i) {
+    for (int i = 0; i < SSIMW_OPT; ++i) {
         const int gy = t.ty0 + r0 + i;
-        if (gy < H && gx < W && sv[(r0 + i + GHALO) * GSW + col + GHALO]) {
+        if (gy < H && gx < W && sv[(r0 + i + SSIMW_HALO) * SSIMW_SW + col + SSIMW_HALO]) {
             acc[0] += 1.0 - msum[i] / 3.0;
             acc[1] += dsum[i] / 3.0;
             acc[2] += 1.0;
         }
     }
-    block_reduce<GT_, 3>(acc, partials + (size_t)blockIdx.x * 3, op_add());
+    block_reduce<SSIMW_THREADS, 3>(acc, partials + (size_t)blockIdx.x * 3, op_add());
 }
 
 // One workgroup.  Thread t adds the partials t, t + GF, .. in that order; block_reduce adds the threads; thread 0 writes the loss and Nv.
@@ -260,23 +162,23 @@ __global__ void __launch_bounds__(GF) geoloss_photo_final_kernel(const double* _
 }
 
 // grid: S_total x tiles; the sources from S on are only zeroed
-__global__ void __launch_bounds__(GT_) geoloss_photo_bwd_kernel(const float* __restrict__ gt, const float* __restrict__ warped, const float* __restrict__ feat,
-                                                                const float* __restrict__ dplanes, size_t total, const double* __restrict__ nv_dev,
-                                                                const float* __restrict__ go_dev, double photo_weight, double w_s, int S, int H, int W, int tiles_x, int tiles,
-                                                                float* __restrict__ grad)
+__global__ void __launch_bounds__(SSIMW_THREADS) geoloss_photo_bwd_kernel(const float* __restrict__ gt, const float* __restrict__ warped, const float* __restrict__ feat,
+                                                                          const float* __restrict__ dplanes, size_t total, const double* __restrict__ nv_dev,
+                                                                          const float* __restrict__ go_dev, double photo_weight, double w_s, int S, int H, int W, int tiles_x, int tiles,
+                                                                          float* __restrict__ grad)
 {
-    __shared__ float sd[3][GSH * GSS];
-    __shared__ __attribute__((aligned(16))) float hq[3][GSH * GEO_TW];
-    const GeoTile t(tiles, tiles_x);
+    __shared__ float sd[3][SSIMW_SH * SSIMW_SS];
+    __shared__ __attribute__((aligned(16))) float hq[3][SSIMW_SH * SSIMW_TW];
+    const SsimwTile t(tiles, tiles_x);
     const size_t plane = (size_t)H * (size_t)W;
-    const int col = threadIdx.x & (GEO_TW - 1), r0 = (int)(threadIdx.x / GEO_TW) * GOPT;
+    const int col = threadIdx.x & (SSIMW_TW - 1), r0 = (int)(threadIdx.x / SSIMW_TW) * SSIMW_OPT;
     const int gx = t.tx0 + col;
 
-    if (t.src >= S) {          // (wave-uniform) never read: their gradient is zero
+    if (t.outer >= S) {          // (wave-uniform) never read: their gradient is zero
         for (int ch = 0; ch < 3; ++ch)
-            for (int i = 0; i < GOPT; ++i) {
+            for (int i = 0; i < SSIMW_OPT; ++i) {
                 const int gy = t.ty0 + r0 + i;
-                if (gy < H && gx < W) grad[((size_t)t.src * 3 + ch) * plane + (size_t)gy * (size_t)W + (size_t)gx] = 0.0f;
+                if (gy < H && gx < W) grad[((size_t)t.outer * 3 + ch) * plane + (size_t)gy * (size_t)W + (size_t)gx] = 0.0f;
             }
         return;
     }
@@ -284,19 +186,19 @@ __global__ void __launch_bounds__(GT_) geoloss_photo_bwd_kernel(const float* __r
     const double nv = *nv_dev, go = (double)*go_dev;
     const double k_s = nv > 0.0 ? -go * photo_weight * w_s / (3.0 * nv) : 0.0;
     const double k_1 = nv > 0.0 ? go * photo_weight * (1.0 - w_s) / (3.0 * nv) : 0.0;
-    const float* const fs = feat + (size_t)t.src * 4 * plane;
-    bool valid[GOPT];
+    const float* const fs = feat + (size_t)t.outer * 4 * plane;
+    bool valid[SSIMW_OPT];
 #pragma unroll
-    for (int i = 0; i < GOPT; ++i) {
+    for (int i = 0; i < SSIMW_OPT; ++i) {
         const int gy = t.ty0 + r0 + i;
         valid[i] = gy < H && gx < W && geo_valid(fs, plane, (size_t)gy * (size_t)W + (size_t)gx);
     }
 
     for (int ch = 0; ch < 3; ++ch) {
-        const size_t base = ((size_t)t.src * 3 + ch) * plane;
-        for (int i = threadIdx.x; i < GSH * GSW; i += GT_) {
-            const int r = i / GSW, c = i - r * GSW;
-            const int gy = t.ty0 - GHALO + r, gxx = t.tx0 - GHALO + c;
+        const size_t base = ((size_t)t.outer * 3 + ch) * plane;
+        for (int i = threadIdx.x; i < SSIMW_SH * SSIMW_SW; i += SSIMW_THREADS) {
+            const int r = i / SSIMW_SW, c = i - r * SSIMW_SW;
+            const int gy = t.ty0 - SSIMW_HALO + r, gxx = t.tx0 - SSIMW_HALO + c;
             float a = 0.0f, b = 0.0f, d = 0.0f;
             if (gy >= 0 && gy < H && gxx >= 0 && gxx < W) {
                 const size_t o = base + (size_t)gy * (size_t)W + (size_t)gxx;
@@ -304,24 +206,24 @@ __global__ void __launch_bounds__(GT_) geoloss_photo_bwd_kernel(const float* __r
                 b = dplanes[total + o];
                 d = dplanes[2 * total + o];
             }
-            sd[0][r * GSS + c] = a;
-            sd[1][r * GSS + c] = b;
-            sd[2][r * GSS + c] = d;
+            sd[0][r * SSIMW_SS + c] = a;
+            sd[1][r * SSIMW_SS + c] = b;
+            sd[2][r * SSIMW_SS + c] = d;
         }
         __syncthreads();
 
-        for (int task = threadIdx.x; task < GSH * GHGROUPS; task += GT_) {
-            const int r = task / GHGROUPS, c0 = (task - r * GHGROUPS) * GOPT;
+        for (int task = threadIdx.x; task < SSIMW_SH * SSIMW_HGROUPS; task += SSIMW_THREADS) {
+            const int r = task / SSIMW_HGROUPS, c0 = (task - r * SSIMW_HGROUPS) * SSIMW_OPT;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) geo_hpass_row(sd[k], hq[k], r, c0);
+            for (int k = 0; k < 3; ++k) ssimw_hpass_row(sd[k], hq[k], r, c0);
         }
         __syncthreads();
 
-        float f[3][GOPT];
+        float f[3][SSIMW_OPT];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) geo_vpass_col(hq[k], r0, col, f[k]);
+        for (int k = 0; k < 3; ++k) ssimw_vpass_col(hq[k], r0, col, f[k]);
 #pragma unroll
-        for (int i = 0; i < GOPT; ++i) {
+        for (int i = 0; i < SSIMW_OPT; ++i) {
             const int gy = t.ty0 + r0 + i;
             if (gy < H && gx < W) {
                 const size_t o = (size_t)gy * (size_t)W + (size_t)gx;
@@ -396,7 +298,7 @@ static bool geo_shape_ok(const char* who, int64_t sources, int64_t H, int64_t W,
                            IBGS_GEOLOSS_MAX_SRC, IBGS_GEOLOSS_MAX_SIDE);
         return false;
     }
-    const size_t tx = ((size_t)W + GEO_TW - 1) / GEO_TW, ty = ((size_t)H + GEO_TH - 1) / GEO_TH;
+    const size_t tx = ((size_t)W + SSIMW_TW - 1) / SSIMW_TW, ty = ((size_t)H + SSIMW_TH - 1) / SSIMW_TH;
     s->tiles = tx * ty;          // <= 2048^2: sources x tiles < 2^31
     s->tiles_x = (int)tx;
     s->plane = (size_t)H * (size_t)W;
@@ -436,8 +338,8 @@ size_t ibgs_geoloss_required_scratch(int64_t sources, int64_t H, int64_t W)
 
 void ibgs_geoloss_tile(int32_t* th, int32_t* tw)
 {
-    if (th) *th = GEO_TH;
-    if (tw) *tw = GEO_TW;
+    if (th) *th = SSIMW_TH;
+    if (tw) *tw = SSIMW_TW;
 }
 
 int32_t ibgs_geoloss_photo_forward(void* stream, int32_t S, int32_t H, int32_t W, const float* gt, const float* warped, const float* cam_feat, double photo_weight,
@@ -453,7 +355,7 @@ int32_t ibgs_geoloss_photo_forward(void* stream, int32_t S, int32_t H, int32_t W
     if (!arena_ok("geoloss_photo_forward", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t groups = (size_t)S * s.tiles;
-    hipLaunchKernelGGL(geoloss_photo_fwd_kernel, dim3((unsigned)groups), dim3(GT_), 0, st, gt, warped, cam_feat, H, W, s.tiles_x, (int)s.tiles, (size_t)S * 3 * s.plane,
+    hipLaunchKernelGGL(geoloss_photo_fwd_kernel, dim3((unsigned)groups), dim3(SSIMW_THREADS), 0, st, gt, warped, cam_feat, H, W, s.tiles_x, (int)s.tiles, (size_t)S * 3 * s.plane,
                        dplanes_out, sc.photo);
     IBGS_HIP(hipGetLastError());
     hipLaunchKernelGGL(geoloss_photo_final_kernel, dim3(1), dim3(GF), 0, st, sc.photo, (int)groups, photo_weight, photo_ssim_weight, loss_out, nv_out);
@@ -469,7 +371,7 @@ int32_t ibgs_geoloss_photo_backward(void* stream, int32_t S, int32_t S_total, in
     if (S > S_total) { set_error("geoloss_photo_backward: %d sources read of %d out of range", S, S_total); return -IBGS_ERR_INVALID; }
     if (!gt || !warped || !cam_feat || !dplanes || !nv || !grad_out || !grad_warped) { set_error("geoloss_photo_backward: null array"); return -IBGS_ERR_INVALID; }
     if (!geo_weight_ok(photo_weight) || !geo_weight_ok(photo_ssim_weight)) { set_error("geoloss_photo_backward: the weights must be finite"); return -IBGS_ERR_INVALID; }
-    hipLaunchKernelGGL(geoloss_photo_bwd_kernel, dim3((unsigned)((size_t)S_total * s.tiles)), dim3(GT_), 0, reinterpret_cast<hipStream_t>(stream), gt, warped, cam_feat, dplanes,
+    hipLaunchKernelGGL(geoloss_photo_bwd_kernel, dim3((unsigned)((size_t)S_total * s.tiles)), dim3(SSIMW_THREADS), 0, reinterpret_cast<hipStream_t>(stream), gt, warped, cam_feat, dplanes,
                        (size_t)S * 3 * s.plane, nv, grad_out, photo_weight, photo_ssim_weight, S, H, W, s.tiles_x, (int)s.tiles, grad_warped);
     IBGS_HIP(hipGetLastError());
     return 0;

@@ -11,9 +11,8 @@
 //              Linear + ReLU layers, the mean or maximum over k < levels, the normalised ray and the colour.
 //   upsample   residual_out = value of residual_r; image_pred_out = render_scale * render + residual_out (product and sum rounded one after the other).
 //
-// THE 32 x 32 PRODUCTS are coloragg.hip's: v_mfma_f32_32x32x2_f32, a wave holds 32 pixels, lane l = (pixel l & 31, half l >> 5), register r of a 16-register
-// tile belongs to channel ch(r, h) = (r & 3) + 8 (r >> 2) + 4 h, so a layer's result is the next product's B operand as it stands.  This unit carries its
-// own copy of that chain (as geoloss.hip carries its SSIM passes): no header is shared, coloragg.hip is not touched.
+// THE SLOT AND THE 32 x 32 PRODUCTS are shared/pv_mlp.h's, the chain coloragg.hip runs: the lane and register map and what the bits rest on are stated there.
+// Of what it hands back this unit uses the slot's row (blended over the four taps before the layers) and h2.
 //
 // KERNELS
 //   rsz_features_kernel  256 threads = 4 waves of 32 reduced pixels, one block of pixels per wave (the grid is not capped); per slot 4 x 7 gathered loads,
@@ -22,75 +21,17 @@
 //                        16-byte stores of both outputs where the row allows (W % 4 == 0, aligned pointers), 4-byte ones otherwise.
 // What bounds them: DESIGN.md section 19.
 #include "common.h"
+#include "shared/pv_mlp.h"
 #include "../../include/ibgs_resample.h"
 
 namespace ibgs {
-
-typedef float rsz_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int RT = 256;                              // threads per workgroup
 constexpr int RWAVES = RT / 64;
 constexpr int RB = 32;                               // reduced pixels per wave
 constexpr int RCHUNK = RWAVES * RB;                  // reduced pixels per workgroup
-constexpr int RF = IBGS_RSZ_FEATURES;                // feature width
-constexpr int RIN = 7, RINP = 8;                     // inputs of the first layer, and the row they are kept in
 constexpr int RQ = 4;                                // output columns per thread of the upsampling
-static_assert(RF == 32 && RB == 32, "the lane maps below");
-
-// the channel of register r of a tile in half h
-__device__ __forceinline__ constexpr int rsz_ch(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ rsz_f32x16 rsz_mfma(float a, float b, rsz_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-// A lane's share of the weights, loaded once: the A operands of the two layers (row = this lane's l & 31, k-step kk = the inputs 2 kk + h of the first
-// layer and the channels ch(kk, h) of the second).
-struct RszFrag {
-    float a1[4], a2[16];
-    __device__ __forceinline__ RszFrag(const float* __restrict__ w1, const float* __restrict__ w2, int row, int h)
-    {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) a1[kk] = 2 * kk + h < RIN ? w1[row * RIN + 2 * kk + h] : 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) a2[kk] = w2[row * RF + rsz_ch(kk, h)];
-    }
-};
-
-// The biases as the tiles the chains start from: [layer][half][register], read from LDS as broadcasts.  Ends with a barrier.
-struct __attribute__((aligned(16))) RszBias { float t[2][2][16]; };
-__device__ __forceinline__ void rsz_stage_bias(RszBias& s, const float* __restrict__ b1, const float* __restrict__ b2)
-{
-    if (threadIdx.x < 64) {
-        const int layer = threadIdx.x >> 5, hh = (threadIdx.x >> 4) & 1, r = threadIdx.x & 15;
-        s.t[layer][hh][r] = (layer ? b2 : b1)[rsz_ch(r, hh)];
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ rsz_f32x16 rsz_bias_tile(const RszBias& s, int layer, int h)
-{
-    rsz_f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(&s.t[layer][h][i]);
-        z[i] = v.x; z[i + 1] = v.y; z[i + 2] = v.z; z[i + 3] = v.w;
-    }
-    return z;
-}
-
-// both layers of the lane's pixel: its 16 channels of h2
-__device__ __forceinline__ rsz_f32x16 rsz_mlp(const RszFrag& f, const RszBias& bias, const float (&x)[RINP], int h)
-{
-    rsz_f32x16 z = rsz_bias_tile(bias, 0, h), h1;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) z = rsz_mfma(f.a1[kk], h ? x[2 * kk + 1] : x[2 * kk], z);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) h1[r] = z[r] > 0.0f ? z[r] : 0.0f;
-    z = rsz_bias_tile(bias, 1, h);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) z = rsz_mfma(f.a2[kk], h1[kk], z);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = z[r] > 0.0f ? z[r] : 0.0f;
-    return z;
-}
+static_assert(PV_F == IBGS_RSZ_FEATURES && RB == PV_F, "the lane maps below");
 
 // One axis of the coordinate rule: the two taps of output index i of an `out`-long axis made of an `in`-long one, t and 1 - t.  (i (in - 1) < 2^32: both
 // sides are at most 65536.)
@@ -113,17 +54,6 @@ __device__ __forceinline__ float rsz_blend(float a, float b, float c, float d, c
     return fmaf(ty.t, bottom, ty.u * top);
 }
 
-// the features of slot k at the full-resolution pixel p (ibgs_color_agg.h): the mask is this pixel's own
-__device__ __forceinline__ void rsz_slot(const float* __restrict__ warped, const float* __restrict__ feat, const float (&r)[3], size_t plane, size_t p, int k, float (&x)[RIN])
-{
-#pragma clang fp contract(off)
-    const float* const f = feat + (size_t)k * 4 * plane + p;
-    const float* const w = warped + (size_t)k * 3 * plane + p;
-    x[3] = f[0]; x[4] = f[plane]; x[5] = f[2 * plane]; x[6] = f[3 * plane];
-    const float v = (((x[3] + x[4]) + x[5]) + x[6]) > 0.0f ? 1.0f : 0.0f;          // the sum's order is the contract
-    x[0] = (w[0] - r[0]) * v; x[1] = (w[plane] - r[1]) * v; x[2] = (w[2 * plane] - r[2]) * v;
-}
-
 __device__ __forceinline__ float rsz_norm3(float a, float b, float c)
 {
 #pragma clang fp contract(off)
@@ -138,9 +68,9 @@ __global__ void __launch_bounds__(RT) rsz_features_kernel(const float* __restric
                                                           uint32_t W, uint32_t Hr, uint32_t Wr, float* __restrict__ out)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const RszFrag f(w1, w2, c, h);
-    __shared__ RszBias bias;
-    rsz_stage_bias(bias, b1, b2);
+    const PvFrag f(w1, w2, c, h);
+    __shared__ PvBias bias;
+    pv_stage_bias(bias, b1, b2);
     const int lv = *levels;          // (wave-uniform)
     const int L = lv < 0 ? 0 : (lv > S ? S : lv);
     const size_t plane = (size_t)H * W, plane_r = (size_t)Hr * Wr;
@@ -156,17 +86,18 @@ __global__ void __launch_bounds__(RT) rsz_features_kernel(const float* __restric
     for (int n = 0; n < 4; ++n) {
         r[n][0] = render[p[n]]; r[n][1] = render[plane + p[n]]; r[n][2] = render[2 * plane + p[n]];
     }
-    rsz_f32x16 agg;
+    pv_f32x16 agg;
 #pragma unroll
     for (int m = 0; m < 16; ++m) agg[m] = 0.0f;
     for (int k = 0; k < L; ++k) {
-        float xf[4][RIN], x[RINP];
+        float xf[4][PV_INP], x[PV_INP];
 #pragma unroll
-        for (int n = 0; n < 4; ++n) rsz_slot(warped, feat, r[n], plane, p[n], k, xf[n]);
+        for (int n = 0; n < 4; ++n) pv_slot(warped, feat, r[n], plane, p[n], k, xf[n]);          // (each tap under its own mask)
 #pragma unroll
-        for (int e = 0; e < RIN; ++e) x[e] = rsz_blend(xf[0][e], xf[1][e], xf[2][e], xf[3][e], ty, tx);
+        for (int e = 0; e < PV_IN; ++e) x[e] = rsz_blend(xf[0][e], xf[1][e], xf[2][e], xf[3][e], ty, tx);
         x[7] = 0.0f;          // the eighth input of the first layer's four k-steps
-        const rsz_f32x16 h2 = rsz_mlp(f, bias, x, h);
+        pv_f32x16 h1, h2;          // (h1 is not used here)
+        pv_mlp(f, bias, x, h, h1, h2);
 #pragma unroll
         for (int m = 0; m < 16; ++m) agg[m] = MODE == IBGS_RSZ_MEAN ? agg[m] + h2[m] : fmaxf(agg[m], h2[m]);          // (h2 >= 0: the maximum may start from 0)
     }
@@ -177,7 +108,7 @@ __global__ void __launch_bounds__(RT) rsz_features_kernel(const float* __restric
     }
     if (!in) return;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) out[(size_t)rsz_ch(m, h) * plane_r + q] = agg[m];
+    for (int m = 0; m < 16; ++m) out[(size_t)pv_ch(m, h) * plane_r + q] = agg[m];
     float v[3];
     if (h == 0) {          // half 0 writes the ray, half 1 the colour
 #pragma unroll
@@ -193,7 +124,7 @@ __global__ void __launch_bounds__(RT) rsz_features_kernel(const float* __restric
         for (int ch = 0; ch < 3; ++ch) v[ch] = rsz_blend(r[0][ch], r[1][ch], r[2][ch], r[3][ch], ty, tx);
     }
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) out[(size_t)(RF + 3 * h + ch) * plane_r + q] = v[ch];
+    for (int ch = 0; ch < 3; ++ch) out[(size_t)(PV_F + 3 * h + ch) * plane_r + q] = v[ch];
 }
 
 // VEC: W % 4 == 0 and render, residual_out, image_pred_out are 16-byte aligned.  Item = (row, quad of 4 columns); the same arithmetic per element either way.

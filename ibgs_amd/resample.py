@@ -16,7 +16,7 @@ import math
 import torch
 
 from . import _device, _lib
-from .coloragg import _count, _f32, _image3, _parameters, _planes
+from .coloragg import _count, _f32, _front_end_arguments, _image3, count_levels          # noqa: F401  (count_levels is part of this module's surface)
 
 MODES = {"mean": _lib.RSZ_MEAN, "max": _lib.RSZ_MAX}
 
@@ -50,27 +50,6 @@ def _forward_only(name, tensors):
                            "residual resolution is not covered" % name)
 
 
-def count_levels(warped_image, nb_visible_src_frames=3):
-    """warped_image (3 S, H, W) or (S, 3, H, W) at FULL resolution -> the 0-d int32 DEVICE tensor min(slots whose colours are not all zero,
-    nb_visible_src_frames, S): the level count of `coloragg.per_view_features` without its forward (ibgs_cagg_levels).  Nothing waits for the host."""
-    name = "count_levels"
-    if not torch.is_tensor(warped_image) or warped_image.dim() not in (3, 4):
-        raise ValueError("%s: warped_image must be a (3 S, H, W) or (S, 3, H, W) tensor" % name)
-    h, w = int(warped_image.shape[-2]), int(warped_image.shape[-1])
-    if h * w == 0 or h > _lib.CAGG_MAX_SIDE or w > _lib.CAGG_MAX_SIDE:
-        raise ValueError("%s: a frame of %d x %d is out of range (sides 1 .. %d)" % (name, h, w, _lib.CAGG_MAX_SIDE))
-    s = _planes(name, "warped_image", warped_image, 3, h, w)
-    nb = _count(name, "nb_visible_src_frames", nb_visible_src_frames, 1)
-    _device.refuse_cpu("resample", "%s's warped_image" % name, warped_image)
-    dev = warped_image.device
-    x = _f32(warped_image)
-    with torch.cuda.device(dev):
-        levels = torch.empty((), dtype=torch.int32, device=dev)
-    sc = _device.scratch(dev, _lib.load().ibgs_cagg_required_scratch(s, h, w))
-    _device.call(dev, "ibgs_cagg_levels", s, h, w, x.data_ptr(), min(nb, s), levels.data_ptr(), sc.data_ptr(), sc.numel())
-    return levels
-
-
 def resized_features(render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, size, levels, mode="mean"):
     """render (3, H, W) (or the exposure-corrected image made of it); warped_image (3 S, H, W) or (S, 3, H, W); cam_feat (4 S, H, W) or (S, 4, H, W);
     camera_ray (3, H, W); the four parameters of `per_view_mlp` in nn.Linear layout; 1 <= S <= 5; size = (Hr, Wr), e.g. `scaled_size(H, W, s)`;
@@ -81,35 +60,14 @@ def resized_features(render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2,
     strides are converted; no argument is written; the same arguments give the same bits on every call and stream; nothing waits for the host.
     Forward only: with grad mode on and an argument that requires grad this raises."""
     name = "resized_features"
-    h, w = _image3(name, "render", render)
-    if _image3(name, "camera_ray", camera_ray) != (h, w):
-        raise ValueError("%s: camera_ray is %s, render %s" % (name, tuple(camera_ray.shape), tuple(render.shape)))
-    s, s_feat = _planes(name, "warped_image", warped_image, 3, h, w), _planes(name, "cam_feat", cam_feat, 4, h, w)
-    if s_feat != s:
-        raise ValueError("%s: warped_image holds %d sources, cam_feat %d" % (name, s, s_feat))
-    _parameters(name, w1, b1, w2, b2)
-    hr, wr = _size(name, size)
-    if mode not in MODES:
-        raise ValueError("%s: mode must be 'mean' or 'max', got %r" % (name, mode))
-    named = [("render", render), ("warped_image", warped_image), ("cam_feat", cam_feat), ("camera_ray", camera_ray), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)]
-    if torch.is_tensor(levels):
-        if levels.dim() != 0 or levels.dtype != torch.int32:
-            raise ValueError("%s: levels must be an int or a 0-d int32 tensor, got %s %s" % (name, tuple(levels.shape), levels.dtype))
-        named.append(("levels", levels))
-    else:
-        levels = _count(name, "levels", levels, 0)
-    _forward_only(name, [t for _, t in named])
-    for what, t in named:
-        _device.refuse_cpu("resample", "%s's %s" % (name, what), t)
+    s, h, w, (hr, wr), levels, tensors = _front_end_arguments("resample", name, render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, MODES, mode, levels,
+                                                              lambda: _size(name, size), lambda ts: _forward_only(name, ts))
     dev = render.device
-    for what, t in named[1:]:
-        if t.device != dev:
-            raise ValueError("%s: render is on %s, %s on %s" % (name, dev, what, t.device))
     with torch.cuda.device(dev):
         if not torch.is_tensor(levels):
             levels = torch.full((), min(levels, s), dtype=torch.int32, device=dev)
         out = torch.empty((1, _lib.RSZ_FEATURES + 6, hr, wr), dtype=torch.float32, device=dev)
-    r, x, feat, ray, p1, q1, p2, q2 = (_f32(t) for _, t in named[:8])
+    r, x, feat, ray, p1, q1, p2, q2 = (_f32(t) for t in tensors)
     _device.call(dev, "ibgs_rsz_features_forward", s, h, w, hr, wr, MODES[mode], r.data_ptr(), x.data_ptr(), feat.data_ptr(), ray.data_ptr(), p1.data_ptr(), q1.data_ptr(),
                  p2.data_ptr(), q2.data_ptr(), levels.data_ptr(), out.data_ptr())
     return out

@@ -1,5 +1,5 @@
 """The geometry-loss unit on a CPU-only box: the C ABI (include/ibgs_geo_loss.h <-> _lib.GEOLOSS_EXPORTS <-> the built library), the build registration,
-the window weights it shares with ssim.hip as text, the entry points' validation with null pointers and bad sizes, the argument checks of
+the window it takes from the header it shares with ssim.hip, the entry points' validation with null pointers and bad sizes, the argument checks of
 ibgs_amd.losses.photometric_loss / normal_consistency (which run before any GPU work), and the float64 restatement (tests/geoloss_ref.py) against the
 float32 torch expression of train.py on one small case."""
 import ctypes
@@ -55,17 +55,26 @@ def test_kernels_attributed_to_the_geoloss_unit():
                   ("ssim_fwd_kernel", "ssim"), ("depth_normal_kernel", "depth_normal")):
         assert _build.tu_of(k) == tu, k
     assert not re.search(r"atomic", _build._code_only(src)), "the sums are per-workgroup partials and a fixed-order final pass"
-    # no header of its own under csrc/: every header there is hashed into every unit's profile stamp
+    # no header of its own under csrc/: every header there is hashed into every unit's profile stamp; the one it shares with ssim.hip lies a directory below
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if "geoloss" in f and not f.startswith("_")) == ["geoloss.hip"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "block_ops.h", "shared/ssim_window.h", "../../include/ibgs_geo_loss.h"]
+    assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
 
 
-def test_window_weights_are_the_ssim_units_text():
-    taps = lambda path, name: re.search(name + r"\[6\]\s*=\s*\{([^}]*)\}", open(path).read()).group(1)
-    mine, theirs = taps(SRC, "GEO_W"), taps(os.path.join(ROOT, "ibgs_amd", "csrc", "ssim.hip"), "SSIM_W")
-    assert mine == theirs
+def test_window_is_defined_once_in_the_shared_header():
+    """Neither unit holds a weight or a C1 / C2 of its own: both include the header, whose values are the reference's."""
+    shared = open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "ssim_window.h")).read()
+    for path in (SRC, os.path.join(ROOT, "ibgs_amd", "csrc", "ssim.hip")):
+        text = open(path).read()
+        code = _build._code_only(text)
+        assert not re.search(r"0[xX][0-9a-fA-F.]+[pP][+-]?\d+", code), path          # no hex-float literal
+        assert not re.search(r"\b\w*C[12]\s*=", code), path          # no C1 / C2 defined here
+        assert '#include "shared/ssim_window.h"' in text and "SSIMW_" in code, path
+    mine = re.search(r"SSIMW_W\[6\]\s*=\s*\{([^}]*)\}", shared).group(1)
+    assert len(re.findall(r"0[xX][0-9a-fA-F.]+[pP][+-]?\d+", _build._code_only(shared))) == 6          # the six taps and no other
     assert [float.fromhex(t.strip().rstrip("f")) for t in mine.split(",")] == [float(x) for x in ssim_ref.gaussian()[:6]]
-    consts = lambda path, name: re.search(name + r"C1\s*=\s*([^,;]*),\s*" + name + r"C2\s*=\s*([^,;]*);", open(path).read()).groups()
-    assert consts(SRC, "GEO_") == consts(os.path.join(ROOT, "ibgs_amd", "csrc", "ssim.hip"), "SSIM_")
+    c1, c2 = re.search(r"SSIMW_C1\s*=\s*([^,;]*),\s*SSIMW_C2\s*=\s*([^,;]*);", shared).groups()
+    assert (c1.strip(), c2.strip()) == ("0.01f * 0.01f", "0.03f * 0.03f")          # 0.01^2 and 0.03^2, formed in float32
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

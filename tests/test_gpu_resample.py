@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from ibgs_amd import hourglass, resample
+from ibgs_amd import coloragg, hourglass, resample
 from tests import dirty_alloc as da
 from tests import exposure_ref
 from tests import hourglass_ref
@@ -99,6 +99,30 @@ def test_resized_features_against_float64(frame, mode):
     assert int(counted) == lv == 3
     if frame == (9, 13, 0.56):          # steps of exactly 2: the colour is the tap itself
         assert torch.equal(got[0, 35:], case[0][:, ::2, ::2])
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+@pytest.mark.parametrize("frame", [(5, 7), (9, 29)], ids=lambda f: "%dx%d" % f)
+def test_at_the_frames_own_size_it_is_the_front_end_bit_for_bit(frame, mode):
+    """resample.hip and coloragg.hip run ONE per-view chain (csrc/shared/pv_mlp.h).  At size == (H, W) every tap has t = 0 and u = 1, and fma(0, b, 1 a) = a for
+    finite inputs: the blended slot is the slot, so the aggregate (channels 0 .. 31) and the colour (35 .. 37) must be `per_view_features`'s to the bit.  The ray
+    channels are not compared: the resampled ray is normalised.  5 x 7: one partial wave; 9 x 29 = 261 pixels: three workgroups, the last wave partial."""
+    h, w = frame
+    g = torch.Generator().manual_seed(100 * h + w)
+    r = lambda *shape: torch.randn(*shape, generator=g)
+    render, warped, feat, ray = r(3, h, w), r(9, h, w), r(12, h, w), r(3, h, w)          # cam_feat signed: about half of every slot's pixels are masked
+    params = (r(32, 7) / 7 ** 0.5, r(32) / 4, r(32, 32) / 32 ** 0.5, r(32) / 4)
+    valid = feat.view(3, 4, h, w).sum(1) > 0
+    assert all(0.25 < float(v.float().mean()) < 0.75 for v in valid)
+    args = tuple(t.to(DEV) for t in (render, warped, feat, ray) + params)
+    for levels in (0, 2, 3):
+        with torch.no_grad():
+            mine = resample.resized_features(*args, (h, w), levels, mode)
+            theirs, _ = coloragg.per_view_features(*args, mode=mode, levels=levels)
+        torch.cuda.synchronize()
+        assert mine.shape == theirs.shape == (1, 38, h, w) and bool(torch.isfinite(mine).all())
+        assert torch.equal(mine[0, :32], theirs[0, :32]) and torch.equal(mine[0, 35:], theirs[0, 35:]), (frame, mode, levels)
+        assert bool(mine[0, :32].any()) == (levels > 0) and torch.equal(theirs[0, 35:], args[0])
 
 
 @pytest.mark.parametrize("frame", [(9, 11, 0.5), (35, 37, 0.5)], ids=lambda f: "%dx%d_s%g" % f)

@@ -48,8 +48,8 @@ def test_window_is_the_references_and_the_kernels_hold_it():
     assert g.dtype == torch.float32 and g.shape == (11,) and torch.equal(g, g.flip(0))
     w2 = ref.window_2d()
     assert w2.dtype == torch.float32 and torch.equal(w2, (g[:, None] * g[None, :]))
-    src = open(os.path.join(ROOT, "ibgs_amd", "csrc", "ssim.hip")).read()
-    taps = re.search(r"SSIM_W\[6\]\s*=\s*\{([^}]*)\}", src).group(1)
+    src = open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "ssim_window.h")).read()          # the one place the kernels of ssim.hip and geoloss.hip take it from
+    taps = re.search(r"SSIMW_W\[6\]\s*=\s*\{([^}]*)\}", src).group(1)
     vals = [float.fromhex(t.strip().rstrip("f")) for t in taps.split(",")]
     assert vals == [float(x) for x in g[:6]]
 
