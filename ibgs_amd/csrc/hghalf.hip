@@ -20,6 +20,7 @@
 // product.  In the last launch the accumulator tile, rounded, is the next product's B operand as it stands: k-step s takes the M tiles 2 s and 2 s + 1, element
 // j of a lane being channel 16 (2 s + (j >> 2)) + 4 kq + (j & 3), and hgh_pack_kernel lays the 1 x 1 weights out in that order.
 #include "common.h"
+#include "shared/hg_net.h"
 #include "../../include/ibgs_hourglass.h"
 #include "../../include/ibgs_hg_half.h"
 
@@ -35,31 +36,26 @@ constexpr int HGH_ROWS = HGH_TILE / (HGH_THREADS / 64);          // rows of the 
 constexpr int HGH_WIN = HGH_TILE + 2;                // the staged window: tile and halo
 constexpr int HGH_NPIX = HGH_WIN * HGH_WIN;
 constexpr int HGH_PSTRIDE = 5;                       // 16-byte units per staged pixel: four octets and one of padding (odd)
-constexpr int HGH_C = IBGS_HG_CHANNELS;
-constexpr int HGH_XO = (HGH_C + 7) / 8;              // octets of x
-enum { HGH_PLAIN = 0, HGH_POOL = 1, HGH_UP = 2 };
+constexpr int HGH_XO = (HG_C + 7) / 8;               // octets of x
 static_assert(HGH_ROWS == 4 && HGH_PSTRIDE % 2 == 1 && HGH_THREADS % 4 == 0, "the lane maps and the bank argument above");
 
 constexpr int hgh_octets(int c) { return (c + 7) / 8; }
 // fragments (eight binary16 each) of a packed 3 x 3 layer: chunks x 9 taps x M tiles x 64 lanes
 constexpr int hgh_frags(int ca, int cb, int cout) { return ((hgh_octets(ca) + hgh_octets(cb) + 3) / 4) * 9 * ((cout + 15) / 16) * 64; }
 constexpr int HGH_FUSE_STEPS = 2 + (HGH_XO + 3) / 4, HGH_FIN_STEPS = 2;          // k-steps of fuse_input (d1: 2, x: 2) and final
-// the nine layers' first fragments in the packed weights, in the order of the C ABI
-constexpr int HGH_AT_ENC1 = 0, HGH_AT_ENC2 = HGH_AT_ENC1 + hgh_frags(38, 0, 38), HGH_AT_ENC3 = HGH_AT_ENC2 + hgh_frags(38, 0, 19),
-              HGH_AT_UP2 = HGH_AT_ENC3 + hgh_frags(19, 0, 9), HGH_AT_DEC2 = HGH_AT_UP2 + hgh_frags(9, 0, 19), HGH_AT_UP1 = HGH_AT_DEC2 + hgh_frags(19, 19, 19),
-              HGH_AT_DEC1 = HGH_AT_UP1 + hgh_frags(19, 0, 38), HGH_AT_FUSE = HGH_AT_DEC1 + hgh_frags(38, 38, 38), HGH_AT_FINAL = HGH_AT_FUSE + HGH_FUSE_STEPS * 3 * 64,
-              HGH_FRAGS = HGH_AT_FINAL + HGH_FIN_STEPS * 64;
+// layer i of HG_LAYERS in the packed weights, which hold the nine in the order of the C ABI: its kind (0: 3 x 3; 1: fuse_input; 2: final), its fragments, its first one
+constexpr int hgh_kind(int i) { return HG_LAYERS[i].side == 3 ? 0 : (i == HG_FINAL ? 2 : 1); }
+constexpr int hgh_layer_frags(int i)
+{
+    const HgLayer& l = HG_LAYERS[i];
+    return hgh_kind(i) == 0 ? hgh_frags(l.ca, l.cb, l.cout) : (hgh_kind(i) == 1 ? HGH_FUSE_STEPS : HGH_FIN_STEPS) * ((l.cout + 15) / 16) * 64;
+}
+constexpr int hgh_at(int i) { return i == 0 ? 0 : hgh_at(i - 1) + hgh_layer_frags(i - 1); }
+constexpr int HGH_FRAGS = hgh_at(HG_LAYER_COUNT);
 static_assert((size_t)HGH_FRAGS * 16 == IBGS_HGH_PACKED_WEIGHT_BYTES, "the header's size of the packed weights");
 
 __device__ __forceinline__ hgh_f32x4 hgh_mfma(hgh_h8 a, hgh_h8 b, hgh_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float hgh_round(float v) { return (float)(_Float16)v; }          // to binary16, to nearest even, and back
-
-__device__ __forceinline__ float hgh_blend(float burned, float render, float residual)
-{
-#pragma clang fp contract(off)
-    const float scaled = burned * render;          // rounded before the sum: torch's two kernels
-    return scaled + residual;
-}
 
 // ---- the packing launch: h(x) pixel-major, and the nine layers' weights as operand fragments ---------------------------------------------------------------
 struct HghPackLayer {
@@ -83,7 +79,7 @@ __global__ void __launch_bounds__(HGH_THREADS) hgh_pack_kernel(const HghPackArgs
         for (int o = 0; o < HGH_XO; ++o) {
             hgh_h8 v;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = 8 * o + j < HGH_C ? (_Float16)a.x[(size_t)(8 * o + j) * a.pixels + p] : (_Float16)0.0f;
+            for (int j = 0; j < 8; ++j) v[j] = 8 * o + j < HG_C ? (_Float16)a.x[(size_t)(8 * o + j) * a.pixels + p] : (_Float16)0.0f;
             a.xh[p * HGH_XO + o] = v;
         }
         return;
@@ -151,8 +147,8 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
     constexpr int NOA = hgh_octets(CA), NOB = hgh_octets(CB), NO = NOA + NOB, NC = (NO + 3) / 4, MT = (COUT + 15) / 16, CPOUT = 8 * hgh_octets(COUT);
     constexpr int NWF = 9 * MT * 64;          // weight fragments of a chunk
     constexpr int NPOS = (HGH_NPIX * 4 + HGH_THREADS - 1) / HGH_THREADS, NW = (NWF + HGH_THREADS - 1) / HGH_THREADS;
-    static_assert(CB == 0 || MODE == HGH_PLAIN, "a second input is read plain, at the first one's resolution");
-    static_assert(!FUSE || (COUT == HGH_C && MT == 3), "the last launch is dec1");
+    static_assert(CB == 0 || MODE == HG_PLAIN, "a second input is read plain, at the first one's resolution");
+    static_assert(!FUSE || (COUT == HG_C && MT == 3), "the last launch is dec1");
     __shared__ hgh_h8 s_in[HGH_NPIX * HGH_PSTRIDE];
     __shared__ hgh_h8 s_w[NWF];
 
@@ -182,8 +178,8 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
         pos_in[r] = p < HGH_NPIX && y >= 0 && y < h && x >= 0 && x < w;
         const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
         // a holds hs x ws pixels: (h, w) itself (plain), >= (2 h, 2 w) (pool: the 2 x 2 maximum; an odd last row or column is never read) or (h / 2, w / 2) (up)
-        if (MODE == HGH_PLAIN) pos[r] = yc * a.ws + xc;
-        else if (MODE == HGH_POOL) pos[r] = 2 * yc * a.ws + 2 * xc;          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
+        if (MODE == HG_PLAIN) pos[r] = yc * a.ws + xc;
+        else if (MODE == HG_POOL) pos[r] = 2 * yc * a.ws + 2 * xc;          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
         else pos[r] = min(yc * a.hs / h, a.hs - 1) * a.ws + min(xc * a.ws / w, a.ws - 1);          // (yc hs < 2^26)
     }
     hgh_h8 iv[NPOS], wv[NW];
@@ -197,7 +193,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
         for (int r = 0; r < NPOS; ++r) {
             const _Float16* const q = base + (size_t)pos[r] * cp;
             hgh_h8 v = *reinterpret_cast<const hgh_h8*>(q);
-            if (MODE == HGH_POOL) {
+            if (MODE == HG_POOL) {
                 const hgh_h8 v1 = *reinterpret_cast<const hgh_h8*>(q + cp), v2 = *reinterpret_cast<const hgh_h8*>(q + (size_t)a.ws * cp),
                              v3 = *reinterpret_cast<const hgh_h8*>(q + ((size_t)a.ws + 1) * cp);
                 v = __builtin_elementwise_max(__builtin_elementwise_max(v, v1), __builtin_elementwise_max(v2, v3));
@@ -267,7 +263,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
         for (int mt = 0; mt < 3; ++mt) {
             hgh_f32x4 start;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) start[r] = mt * 16 + kq * 4 + r < HGH_C ? hgh_round(a.fuse_b[mt * 16 + kq * 4 + r]) : 0.0f;
+            for (int r = 0; r < 4; ++r) start[r] = mt * 16 + kq * 4 + r < HG_C ? hgh_round(a.fuse_b[mt * 16 + kq * 4 + r]) : 0.0f;
 #pragma unroll
             for (int nt = 0; nt < HGH_ROWS; ++nt) f[mt][nt] = start;
         }
@@ -313,7 +309,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) {
                         a.residual[(size_t)ch * plane + p] = res[nt][ch];
-                        if (a.image_pred) a.image_pred[(size_t)ch * plane + p] = hgh_blend(a.burned, a.x[(size_t)(HGH_C - 3 + ch) * plane + p], res[nt][ch]);
+                        if (a.image_pred) a.image_pred[(size_t)ch * plane + p] = hg_blend(a.burned, a.x[(size_t)(HG_C - 3 + ch) * plane + p], res[nt][ch]);
                     }
                 }
             }
@@ -321,34 +317,18 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
     }
 }
 
-// who == nullptr: silent (the size query)
-static bool hgh_shape_ok(const char* who, int64_t H, int64_t W)
-{
-    if (H < IBGS_HG_MIN_SIDE || W < IBGS_HG_MIN_SIDE || H > IBGS_HG_MAX_SIDE || W > IBGS_HG_MAX_SIDE) {
-        if (who) set_error("%s: a frame of %lld x %lld is out of range (sides %d .. %d)", who, (long long)H, (long long)W, IBGS_HG_MIN_SIDE, IBGS_HG_MAX_SIDE);
-        return false;
-    }
-    return true;
-}
-
-struct HghScratch {          // the arena of the header, in its order
-    _Float16 *xh, *e1, *e2, *b, *u2, *d2, *u1;
+struct HghScratch {          // the arena of the header, in its order: h(x), the six stages (both pixel-major octets), the packed weights
+    _Float16* xh;
+    HgStages<_Float16> s;
     hgh_h8* packed;
-    static HghScratch carve(char* base, size_t H, size_t W, size_t* total)
+    size_t bytes;
+    HghScratch(char* base, size_t H, size_t W)
     {
-        const size_t p1 = H * W, p2 = (H / 2) * (W / 2), p4 = (H / 4) * (W / 4);
-        HghScratch s;
         Carver c(base);
-        s.xh = c.take<_Float16>(40 * p1);
-        s.e1 = c.take<_Float16>(40 * p1);
-        s.e2 = c.take<_Float16>(24 * p2);
-        s.b = c.take<_Float16>(16 * p4);
-        s.u2 = c.take<_Float16>(24 * p2);
-        s.d2 = c.take<_Float16>(24 * p2);
-        s.u1 = c.take<_Float16>(40 * p1);
-        s.packed = c.take<hgh_h8>(HGH_FRAGS);
-        if (total) *total = ((c.cur + 127) & ~uintptr_t(127)) - reinterpret_cast<uintptr_t>(base);
-        return s;
+        xh = c.take<_Float16>(8 * HGH_XO * H * W);
+        s = hg_carve_stages<_Float16>(c, H, W, 8);
+        packed = c.take<hgh_h8>(HGH_FRAGS);
+        bytes = hg_carved_bytes(c, base);
     }
 };
 
@@ -374,10 +354,7 @@ extern "C" {
 
 size_t ibgs_hgh_required_scratch(int64_t H, int64_t W)
 {
-    size_t total = 0;
-    if (!hgh_shape_ok(nullptr, H, W)) return 0;
-    HghScratch::carve(nullptr, (size_t)H, (size_t)W, &total);
-    return total;
+    return hg_shape_ok(nullptr, H, W) ? HghScratch(nullptr, (size_t)H, (size_t)W).bytes : 0;
 }
 
 int32_t ibgs_hgh_forward(void* stream, int32_t H, int32_t W, const float* x, const float* enc1_w, const float* enc1_b, const float* enc2_w,
@@ -386,39 +363,33 @@ int32_t ibgs_hgh_forward(void* stream, int32_t H, int32_t W, const float* x, con
                          const float* dec1_b, const float* fuse_input_w, const float* fuse_input_b, const float* final_w, const float* final_b,
                          float burned_in_gauss, float* residual, float* image_pred, void* scratch, size_t scratch_bytes)
 {
-    size_t need = 0;
-    if (!hgh_shape_ok("hgh_forward", H, W)) return -IBGS_ERR_INVALID;
+    if (!hg_shape_ok("hgh_forward", H, W)) return -IBGS_ERR_INVALID;
     if (!x) { set_error("hgh_forward: null input"); return -IBGS_ERR_INVALID; }
     const float* const params[18] = {enc1_w, enc1_b, enc2_w, enc2_b, enc3_w, enc3_b, up2_conv_w, up2_conv_b, dec2_w, dec2_b, up1_conv_w, up1_conv_b, dec1_w, dec1_b,
                                      fuse_input_w, fuse_input_b, final_w, final_b};
-    static const char* const names[9] = {"enc1", "enc2", "enc3", "up2_conv", "dec2", "up1_conv", "dec1", "fuse_input", "final"};
-    for (int i = 0; i < 18; ++i)
-        if (!params[i]) { set_error("hgh_forward: null parameters: %s's %s", names[i / 2], i & 1 ? "bias" : "weight"); return -IBGS_ERR_INVALID; }
+    if (!hg_params_ok("hgh_forward", params)) return -IBGS_ERR_INVALID;
     if (!residual) { set_error("hgh_forward: null outputs: residual is required"); return -IBGS_ERR_INVALID; }
-    const HghScratch sc = HghScratch::carve(static_cast<char*>(scratch), (size_t)H, (size_t)W, &need);
-    if (!arena_ok("hgh_forward", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
+    const HghScratch sc(static_cast<char*>(scratch), (size_t)H, (size_t)W);
+    if (!arena_ok("hgh_forward", "scratch", scratch, scratch_bytes, sc.bytes)) return -IBGS_ERR_INVALID;
+    const HgStages<_Float16>& s = sc.s;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
 
     HghPackArgs pk = {};
     pk.x = x; pk.xh = reinterpret_cast<hgh_h8*>(sc.xh); pk.pixels = (size_t)H * (size_t)W; pk.x_blocks = grid_for(pk.pixels, HGH_THREADS); pk.packed = sc.packed;
-    // (weight, rows, channels of a, of b, first fragment, kind) in the order of the C ABI
-    const HghPackLayer layers[9] = {{enc1_w, 38, 38, 0, HGH_AT_ENC1, 0}, {enc2_w, 19, 38, 0, HGH_AT_ENC2, 0}, {enc3_w, 9, 19, 0, HGH_AT_ENC3, 0},
-                                    {up2_conv_w, 19, 9, 0, HGH_AT_UP2, 0}, {dec2_w, 19, 19, 19, HGH_AT_DEC2, 0}, {up1_conv_w, 38, 19, 0, HGH_AT_UP1, 0},
-                                    {dec1_w, 38, 38, 38, HGH_AT_DEC1, 0}, {fuse_input_w, 38, 38, 38, HGH_AT_FUSE, 1}, {final_w, 3, 38, 0, HGH_AT_FINAL, 2}};
-    for (int i = 0; i < 9; ++i) pk.layer[i] = layers[i];
+    for (int i = 0; i < HG_LAYER_COUNT; ++i) pk.layer[i] = {params[2 * i], HG_LAYERS[i].cout, HG_LAYERS[i].ca, HG_LAYERS[i].cb, hgh_at(i), hgh_kind(i)};
     hipLaunchKernelGGL(hgh_pack_kernel, dim3(pk.x_blocks + grid_for(HGH_FRAGS, HGH_THREADS)), dim3(HGH_THREADS), 0, st, pk);
 
-    hgh_launch<38, 0, 38, HGH_PLAIN, false>(st, hgh_layer(sc.xh, nullptr, sc.packed + HGH_AT_ENC1, enc1_b, sc.e1, H, W, H, W));
-    hgh_launch<38, 0, 19, HGH_POOL, false>(st, hgh_layer(sc.e1, nullptr, sc.packed + HGH_AT_ENC2, enc2_b, sc.e2, H2, W2, H, W));
-    hgh_launch<19, 0, 9, HGH_POOL, false>(st, hgh_layer(sc.e2, nullptr, sc.packed + HGH_AT_ENC3, enc3_b, sc.b, H4, W4, H2, W2));
-    hgh_launch<9, 0, 19, HGH_UP, false>(st, hgh_layer(sc.b, nullptr, sc.packed + HGH_AT_UP2, up2_conv_b, sc.u2, H2, W2, H4, W4));
-    hgh_launch<19, 19, 19, HGH_PLAIN, false>(st, hgh_layer(sc.u2, sc.e2, sc.packed + HGH_AT_DEC2, dec2_b, sc.d2, H2, W2, H2, W2));
-    hgh_launch<19, 0, 38, HGH_UP, false>(st, hgh_layer(sc.d2, nullptr, sc.packed + HGH_AT_UP1, up1_conv_b, sc.u1, H, W, H2, W2));
-    HghArgs last = hgh_layer(sc.u1, sc.e1, sc.packed + HGH_AT_DEC1, dec1_b, nullptr, H, W, H, W);
-    last.xh = sc.xh; last.x = x; last.fuse_frag = sc.packed + HGH_AT_FUSE; last.fuse_b = fuse_input_b; last.final_frag = sc.packed + HGH_AT_FINAL; last.final_b = final_b;
+    hgh_launch<38, 0, 38, HG_PLAIN, false>(st, hgh_layer(sc.xh, nullptr, sc.packed + hgh_at(HG_ENC1), enc1_b, s.e1, H, W, H, W));
+    hgh_launch<38, 0, 19, HG_POOL, false>(st, hgh_layer(s.e1, nullptr, sc.packed + hgh_at(HG_ENC2), enc2_b, s.e2, H2, W2, H, W));
+    hgh_launch<19, 0, 9, HG_POOL, false>(st, hgh_layer(s.e2, nullptr, sc.packed + hgh_at(HG_ENC3), enc3_b, s.b, H4, W4, H2, W2));
+    hgh_launch<9, 0, 19, HG_UP, false>(st, hgh_layer(s.b, nullptr, sc.packed + hgh_at(HG_UP2_CONV), up2_conv_b, s.u2, H2, W2, H4, W4));
+    hgh_launch<19, 19, 19, HG_PLAIN, false>(st, hgh_layer(s.u2, s.e2, sc.packed + hgh_at(HG_DEC2), dec2_b, s.d2, H2, W2, H2, W2));
+    hgh_launch<19, 0, 38, HG_UP, false>(st, hgh_layer(s.d2, nullptr, sc.packed + hgh_at(HG_UP1_CONV), up1_conv_b, s.u1, H, W, H2, W2));
+    HghArgs last = hgh_layer(s.u1, s.e1, sc.packed + hgh_at(HG_DEC1), dec1_b, nullptr, H, W, H, W);
+    last.xh = sc.xh; last.x = x; last.fuse_frag = sc.packed + hgh_at(HG_FUSE_INPUT); last.fuse_b = fuse_input_b; last.final_frag = sc.packed + hgh_at(HG_FINAL); last.final_b = final_b;
     last.burned = burned_in_gauss; last.residual = residual; last.image_pred = image_pred;
-    hgh_launch<38, 38, 38, HGH_PLAIN, true>(st, last);
+    hgh_launch<38, 38, 38, HG_PLAIN, true>(st, last);
     IBGS_HIP(hipGetLastError());
     return 0;
 }

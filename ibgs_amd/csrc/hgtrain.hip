@@ -22,6 +22,7 @@
 // STAGING keeps the forward's discipline: coordinates are clamped into the frame before an offset is formed, every load is unconditional and from a valid
 // address, and what lies outside the frame or past the last channel is replaced by zero afterwards.
 #include "common.h"
+#include "shared/hg_net.h"
 #include "../../include/ibgs_hourglass.h"
 #include "../../include/ibgs_hg_train.h"
 
@@ -38,8 +39,6 @@ constexpr int HGB_WT_W = 16;                         // ... and columns
 constexpr int HGB_MAX_STRIPS = 128;                  // strips (partials) per weight gradient, at most
 constexpr int HGB_MIN_STRIP_TILES = 2;               // tiles of a strip, at least
 constexpr int HGB_GPLANE = HGB_WT_H * HGB_WT_W + 4;  // floats per staged channel of G: the 64 lanes of a read fall into 64 banks
-constexpr int HGB_C = IBGS_HG_CHANNELS;
-enum { HGB_PLAIN = 0, HGB_POOL = 1, HGB_UP = 2 };
 
 __device__ __forceinline__ hgb_f32x4 hgb_mfma(float a, float b, hgb_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
@@ -191,7 +190,7 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_wgrad_kernel(const HgbWgra
     constexpr int CIN = CA + CB, MT = (COUT + 15) / 16, COUTP = MT * 16, NT = S::NT, CI = S::CI;
     constexpr int PAD = TAPS == 9 ? 1 : 0, WINW = HGB_WT_W + 2 * PAD, WINH = HGB_WT_H + 2 * PAD, IPL = WINW * WINH;
     constexpr int ROWS = HGB_WT_H / 4;          // rows of a tile per wave
-    static_assert(CB == 0 || MODE == HGB_PLAIN, "a second input is read plain, at the first one's resolution");
+    static_assert(CB == 0 || MODE == HG_PLAIN, "a second input is read plain, at the first one's resolution");
     constexpr int G_WORDS = COUTP * HGB_GPLANE, I_WORDS = CI * IPL, RED_WORDS = 2 * 4 * NT * 256;          // the last: one row of result tiles of the four waves, in double
     __shared__ __attribute__((aligned(16))) float s_mem[G_WORDS + I_WORDS > RED_WORDS ? G_WORDS + I_WORDS : RED_WORDS];
     float* const s_g = s_mem;
@@ -240,8 +239,8 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_wgrad_kernel(const HgbWgra
             const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
             const float* const base = (CB == 0 || cc < CA) ? a.a + (size_t)cc * plane_a : a.b + (size_t)(cc - CA) * plane_a;
             float v;
-            if (MODE == HGB_PLAIN) v = base[yc * a.ws + xc];
-            else if (MODE == HGB_POOL) {          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
+            if (MODE == HG_PLAIN) v = base[yc * a.ws + xc];
+            else if (MODE == HG_POOL) {          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
                 const float* const q = base + 2 * yc * a.ws + 2 * xc;
                 v = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[a.ws], q[a.ws + 1]));
             } else v = base[min(yc * a.hs / h, a.hs - 1) * a.ws + min(xc * a.ws / w, a.ws - 1)];
@@ -364,15 +363,6 @@ __global__ void __launch_bounds__(HGB_THREADS) hgb_unup_kernel(const float* __re
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
-static bool hgb_shape_ok(const char* who, int64_t H, int64_t W)
-{
-    if (H < IBGS_HG_MIN_SIDE || W < IBGS_HG_MIN_SIDE || H > IBGS_HG_MAX_SIDE || W > IBGS_HG_MAX_SIDE) {
-        if (who) set_error("%s: a frame of %lld x %lld is out of range (sides %d .. %d)", who, (long long)H, (long long)W, IBGS_HG_MIN_SIDE, IBGS_HG_MAX_SIDE);
-        return false;
-    }
-    return true;
-}
-
 struct HgbStrips {          // how a frame of h x w is cut into strips of tiles
     int tiles_x, ntiles, strip_tiles, strips;
     HgbStrips(int h, int w)
@@ -385,36 +375,26 @@ struct HgbStrips {          // how a frame of h x w is cut into strips of tiles
     }
 };
 
-template <int CIN, int COUT, int TAPS>
-static size_t hgb_partial_floats(int h, int w)
+// the floats of the partials of the weight gradients of layers I .. of HG_LAYERS, each at its own resolution: the most any of them takes
+template <int I = 0>
+static size_t hgb_partial_floats(const int (&h)[3], const int (&w)[3])
 {
-    using S = HgbSlice<CIN, COUT, TAPS>;
-    return (size_t)HgbStrips(h, w).strips * S::SLICES * (size_t)(((COUT + 15) / 16) * 16 * S::COLSP);
-}
-
-struct HgbStages {          // the arena of ibgs_hg_forward (include/ibgs_hourglass.h), read only
-    const float *e1, *e2, *b, *u2, *d2, *u1;
-    static HgbStages carve(const char* base, size_t H, size_t W)
-    {
-        const size_t p1 = H * W, p2 = (H / 2) * (W / 2), p4 = (H / 4) * (W / 4);
-        HgbStages s;
-        Carver c(const_cast<char*>(base));
-        s.e1 = c.take<float>(38 * p1);
-        s.e2 = c.take<float>(19 * p2);
-        s.b = c.take<float>(9 * p4);
-        s.u2 = c.take<float>(19 * p2);
-        s.d2 = c.take<float>(19 * p2);
-        s.u1 = c.take<float>(38 * p1);
-        return s;
+    if constexpr (I == HG_LAYER_COUNT) return 0;
+    else {
+        constexpr HgLayer L = HG_LAYERS[I];
+        using S = HgbSlice<L.ca + L.cb, L.cout, L.side * L.side>;
+        const size_t mine = (size_t)HgbStrips(h[L.level], w[L.level]).strips * S::SLICES * (size_t)(((L.cout + 15) / 16) * 16 * S::COLSP);
+        const size_t rest = hgb_partial_floats<I + 1>(h, w);
+        return mine > rest ? mine : rest;
     }
-};
+}
 
 struct HgbScratch {          // the arena of the header, in its order
     float *A, *B, *C, *D, *g, *Gd2, *Gu2, *E2, *Iup2, *Ienc2, *Gb, *Ienc3, *partial;
     static HgbScratch carve(char* base, int H, int W, size_t* total)
     {
-        const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
-        const size_t p1 = (size_t)H * W, p2 = (size_t)H2 * W2, p4 = (size_t)H4 * W4;
+        const int h[3] = {H, H / 2, H / 2 / 2}, w[3] = {W, W / 2, W / 2 / 2};
+        const size_t p1 = (size_t)H * W, p2 = (size_t)h[1] * w[1], p4 = (size_t)h[2] * w[2];
         HgbScratch s;
         Carver c(base);
         s.A = c.take<float>(38 * p1);
@@ -429,13 +409,8 @@ struct HgbScratch {          // the arena of the header, in its order
         s.Ienc2 = c.take<float>(38 * p2);
         s.Gb = c.take<float>(9 * p4);
         s.Ienc3 = c.take<float>(19 * p4);
-        size_t most = hgb_partial_floats<38, 3, 1>(H, W);
-        const size_t others[8] = {hgb_partial_floats<76, 38, 1>(H, W), hgb_partial_floats<76, 38, 9>(H, W), hgb_partial_floats<19, 38, 9>(H, W),
-                                  hgb_partial_floats<38, 38, 9>(H, W), hgb_partial_floats<38, 19, 9>(H2, W2), hgb_partial_floats<9, 19, 9>(H2, W2),
-                                  hgb_partial_floats<38, 19, 9>(H2, W2), hgb_partial_floats<19, 9, 9>(H4, W4)};
-        for (size_t v : others) most = v > most ? v : most;
-        s.partial = c.take<float>(most);
-        if (total) *total = ((c.cur + 127) & ~uintptr_t(127)) - reinterpret_cast<uintptr_t>(base);
+        s.partial = c.take<float>(hgb_partial_floats(h, w));
+        if (total) *total = hg_carved_bytes(c, base);
         return s;
     }
 };
@@ -481,7 +456,7 @@ extern "C" {
 size_t ibgs_hgb_required_scratch(int64_t H, int64_t W)
 {
     size_t total = 0;
-    if (!hgb_shape_ok(nullptr, H, W)) return 0;
+    if (!hg_shape_ok(nullptr, H, W)) return 0;
     HgbScratch::carve(nullptr, (int)H, (int)W, &total);
     return total;
 }
@@ -498,32 +473,29 @@ int32_t ibgs_hgb_backward(void* stream, int32_t H, int32_t W, const float* x, co
 {
     const char* const who = "hgb_backward";
     size_t need = 0;
-    if (!hgb_shape_ok(who, H, W)) return -IBGS_ERR_INVALID;
+    if (!hg_shape_ok(who, H, W)) return -IBGS_ERR_INVALID;
     if (!x) { set_error("%s: null input", who); return -IBGS_ERR_INVALID; }
     const float* const params[18] = {enc1_w, enc1_b, enc2_w, enc2_b, enc3_w, enc3_b, up2_conv_w, up2_conv_b, dec2_w, dec2_b, up1_conv_w, up1_conv_b, dec1_w, dec1_b,
                                      fuse_input_w, fuse_input_b, final_w, final_b};
     float* const grads[18] = {grad_enc1_w, grad_enc1_b, grad_enc2_w, grad_enc2_b, grad_enc3_w, grad_enc3_b, grad_up2_conv_w, grad_up2_conv_b, grad_dec2_w, grad_dec2_b,
                               grad_up1_conv_w, grad_up1_conv_b, grad_dec1_w, grad_dec1_b, grad_fuse_input_w, grad_fuse_input_b, grad_final_w, grad_final_b};
-    static const char* const names[9] = {"enc1", "enc2", "enc3", "up2_conv", "dec2", "up1_conv", "dec1", "fuse_input", "final"};
-    for (int i = 0; i < 18; ++i)
-        if (!params[i]) { set_error("%s: null parameters: %s's %s", who, names[i / 2], i & 1 ? "bias" : "weight"); return -IBGS_ERR_INVALID; }
+    if (!hg_params_ok(who, params)) return -IBGS_ERR_INVALID;
     if (!stages_arena) { set_error("%s: null stages arena", who); return -IBGS_ERR_INVALID; }
     if (reinterpret_cast<uintptr_t>(stages_arena) & 127) { set_error("%s: stages arena is not 128-byte aligned", who); return -IBGS_ERR_INVALID; }
     if (!grad_residual && !grad_image_pred) { set_error("%s: null upstream: grad_residual and grad_image_pred are both null", who); return -IBGS_ERR_INVALID; }
     int given = 0;
     for (int i = 0; i < 18; ++i) given += grads[i] != nullptr;
     if (given != 0 && given != 18) {
-        for (int i = 0; i < 18; ++i)
-            if (!grads[i]) {
-                set_error("%s: null gradients: %s's %s (the eighteen are given together or not at all)", who, names[i / 2], i & 1 ? "bias" : "weight");
-                return -IBGS_ERR_INVALID;
-            }
+        const int i = hg_first_null(grads);
+        set_error("%s: null gradients: %s's %s (the eighteen are given together or not at all)", who, HG_LAYERS[i / 2].name, hg_part(i));
+        return -IBGS_ERR_INVALID;
     }
     const bool want_params = given == 18, want_x = grad_x != nullptr;
     if (!want_params && !want_x) { set_error("%s: null outputs: neither grad_x nor the parameter gradients are asked for", who); return -IBGS_ERR_INVALID; }
     const HgbScratch sc = HgbScratch::carve(static_cast<char*>(scratch), H, W, &need);
     if (!arena_ok(who, "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
-    const HgbStages sg = HgbStages::carve(static_cast<const char*>(stages_arena), (size_t)H, (size_t)W);
+    Carver forward_arena(static_cast<char*>(const_cast<void*>(stages_arena)));          // the arena of ibgs_hg_forward, read only
+    const HgStages<const float> sg = hg_carve_stages<const float>(forward_arena, (size_t)H, (size_t)W, 1);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
     const size_t p1 = (size_t)H * W, p2 = (size_t)H2 * W2, p4 = (size_t)H4 * W4;
@@ -540,35 +512,35 @@ int32_t ibgs_hgb_backward(void* stream, int32_t H, int32_t W, const float* x, co
     hgb_conv<38, 0, 38, 1, true>(st, sc.C, nullptr, fuse_input_w, nullptr, 76, 0, sc.D, nullptr, nullptr, 0.0f, sc.A, false, H, W);
     if (want_x) hgb_conv<38, 0, 38, 1, true>(st, sc.C, nullptr, fuse_input_w, nullptr, 76, 38, grad_x, nullptr, grad_image_pred, burned_in_gauss, nullptr, false, H, W);
     if (want_params) {
-        hgb_wgrad<38, 0, 3, HGB_PLAIN, 1>(st, g, sc.B, nullptr, sc.partial, grad_final_w, grad_final_b, H, W, H, W);
-        hgb_wgrad<38, 38, 38, HGB_PLAIN, 1>(st, sc.C, sc.A, x, sc.partial, grad_fuse_input_w, grad_fuse_input_b, H, W, H, W);
-        hgb_wgrad<38, 38, 38, HGB_PLAIN, 9>(st, sc.D, sg.u1, sg.e1, sc.partial, grad_dec1_w, grad_dec1_b, H, W, H, W);
+        hgb_wgrad<38, 0, 3, HG_PLAIN, 1>(st, g, sc.B, nullptr, sc.partial, grad_final_w, grad_final_b, H, W, H, W);
+        hgb_wgrad<38, 38, 38, HG_PLAIN, 1>(st, sc.C, sc.A, x, sc.partial, grad_fuse_input_w, grad_fuse_input_b, H, W, H, W);
+        hgb_wgrad<38, 38, 38, HG_PLAIN, 9>(st, sc.D, sg.u1, sg.e1, sc.partial, grad_dec1_w, grad_dec1_b, H, W, H, W);
     }
     // dec1: G_u1 -> A, g_e1a -> B
     hgb_dgrad<38, 38>(st, sc.D, dec1_w, 76, 0, sc.A, nullptr, sg.u1, H, W);
     hgb_dgrad<38, 38>(st, sc.D, dec1_w, 76, 38, sc.B, nullptr, nullptr, H, W);
     // up1_conv: its g_I -> C, G_d2
-    if (want_params) hgb_wgrad<19, 0, 38, HGB_UP, 9>(st, sc.A, sg.d2, nullptr, sc.partial, grad_up1_conv_w, grad_up1_conv_b, H, W, H2, W2);
+    if (want_params) hgb_wgrad<19, 0, 38, HG_UP, 9>(st, sc.A, sg.d2, nullptr, sc.partial, grad_up1_conv_w, grad_up1_conv_b, H, W, H2, W2);
     hgb_dgrad<38, 19>(st, sc.A, up1_conv_w, 19, 0, sc.C, nullptr, nullptr, H, W);
     hipLaunchKernelGGL(hgb_unup_kernel, dim3(grid_for(19 * p2, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.C, sg.d2, sc.Gd2, 19, H, W, H2, W2);
     // dec2: G_u2, g_e2a -> E2
-    if (want_params) hgb_wgrad<19, 19, 19, HGB_PLAIN, 9>(st, sc.Gd2, sg.u2, sg.e2, sc.partial, grad_dec2_w, grad_dec2_b, H2, W2, H2, W2);
+    if (want_params) hgb_wgrad<19, 19, 19, HG_PLAIN, 9>(st, sc.Gd2, sg.u2, sg.e2, sc.partial, grad_dec2_w, grad_dec2_b, H2, W2, H2, W2);
     hgb_dgrad<19, 19>(st, sc.Gd2, dec2_w, 38, 0, sc.Gu2, nullptr, sg.u2, H2, W2);
     hgb_dgrad<19, 19>(st, sc.Gd2, dec2_w, 38, 19, sc.E2, nullptr, nullptr, H2, W2);
     // up2_conv: G_b
-    if (want_params) hgb_wgrad<9, 0, 19, HGB_UP, 9>(st, sc.Gu2, sg.b, nullptr, sc.partial, grad_up2_conv_w, grad_up2_conv_b, H2, W2, H4, W4);
+    if (want_params) hgb_wgrad<9, 0, 19, HG_UP, 9>(st, sc.Gu2, sg.b, nullptr, sc.partial, grad_up2_conv_w, grad_up2_conv_b, H2, W2, H4, W4);
     hgb_dgrad<19, 9>(st, sc.Gu2, up2_conv_w, 9, 0, sc.Iup2, nullptr, nullptr, H2, W2);
     hipLaunchKernelGGL(hgb_unup_kernel, dim3(grid_for(9 * p4, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Iup2, sg.b, sc.Gb, 9, H2, W2, H4, W4);
     // enc3: G_e2 (in E2)
-    if (want_params) hgb_wgrad<19, 0, 9, HGB_POOL, 9>(st, sc.Gb, sg.e2, nullptr, sc.partial, grad_enc3_w, grad_enc3_b, H4, W4, H2, W2);
+    if (want_params) hgb_wgrad<19, 0, 9, HG_POOL, 9>(st, sc.Gb, sg.e2, nullptr, sc.partial, grad_enc3_w, grad_enc3_b, H4, W4, H2, W2);
     hgb_dgrad<9, 19>(st, sc.Gb, enc3_w, 19, 0, sc.Ienc3, nullptr, nullptr, H4, W4);
     hipLaunchKernelGGL(hgb_unpool_kernel, dim3(grid_for(19 * p2, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Ienc3, sg.e2, sc.E2, sc.E2, 19, H2, W2, H4, W4);
     // enc2: G_e1 (in B)
-    if (want_params) hgb_wgrad<38, 0, 19, HGB_POOL, 9>(st, sc.E2, sg.e1, nullptr, sc.partial, grad_enc2_w, grad_enc2_b, H2, W2, H, W);
+    if (want_params) hgb_wgrad<38, 0, 19, HG_POOL, 9>(st, sc.E2, sg.e1, nullptr, sc.partial, grad_enc2_w, grad_enc2_b, H2, W2, H, W);
     hgb_dgrad<19, 38>(st, sc.E2, enc2_w, 38, 0, sc.Ienc2, nullptr, nullptr, H2, W2);
     hipLaunchKernelGGL(hgb_unpool_kernel, dim3(grid_for(38 * p1, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Ienc2, sg.e1, sc.B, sc.B, 38, H, W, H2, W2);
     // enc1
-    if (want_params) hgb_wgrad<38, 0, 38, HGB_PLAIN, 9>(st, sc.B, x, nullptr, sc.partial, grad_enc1_w, grad_enc1_b, H, W, H, W);
+    if (want_params) hgb_wgrad<38, 0, 38, HG_PLAIN, 9>(st, sc.B, x, nullptr, sc.partial, grad_enc1_w, grad_enc1_b, H, W, H, W);
     if (want_x) hgb_dgrad<38, 38>(st, sc.B, enc1_w, 38, 0, grad_x, grad_x, nullptr, H, W);
     IBGS_HIP(hipGetLastError());
     return 0;

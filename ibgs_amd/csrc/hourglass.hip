@@ -27,6 +27,7 @@
 // k of the weights 49: the lanes of a half-wave read disjoint banks but for one.
 // What bounds it and what was measured: DESIGN.md section 15.
 #include "common.h"
+#include "shared/hg_net.h"
 #include "../../include/ibgs_hourglass.h"
 
 namespace ibgs {
@@ -40,18 +41,9 @@ constexpr int HG_ROWS = HG_TILE / HG_WAVES;          // rows of the tile per wav
 constexpr int HG_WIN = HG_TILE + 2;                  // the staged window: tile and halo
 constexpr int HG_PLANE = 336;                        // floats per staged channel (18 x 18 = 324, padded to 16 mod 32)
 constexpr int HG_QC = 2;                             // groups of four input channels per staged chunk
-constexpr int HG_C = IBGS_HG_CHANNELS;
-enum { HG_PLAIN = 0, HG_POOL = 1, HG_UP = 2 };
 static_assert(HG_ROWS == 4 && HG_WIN * HG_WIN <= HG_PLANE && HG_PLANE % 32 == 16, "the lane maps and the bank argument below");
 
 __device__ __forceinline__ f32x4 hg_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ float hg_blend(float burned, float render, float residual)
-{
-#pragma clang fp contract(off)
-    const float scaled = burned * render;          // rounded before the sum: torch's two kernels
-    return scaled + residual;
-}
 
 // channel c of x (planes of h x w) at (y, x); zero outside the frame
 __device__ __forceinline__ float hg_read_plain(const float* __restrict__ src, int c, int y, int x, int h, int w)
@@ -282,34 +274,6 @@ __global__ void __launch_bounds__(HG_THREADS, 2) hg_conv3_kernel(const HgArgs a)
     }
 }
 
-// who == nullptr: silent (the size query)
-static bool hg_shape_ok(const char* who, int64_t H, int64_t W)
-{
-    if (H < IBGS_HG_MIN_SIDE || W < IBGS_HG_MIN_SIDE || H > IBGS_HG_MAX_SIDE || W > IBGS_HG_MAX_SIDE) {
-        if (who) set_error("%s: a frame of %lld x %lld is out of range (sides %d .. %d)", who, (long long)H, (long long)W, IBGS_HG_MIN_SIDE, IBGS_HG_MAX_SIDE);
-        return false;
-    }
-    return true;
-}
-
-struct HgScratch {          // the arena of the header, in its order
-    float *e1, *e2, *b, *u2, *d2, *u1;
-    static HgScratch carve(char* base, size_t H, size_t W, size_t* total)
-    {
-        const size_t p1 = H * W, p2 = (H / 2) * (W / 2), p4 = (H / 4) * (W / 4);
-        HgScratch s;
-        Carver c(base);
-        s.e1 = c.take<float>(38 * p1);
-        s.e2 = c.take<float>(19 * p2);
-        s.b = c.take<float>(9 * p4);
-        s.u2 = c.take<float>(19 * p2);
-        s.d2 = c.take<float>(19 * p2);
-        s.u1 = c.take<float>(38 * p1);
-        if (total) *total = ((c.cur + 127) & ~uintptr_t(127)) - reinterpret_cast<uintptr_t>(base);
-        return s;
-    }
-};
-
 template <int CA, int CB, int COUT, int MODE, bool FUSE>
 static void hg_launch(hipStream_t st, const HgArgs& a)
 {
@@ -332,10 +296,10 @@ extern "C" {
 
 size_t ibgs_hg_required_scratch(int64_t H, int64_t W)
 {
-    size_t total = 0;
     if (!hg_shape_ok(nullptr, H, W)) return 0;
-    HgScratch::carve(nullptr, (size_t)H, (size_t)W, &total);
-    return total;
+    Carver c(nullptr);
+    hg_carve_stages<float>(c, (size_t)H, (size_t)W, 1);
+    return hg_carved_bytes(c, nullptr);
 }
 
 int32_t ibgs_hg_forward(void* stream, int32_t H, int32_t W, const float* x, const float* enc1_w, const float* enc1_b, const float* enc2_w,
@@ -344,17 +308,15 @@ int32_t ibgs_hg_forward(void* stream, int32_t H, int32_t W, const float* x, cons
                         const float* dec1_b, const float* fuse_input_w, const float* fuse_input_b, const float* final_w, const float* final_b,
                         float burned_in_gauss, float* residual, float* image_pred, void* scratch, size_t scratch_bytes)
 {
-    size_t need = 0;
     if (!hg_shape_ok("hg_forward", H, W)) return -IBGS_ERR_INVALID;
     if (!x) { set_error("hg_forward: null input"); return -IBGS_ERR_INVALID; }
     const float* const params[18] = {enc1_w, enc1_b, enc2_w, enc2_b, enc3_w, enc3_b, up2_conv_w, up2_conv_b, dec2_w, dec2_b, up1_conv_w, up1_conv_b, dec1_w, dec1_b,
                                      fuse_input_w, fuse_input_b, final_w, final_b};
-    static const char* const names[9] = {"enc1", "enc2", "enc3", "up2_conv", "dec2", "up1_conv", "dec1", "fuse_input", "final"};
-    for (int i = 0; i < 18; ++i)
-        if (!params[i]) { set_error("hg_forward: null parameters: %s's %s", names[i / 2], i & 1 ? "bias" : "weight"); return -IBGS_ERR_INVALID; }
+    if (!hg_params_ok("hg_forward", params)) return -IBGS_ERR_INVALID;
     if (!residual) { set_error("hg_forward: null outputs: residual is required"); return -IBGS_ERR_INVALID; }
-    const HgScratch sc = HgScratch::carve(static_cast<char*>(scratch), (size_t)H, (size_t)W, &need);
-    if (!arena_ok("hg_forward", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
+    Carver c(static_cast<char*>(scratch));
+    const HgStages<float> sc = hg_carve_stages<float>(c, (size_t)H, (size_t)W, 1);          // the arena of the header: float32 planes
+    if (!arena_ok("hg_forward", "scratch", scratch, scratch_bytes, hg_carved_bytes(c, scratch))) return -IBGS_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
     hg_launch<38, 0, 38, HG_PLAIN, false>(st, hg_layer(x, nullptr, enc1_w, enc1_b, sc.e1, H, W, H, W));

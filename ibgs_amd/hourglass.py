@@ -35,15 +35,21 @@ for _name, _, _, _ in LAYERS:
 STAGES = (("e1", C, 0), ("e2", C // 2, 1), ("b", C // 4, 2), ("u2", C // 2, 1), ("d2", C // 2, 1), ("u1", C, 0))
 
 
-def _stage_views(arena, h, w):
+def _arena_views(arena, h, w, half=False):
+    """The six stages inside the arena of a forward, (channels, h, w) views each: float32 planes (include/ibgs_hourglass.h), or with `half` pixel-major binary16
+    with the channels padded to a multiple of 8, after h(x) (include/ibgs_hg_half.h).  Every entry starts at the next multiple of 128 bytes."""
     sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
+    dtype, size, pad = (torch.float16, 2, 8) if half else (torch.float32, 4, 1)
     out, at = {}, 0
-    for name, ch, level in STAGES:
+    for name, ch, level in ((("xh", C, 0),) if half else ()) + STAGES:
         hh, ww = sides[level]
         at = (at + 127) // 128 * 128
-        n = ch * hh * ww * 4
-        out[name] = arena[at:at + n].view(torch.float32).view(ch, hh, ww)
+        cp = (ch + pad - 1) // pad * pad
+        n = cp * hh * ww * size
+        flat = arena[at:at + n].view(dtype)
+        out[name] = flat.view(hh, ww, cp).permute(2, 0, 1)[:ch] if half else flat.view(ch, hh, ww)
         at += n
+    out.pop("xh", None)
     return out
 
 
@@ -53,21 +59,6 @@ PRECISIONS = ("float32", "float16")
 def _check_precision(name, precision):
     if precision not in PRECISIONS:
         raise ValueError("%s: precision must be \"float32\" or \"float16\", got %r" % (name, precision))
-
-
-def _stage_views_half(arena, h, w):
-    """The half-precision arena (include/ibgs_hg_half.h): h(x), then the six stages, pixel-major binary16 with the channels padded to a multiple of 8."""
-    sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
-    out, at = {}, 0
-    for name, ch, level in (("xh", C, 0),) + STAGES:
-        hh, ww = sides[level]
-        at = (at + 127) // 128 * 128
-        cp = (ch + 7) // 8 * 8
-        n = cp * hh * ww * 2
-        out[name] = arena[at:at + n].view(torch.float16).view(hh, ww, cp).permute(2, 0, 1)[:ch]
-        at += n
-    del out["xh"]
-    return out
 
 
 def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False, precision="float32"):
@@ -85,6 +76,24 @@ def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False,
     torch's CNN behind coloragg.fuse_color_inputs.  Nothing waits for the host."""
     name = "hourglass_forward"
     _check_precision(name, precision)
+    x, h, w, tensors = _checked(name, cnn_input, params)
+    if render_scale is not None:
+        render_scale = float(render_scale)
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for _, t in tensors)):
+        raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
+                           "torch's CNN behind coloragg.fuse_color_inputs" % name)
+    _on_one_device(name, x, tensors)
+    half = precision == "float16"
+    arena = _device.scratch(x.device, (_lib.load().ibgs_hgh_required_scratch if half else _lib.load().ibgs_hg_required_scratch)(h, w))
+    residual, image_pred = _forward_call(x.device, h, w, _f32(x), [_f32(t) for _, t in tensors], render_scale, arena, half)
+    out = (residual,) if image_pred is None else (residual, image_pred)
+    if return_stages:
+        out += (_arena_views(arena, h, w, half),)
+    return out[0] if len(out) == 1 else out
+
+
+def _checked(name, cnn_input, params):
+    """The checks of types and shapes that every entry point makes first.  -> (x (38, H, W), h, w, [(name, parameter)] in the C ABI's order)"""
     if not isinstance(params, HourglassCNN):
         raise TypeError("%s: params must be a HourglassCNN, got %s" % (name, type(params).__name__))
     if not torch.is_tensor(cnn_input):
@@ -108,31 +117,27 @@ def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False,
         if tuple(bt.shape) != (cout,):
             raise ValueError("%s: %s_b must be %s, got %s" % (name, layer, (cout,), tuple(bt.shape)))
         tensors += [(layer + "_w", wt), (layer + "_b", bt)]
-    if render_scale is not None:
-        render_scale = float(render_scale)
-    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for _, t in tensors)):
-        raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
-                           "torch's CNN behind coloragg.fuse_color_inputs" % name)
+    return x, h, w, tensors
+
+
+def _on_one_device(name, x, tensors):
+    """... and the checks that come last (after the forward-only refusal, where there is one): nothing on the CPU, everything on x's device."""
     _device.refuse_cpu("hourglass", "%s's cnn_input" % name, x)
     for what, t in tensors:
         _device.refuse_cpu("hourglass", "%s's %s" % (name, what), t)
-    dev = x.device
     for what, t in tensors:
-        if t.device != dev:
-            raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, dev, what, t.device))
-    x = _f32(x)
-    flat = [_f32(t) for _, t in tensors]
+        if t.device != x.device:
+            raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, x.device, what, t.device))
+
+
+def _forward_call(dev, h, w, x, flat, render_scale, arena, half=False):
+    """x, flat: float32, contiguous, on dev; arena: that of the precision's C ABI, at least its required size.  -> (residual, image_pred or None)"""
     with torch.cuda.device(dev):
         residual = torch.empty((3, h, w), dtype=torch.float32, device=dev)
         image_pred = torch.empty((3, h, w), dtype=torch.float32, device=dev) if render_scale is not None else None
-    half = precision == "float16"
-    arena = _device.scratch(dev, (_lib.load().ibgs_hgh_required_scratch if half else _lib.load().ibgs_hg_required_scratch)(h, w))
-    _device.call(dev, "ibgs_hgh_forward" if half else "ibgs_hg_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if render_scale is None else render_scale, residual.data_ptr(),
-                 None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
-    out = (residual,) if image_pred is None else (residual, image_pred)
-    if return_stages:
-        out += ((_stage_views_half if half else _stage_views)(arena, h, w),)
-    return out[0] if len(out) == 1 else out
+    _device.call(dev, "ibgs_hgh_forward" if half else "ibgs_hg_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if render_scale is None else render_scale,
+                 residual.data_ptr(), None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
+    return residual, image_pred
 
 
 class HourglassCNN(nn.Module):
@@ -215,17 +220,7 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     Forward only: call it under torch.no_grad()."""
     name = "fuse_color"
     _check_precision(name, precision)
-    if not isinstance(net, ColorAggregationNet):
-        raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
-    for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
-        if key not in render_pkg:
-            raise KeyError("%s: render_pkg lacks %r" % (name, key))
-    render = render_pkg["render"]
-    if not torch.is_tensor(render) or render.dim() != 3 or render.shape[0] != 3:
-        raise ValueError("%s: render_pkg['render'] must be a (3, H, W) tensor" % name)
-    h, w = int(render.shape[1]), int(render.shape[2])
-    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
-        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    render, h, w = _checked_package(name, render_pkg, net)
     reduced = None
     if residual_resolution_scale != 1:
         reduced = scaled_size(h, w, residual_resolution_scale)
@@ -235,9 +230,7 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     if torch.is_grad_enabled() and (any(torch.is_tensor(v) and v.requires_grad for v in render_pkg.values()) or any(p.requires_grad for p in net.parameters())):
         raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training keeps "
                            "torch's CNN behind coloragg.fuse_color_inputs" % name)
-    camera_ray = render_pkg["camera_ray"]
-    if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
-        camera_ray = camera_ray.view(3, h, w)
+    camera_ray = _ray_planes(render_pkg["camera_ray"], h, w)
     warped = render_pkg["warped_image"]
     exposure = {}
     if enable_exposure_correction:
@@ -254,47 +247,42 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
         residual, image_pred = hourglass_forward(cnn_input, net.cnn, render_scale=float(burned_in_gauss), precision=precision)
     else:
         residual, image_pred = upsample_residual(hourglass_forward(cnn_input, net.cnn, precision=precision), render, float(burned_in_gauss))
+    return _fused(image_pred, residual, render_pkg["min_depth_diff"], float(burned_in_gauss), levels, warped, nb_visible_src_frames, exposure)
+
+
+def _checked_package(name, render_pkg, net):
+    """The checks `fuse_color` and `fuse_color_train` make first.  -> (render, H, W)"""
+    if not isinstance(net, ColorAggregationNet):
+        raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
+    for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
+        if key not in render_pkg:
+            raise KeyError("%s: render_pkg lacks %r" % (name, key))
+    render = render_pkg["render"]
+    if not torch.is_tensor(render) or render.dim() != 3 or render.shape[0] != 3:
+        raise ValueError("%s: render_pkg['render'] must be a (3, H, W) tensor" % name)
+    h, w = int(render.shape[1]), int(render.shape[2])
+    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
+        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    return render, h, w
+
+
+def _ray_planes(camera_ray, h, w):
+    """render()'s (3, H W) rays as planes; anything else is left to the front end"""
+    if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
+        return camera_ray.view(3, h, w)
+    return camera_ray
+
+
+def _fused(image_pred, residual, min_depth_diff, burned, levels, warped, nb_visible_src_frames, exposure):
+    """The dictionary `fuse_color` and `fuse_color_train` return"""
+    h, w = residual.shape[1:]
     slots = warped.reshape(-1, 3, h, w)
     slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
-    return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (render_pkg["min_depth_diff"] < 0.999).float(),
-            "burned_in_gauss": float(burned_in_gauss), "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1), **exposure}
+    return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (min_depth_diff < 0.999).float(), "burned_in_gauss": burned,
+            "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1), **exposure}
 
 
 # ---- training: the backward (C ABI include/ibgs_hg_train.h, csrc/hgtrain.hip) --------------------------------------------------------------------------------
-def _checked(name, cnn_input, params):
-    """The argument checks of `hourglass_forward`, for the training entry points.  -> (x (38, H, W), h, w, [(name, parameter)] in the C ABI's order)"""
-    if not isinstance(params, HourglassCNN):
-        raise TypeError("%s: params must be a HourglassCNN, got %s" % (name, type(params).__name__))
-    if not torch.is_tensor(cnn_input):
-        raise TypeError("%s: cnn_input must be a tensor" % name)
-    x = cnn_input
-    if x.dim() == 4 and x.shape[0] == 1:
-        x = x[0]
-    if x.dim() != 3:
-        raise ValueError("%s: cnn_input must be (1, %d, H, W) or (%d, H, W), got %s" % (name, C, C, tuple(cnn_input.shape)))
-    if x.shape[0] != C:
-        raise ValueError("%s: cnn_input has %d channels, which implies hidden_dim = %d; the kernels have hidden_dim = %d only (32 per-view features + ray + colour)"
-                         % (name, x.shape[0], x.shape[0], C))
-    h, w = int(x.shape[1]), int(x.shape[2])
-    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
-        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d: the bottleneck is a quarter of the frame)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
-    tensors = []
-    for layer, cout, cin, k in LAYERS:
-        wt, bt = getattr(params, layer + "_w"), getattr(params, layer + "_b")
-        if tuple(wt.shape) != (cout, cin, k, k):
-            raise ValueError("%s: %s_w must be %s, got %s" % (name, layer, (cout, cin, k, k), tuple(wt.shape)))
-        if tuple(bt.shape) != (cout,):
-            raise ValueError("%s: %s_b must be %s, got %s" % (name, layer, (cout,), tuple(bt.shape)))
-        tensors += [(layer + "_w", wt), (layer + "_b", bt)]
-    _device.refuse_cpu("hourglass", "%s's cnn_input" % name, x)
-    for what, t in tensors:
-        _device.refuse_cpu("hourglass", "%s's %s" % (name, what), t)
-    for what, t in tensors:
-        if t.device != x.device:
-            raise ValueError("%s: cnn_input is on %s, %s on %s" % (name, x.device, what, t.device))
-    return x, h, w, tensors
-
-
 def _backward_call(dev, h, w, x, flat, burned, arena, g_res, g_ip, need_x, need_params):
     """x, flat, g_res, g_ip: float32, contiguous, on dev; arena: the owned stages arena.  -> (grad_x (38, h, w) or None, [18 gradients] or None)"""
     ptr = lambda t: None if t is None else t.data_ptr()
@@ -327,6 +315,7 @@ def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image
     bits; nothing waits for the host and no argument is written.  It refuses what `hourglass_forward` refuses."""
     name = "hourglass_backward"
     x, h, w, tensors = _checked(name, cnn_input, params)
+    _on_one_device(name, x, tensors)
     dev = x.device
     if grad_residual is None and grad_image_pred is None:
         raise ValueError("%s: grad_residual and grad_image_pred are both None" % name)
@@ -338,7 +327,7 @@ def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image
     if isinstance(stages, dict):
         sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
         arena = _device.scratch(dev, need)
-        views = _stage_views(arena, h, w)
+        views = _arena_views(arena, h, w)
         for stage, ch, level in STAGES:
             if stage not in stages or not torch.is_tensor(stages[stage]) or tuple(stages[stage].shape[-3:]) != (ch,) + sides[level] or stages[stage].numel() != views[stage].numel():
                 raise ValueError("%s: stages[%r] must be a (%d, %d, %d) tensor" % (name, stage, ch, sides[level][0], sides[level][1]))
@@ -363,12 +352,8 @@ class _HourglassTrain(torch.autograd.Function):
         dev = x.device
         x32 = _f32(x).view(C, h, w)
         flat = [_f32(t) for t in params]
-        with torch.cuda.device(dev):
-            residual = torch.empty((3, h, w), dtype=torch.float32, device=dev)
-            image_pred = torch.empty((3, h, w), dtype=torch.float32, device=dev) if burned is not None else None
-            arena = torch.empty(_lib.load().ibgs_hg_required_scratch(h, w), dtype=torch.uint8, device=dev)          # owned: the backward reads it
-        _device.call(dev, "ibgs_hg_forward", h, w, x32.data_ptr(), *[t.data_ptr() for t in flat], 1.0 if burned is None else burned, residual.data_ptr(),
-                     None if image_pred is None else image_pred.data_ptr(), arena.data_ptr(), arena.numel())
+        arena = torch.empty(_lib.load().ibgs_hg_required_scratch(h, w), dtype=torch.uint8, device=dev)          # owned: the backward reads it
+        residual, image_pred = _forward_call(dev, h, w, x32, flat, burned, arena)
         ctx.dims, ctx.burned, ctx.x_shape, ctx.x_dtype = dims, burned, x.shape, x.dtype
         ctx.set_materialize_grads(False)          # an output nobody used arrives as None, not as a plane of zeros
         ctx.save_for_backward(x32, arena, *flat)
@@ -405,6 +390,7 @@ def hourglass_train(cnn_input, params, render_scale=None):
     CNN: no weight gradient runs; a detached input: no enc1 input gradient).  Double backward raises.  Nothing waits for the host."""
     name = "hourglass_train"
     x, h, w, tensors = _checked(name, cnn_input, params)
+    _on_one_device(name, x, tensors)
     if render_scale is not None:
         render_scale = float(render_scale)
     return _HourglassTrain.apply(cnn_input, (h, w), render_scale, *[t for _, t in tensors])
@@ -419,17 +405,7 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
     `enable_exposure_correction`: as in `fuse_color`, after the detaching, in the reference's order; "render" receives its gradient through the correction
     (the affine map is a constant of the backward), "warped_image" only the front end's.  Without the keyword every bit and every key is what it was."""
     name = "fuse_color_train"
-    if not isinstance(net, ColorAggregationNet):
-        raise TypeError("%s: net must be a ColorAggregationNet, got %s" % (name, type(net).__name__))
-    for key in ("render", "warped_image", "cam_feat", "camera_ray", "min_depth_diff"):
-        if key not in render_pkg:
-            raise KeyError("%s: render_pkg lacks %r" % (name, key))
-    render = render_pkg["render"]
-    if not torch.is_tensor(render) or render.dim() != 3 or render.shape[0] != 3:
-        raise ValueError("%s: render_pkg['render'] must be a (3, H, W) tensor" % name)
-    h, w = int(render.shape[1]), int(render.shape[2])
-    if min(h, w) < _lib.HG_MIN_SIDE or max(h, w) > _lib.HG_MAX_SIDE:
-        raise ValueError("%s: a frame of %d x %d is out of range (sides %d .. %d)" % (name, h, w, _lib.HG_MIN_SIDE, _lib.HG_MAX_SIDE))
+    render, h, w = _checked_package(name, render_pkg, net)
     if iter_count is None or burn_start is None or burn_end is None:
         burned = 1.0
     else:
@@ -437,8 +413,7 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
     warped, cam_feat, camera_ray, min_depth_diff = render_pkg["warped_image"], render_pkg["cam_feat"], render_pkg["camera_ray"], render_pkg["min_depth_diff"]
     if burned < 1.0:          # the gradients to the Gaussians are blocked while the residual is not fully used
         render, warped, cam_feat, camera_ray, min_depth_diff = (t.detach() for t in (render, warped, cam_feat, camera_ray, min_depth_diff))
-    if torch.is_tensor(camera_ray) and camera_ray.numel() == 3 * h * w:
-        camera_ray = camera_ray.view(3, h, w)
+    camera_ray = _ray_planes(camera_ray, h, w)
     exposure = {}
     if enable_exposure_correction:
         render, exposure["exposure_affine"], exposure["exposure_fit_ok"] = correct_package(name, render_pkg, render, warped)
@@ -446,7 +421,4 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
     if none_if_no_level and int(levels.item()) == 0:
         return None
     residual, image_pred = hourglass_train(cnn_input, net.cnn, render_scale=burned)
-    slots = warped.reshape(-1, 3, h, w)
-    slots = slots[:min(int(nb_visible_src_frames), slots.shape[0])]
-    return {"image_pred": image_pred, "residual": residual, "valid_warp_mask": (min_depth_diff < 0.999).float(), "burned_in_gauss": burned,
-            "nb_valid_warp_level": levels, "warped_image_list": slots.permute(2, 3, 0, 1), **exposure}
+    return _fused(image_pred, residual, min_depth_diff, burned, levels, warped, nb_visible_src_frames, exposure)

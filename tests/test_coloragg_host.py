@@ -66,10 +66,10 @@ def test_kernels_attributed_to_the_coloragg_unit():
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if "coloragg" in f and not f.startswith("_")) == ["coloragg.hip"]
     assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp.h", "../../include/ibgs_color_agg.h"]
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["pv_mlp.h", "ssim_window.h"]
+    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["hg_net.h", "pv_mlp.h", "ssim_window.h"]
     for unit, header in (("coloragg", "pv_mlp.h"), ("resample", "pv_mlp.h"), ("ssim", "ssim_window.h"), ("geoloss", "ssim_window.h")):
         assert [os.path.basename(h) for h in _build.UNIT_HEADERS[unit]][1:] == [header], unit
-    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 4          # no other unit's stamp holds them
+    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 7          # no other unit's stamp holds them
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

@@ -190,7 +190,7 @@ def test_exact_properties():
         ip = torch.full((3, h, w), float("nan"), device="cuda")
         _device.call(x.device, "ibgs_hgh_forward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], 0.75, r.data_ptr(), ip.data_ptr(), arena.data_ptr(), arena.numel())
         torch.cuda.synchronize()
-        st = hourglass._stage_views_half(arena, h, w)
+        st = hourglass._arena_views(arena, h, w, half=True)
         assert torch.equal(r, plain) and torch.equal(ip, image_pred) and all(torch.equal(st[k], side_stages[k]) for k in ref.STAGES)
         assert not bool(torch.isnan(r).any()) and not bool(torch.isnan(ip).any()) and not any(bool(torch.isnan(v).any()) for v in st.values())
         e1_all = arena[st["e1"].data_ptr() - arena.data_ptr():][:h * w * 40 * 2].view(torch.float16).view(h, w, 40)          # the padding channels: zeros

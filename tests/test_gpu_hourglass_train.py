@@ -228,7 +228,7 @@ def test_exact_properties():
     with pytest.raises(ValueError, match="both None"):
         hourglass.hourglass_backward(xd, net, arena)
     # a dict of the stages is packed into the same arena
-    a, b = hourglass.hourglass_backward(xd, net, hourglass._stage_views(arena, h, w), g_res, g_ip, render_scale=0.75)
+    a, b = hourglass.hourglass_backward(xd, net, hourglass._arena_views(arena, h, w), g_res, g_ip, render_scale=0.75)
     assert torch.equal(a, gx) and all(torch.equal(b[k], gp[k]) for k in NAMES)
     torch.cuda.synchronize()
     assert torch.equal(arena, arena0) and torch.equal(xd, x0) and all(torch.equal(q, q0) for q, q0 in zip(net.parameters(), p0))
@@ -239,6 +239,21 @@ def test_exact_properties():
     (gx_graph,) = torch.autograd.grad(r2, x2, g_res, create_graph=True)
     with pytest.raises(RuntimeError):
         gx_graph.sum().backward()
+
+
+@pytest.mark.parametrize("h,w", [(5, 7), (17, 67)])
+def test_writer_reader_and_views_share_one_layout(h, w):
+    """The six stages `hourglass_forward` returns -- the Python views of the arena its kernels wrote, cloned -- handed to `hourglass_backward` as a dict give, bit
+    for bit, the gradients autograd obtains through `hourglass_train`, whose backward reads the forward's arena as it lies: the forward's carve, the
+    backward's and hourglass._arena_views are one layout (csrc/shared/hg_net.h; odd sides: the H / 2 / 2 rounding)."""
+    c = _case(h, w, "default")
+    got, (x, net, _, _) = _autograd(c, "default")
+    with torch.no_grad():
+        _, _, views = hourglass.hourglass_forward(x.detach(), net, render_scale=c["burned"], return_stages=True)
+        stages = {k: v.clone() for k, v in views.items()}
+    assert list(stages) == [n for n, _, _ in hourglass.STAGES]
+    gx, gp = hourglass.hourglass_backward(x.detach(), net, stages, _dev(c["g_res"]), _dev(c["g_ip"]), render_scale=c["burned"])
+    assert torch.equal(gx, got["x"].reshape(gx.shape)) and all(torch.equal(gp[k], got[k]) for k in NAMES)
 
 
 # ---- 5. pruning ------------------------------------------------------------------------------------------------------------------------------------------------

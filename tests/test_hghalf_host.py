@@ -13,6 +13,7 @@ import torch
 from ibgs_amd import _build, _lib, hourglass
 from tests import hghalf_ref as href
 from tests import hourglass_ref as ref
+from tests.test_hourglass_host import _layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ibgs_amd", "csrc", "hghalf.hip")
@@ -59,7 +60,7 @@ def test_build_registration_and_the_kernels():
     assert _build.SOURCES[-1] == "hourglass" and _build.SOURCES.index("hghalf") < _build.SOURCES.index("hourglass")
     assert "hghalf" in _build.UNIT_HEADERS and "hghalf" in _build.tu_shas() and "hghalf" not in _build.EXTRA
     assert _build.compile_flags("hghalf") == _build.compile_flags("hourglass")
-    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h"]
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h"]
     assert all(os.path.exists(h) for h in _build.UNIT_HEADERS["hghalf"])
     # the float32 unit's kernel still goes where it went
     assert _build.tu_of("hg_conv3_kernel") == "hourglass" and _build.tu_of("hgb_wgrad_kernel") == "hgtrain"
@@ -71,30 +72,19 @@ def test_build_registration_and_the_kernels():
     assert re.search(r"constexpr int HGH_TILE = 16;", code) and re.search(r"constexpr int HGH_THREADS = 256;", code)
     assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ HGH_TILE - 1\) / HGH_TILE\), \(unsigned\)\(\(a\.h \+ HGH_TILE - 1\) / HGH_TILE\)\);", code)
     assert len(re.findall(r"hgh_launch<", code)) == 7 and len(re.findall(r"hipLaunchKernelGGL\(hgh_pack_kernel", code)) == 1
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h"]
-
-
-def _layout(h, w):
-    at, offs = 0, {}
-    sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
-    for name, cp, level in (("xh", 40, 0), ("e1", 40, 0), ("e2", 24, 1), ("b", 16, 2), ("u2", 24, 1), ("d2", 24, 1), ("u1", 40, 0)):
-        at = (at + 127) // 128 * 128
-        offs[name] = at
-        at += 2 * cp * sides[level][0] * sides[level][1]
-    at = (at + 127) // 128 * 128 + _lib.HGH_PACKED_WEIGHT_BYTES
-    return (at + 127) // 128 * 128, offs
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h"]
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):
     need = built_lib.ibgs_hgh_required_scratch
     assert _lib.HGH_PACKED_WEIGHT_BYTES == 17600 * 16
     for h, w in ((4, 4), (5, 7), (16, 24), (17, 67), (1080, 1920), (8192, 8192), (4, 8192)):
-        total, offs = _layout(h, w)
+        total, offs = _layout(h, w, half=True)
         assert need(h, w) == total and total % 128 == 0, (h, w)
         if h * w > 1 << 22:
             continue
-        views = hourglass._stage_views_half(torch.empty(total, dtype=torch.uint8), h, w)
-        assert [n for n, _, _ in hourglass.STAGES] == list(views) == [n for n in offs if n != "xh"]
+        views = hourglass._arena_views(torch.empty(total, dtype=torch.uint8), h, w, half=True)
+        assert [n for n, _, _ in hourglass.STAGES] == list(views) == [n for n in offs if n not in ("xh", "packed")]
         base = views["e1"].untyped_storage().data_ptr()
         for (n, ch, level), v in zip(hourglass.STAGES, views.values()):
             cp = (ch + 7) // 8 * 8

@@ -16,6 +16,7 @@ from tests import hourglass_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ibgs_amd", "csrc", "hourglass.hip")
+NET_H = os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "hg_net.h")          # the network as hourglass.hip, hgtrain.hip and hghalf.hip share it
 GOLDEN = os.path.join(ROOT, "tests", "golden", "hourglass.npz")
 
 
@@ -76,17 +77,55 @@ def test_kernels_attributed_to_the_hourglass_unit():
     assert len(re.findall(r"hg_launch<", code)) == 7          # seven launches
     assert "mfma_f32_16x16x4f32" in code
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if "hourglass" in f and not f.startswith("_")) == ["hourglass.hip"]
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "../../include/ibgs_hourglass.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "../../include/ibgs_hourglass.h"]
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hourglass"]] == ["ibgs_hourglass.h", "hg_net.h"]
+    shared = _build._code_only(open(NET_H).read())
+    assert re.search(r"enum \{ HG_PLAIN = 0, HG_POOL = 1, HG_UP = 2 \};", shared) and re.search(r"constexpr int HG_C = IBGS_HG_CHANNELS;", shared)
+    for unit in ("hourglass", "hgtrain", "hghalf"):          # ... and nobody keeps a copy of what the header holds
+        code = _build._code_only(open(os.path.join(ROOT, "ibgs_amd", "csrc", unit + ".hip")).read())
+        assert not re.search(r"_PLAIN = 0|_shape_ok\(const char|names\[9\]|_blend\(float", code), unit
 
 
-def _layout(h, w):
+def test_layer_table_of_the_shared_header_is_LAYERS():
+    """(name, Cout, Ca, Cb, kernel side, level of the output) in csrc/shared/hg_net.h against hourglass.LAYERS and, for the six layers whose output is kept,
+    hourglass.STAGES."""
+    code = _build._code_only(open(NET_H).read())
+    table = re.search(r"HG_LAYERS\[HG_LAYER_COUNT\] = \{(.*?)\};", code, re.S).group(1)
+    rows = [(n,) + tuple(int(v) for v in rest.split(",")) for n, rest in re.findall(r'\{"(\w+)",([\d,\s]+)\}', table)]
+    assert [(n, cout, ca + cb, side) for n, cout, ca, cb, side, _ in rows] == list(hourglass.LAYERS)
+    assert [(cout, level) for _, cout, _, _, _, level in rows[:len(hourglass.STAGES)]] == [(ch, level) for _, ch, level in hourglass.STAGES]
+    assert all(level == 0 for *_, level in rows[len(hourglass.STAGES):]) and re.search(r"constexpr int HG_STAGE_COUNT = %d;" % len(hourglass.STAGES), code)
+    ids = re.search(r"enum \{ (HG_ENC1,.*?), HG_LAYER_COUNT \};", code).group(1).split(", ")
+    assert [i[3:].lower() for i in ids] == [n for n, _, _, _ in hourglass.LAYERS]
+    # a concatenation's halves are its two inputs' channels: dec2 reads [u2, e2], dec1 [u1, e1], fuse_input [d1, x]
+    assert [(n, ca, cb) for n, _, ca, cb, _, _ in rows if cb] == [("dec2", 19, 19), ("dec1", 38, 38), ("fuse_input", 38, 38)]
+
+
+def _layout(h, w, half=False):
+    """The documented arenas (include/ibgs_hourglass.h; half: include/ibgs_hg_half.h) from hourglass.STAGES: the one statement of the layout the tests hold
+    the library's sizes and hourglass._arena_views against.  -> (bytes, {entry: offset})"""
+    assert hourglass.STAGES == (("e1", 38, 0), ("e2", 19, 1), ("b", 9, 2), ("u2", 19, 1), ("d2", 19, 1), ("u1", 38, 0))
+    size, pad = (2, 8) if half else (4, 1)
+    entries = [(name, (ch + pad - 1) // pad * pad * (h >> level) * (w >> level) * size) for name, ch, level in ((("xh", 38, 0),) if half else ()) + hourglass.STAGES]
     at, offs = 0, {}
-    sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
-    for name, ch, level in (("e1", 38, 0), ("e2", 19, 1), ("b", 9, 2), ("u2", 19, 1), ("d2", 19, 1), ("u1", 38, 0)):
-        at = (at + 127) // 128 * 128
-        offs[name] = at
-        at += 4 * ch * sides[level][0] * sides[level][1]
+    for name, n in entries + ([("packed", _lib.HGH_PACKED_WEIGHT_BYTES)] if half else []):
+        offs[name] = at = (at + 127) // 128 * 128
+        at += n
     return (at + 127) // 128 * 128, offs
+
+
+@pytest.mark.parametrize("h,w", [(4, 4), (5, 7), (17, 67), (4, 8192), (8192, 8192)])
+def test_one_layout_for_both_arenas_and_their_views(built_lib, h, w):
+    """Odd sides: the H / 2 / 2 rounding; the extremes: size_t (the float32 arena of 8192 x 8192 is 2^34.7 bytes).  The views are taken of a meta tensor."""
+    for half, need in ((False, built_lib.ibgs_hg_required_scratch), (True, built_lib.ibgs_hgh_required_scratch)):
+        total, offs = _layout(h, w, half)
+        assert need(h, w) == total and total % 128 == 0 and all(o % 128 == 0 for o in offs.values()), (h, w, half)
+        views = hourglass._arena_views(torch.empty(total, dtype=torch.uint8, device="meta"), h, w, half)
+        assert list(views) == [n for n, _, _ in hourglass.STAGES] == [n for n in offs if n not in ("xh", "packed")]
+        for (n, ch, level), v in zip(hourglass.STAGES, views.values()):
+            assert v.storage_offset() * v.element_size() == offs[n] and tuple(v.shape) == (ch, h >> level, w >> level), (h, w, half, n)
+            assert v.dtype == (torch.float16 if half else torch.float32), (h, w, half, n)
+    assert (8192 * 8192 * 38 * 4 > 1 << 33) and built_lib.ibgs_hg_required_scratch(8192, 8192) > 1 << 34
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):
@@ -94,7 +133,7 @@ def test_sizes_and_validation_before_any_gpu_work(built_lib):
     for h, w in ((4, 4), (5, 7), (16, 24), (17, 67), (1080, 1920), (8192, 8192), (4, 8192)):
         total, offs = _layout(h, w)
         assert need(h, w) == total and total % 128 == 0, (h, w)
-        views = hourglass._stage_views(torch.empty(total, dtype=torch.uint8), h, w)
+        views = hourglass._arena_views(torch.empty(total, dtype=torch.uint8), h, w)
         base = views["e1"].untyped_storage().data_ptr()
         assert [n for n, _, _ in hourglass.STAGES] == list(offs) == list(views)
         for n in offs:
