@@ -14,7 +14,8 @@ these three units), and lpips.hip (LPIPS on VGG16 for the image evaluation: a to
 are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
 the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
 (the reduced-resolution colour tail: a tolerance contract; its blends are written as fmaf, its MLP is the matrix-core chain it shares with coloragg.hip
-(csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves).
+(csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves), and rsztrain.hip (that tail's backward: the same chain, the same
+blends, and a gather whose products and sums say themselves that they are not contracted).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -27,7 +28,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "resample", "lpips", "hgtrain", "hghalf", "hourglass"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "resample", "rsztrain", "lpips", "hgtrain", "hghalf", "hourglass"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -62,7 +63,16 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
                 "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")],
                 "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
-                "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H]}
+                "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H],
+                "rsztrain": [os.path.join(HERE, "..", "include", "ibgs_resample_train.h")]}
+# headers a unit includes besides its own, where UNIT_HEADERS lists only its own: rebuild triggers and part of the unit's stamp exactly like those above
+# (rsztrain.hip runs pv_mlp.h's chain and reads ibgs_resample.h's limits and modes)
+BORROWED_HEADERS = {"rsztrain": [PV_MLP_H, os.path.join(HERE, "..", "include", "ibgs_resample.h")]}
+
+
+def unit_headers(name):
+    """Every header outside csrc/*.h and include/ibgs_rast.h that translation unit `name` includes."""
+    return UNIT_HEADERS.get(name, []) + BORROWED_HEADERS.get(name, [])
 
 
 def _hipcc():
@@ -75,7 +85,7 @@ def _hipcc():
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "..", "include", "ibgs_rast.h"))
-    deps += [h for hs in UNIT_HEADERS.values() for h in hs]
+    deps += [h for name in SOURCES for h in unit_headers(name)]
     return max(os.path.getmtime(d) for d in deps)
 
 
@@ -105,8 +115,8 @@ def csrc_sha():
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning; "dtu_" before "mesh_" and "scan_":
 # a dtu_emit_mesh_* or dtu_scan_* would otherwise go to those units; "lpips_" ahead of every entry that could claim one of its kernels by substring -- all but
-# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel; the same holds for "rsz_")
-KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("rsz_", "resample"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel; the same holds for "rsz_" and "rzt_")
+KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("rsz_", "resample"), ("rzt_", "rsztrain"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))
@@ -131,7 +141,7 @@ def tu_shas():
     for name in SOURCES:
         h = hdr.copy()
         h.update(_code_only(open(os.path.join(CSRC, name + ".hip"), "r").read()).encode())
-        for u in UNIT_HEADERS.get(name, []):
+        for u in unit_headers(name):
             h.update(_code_only(open(u, "r").read()).encode())
         h.update(" ".join(EXTRA.get(name, [])).encode())
         out[name] = h.hexdigest()[:12]
@@ -155,7 +165,7 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(OBJ, name + ".o")
-        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
+        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in unit_headers(name)])
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
         cmd = [hipcc] + compile_flags(name) + ["-c", src, "-o", obj]

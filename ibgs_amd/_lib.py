@@ -247,6 +247,9 @@ RSZ_MAX_SIDE = 65536
 RSZ_FEATURES = 32
 RSZ_MEAN, RSZ_MAX = 0, 1
 
+# every symbol include/ibgs_resample_train.h declares (tests/test_resample_train_host.py compares the two); its limits and modes are ibgs_resample.h's
+RZT_EXPORTS = ["ibgs_rzt_required_scratch", "ibgs_rzt_features_backward", "ibgs_rzt_upsample_backward"]
+
 
 _lib = None
 
@@ -514,6 +517,17 @@ def load():
     lib.ibgs_rsz_residual_upsample.restype = i32
     # (stream, H, W, Hr, Wr, residual_r, render, render_scale, residual_out, image_pred_out)
     lib.ibgs_rsz_residual_upsample.argtypes = [vp, i32, i32, i32, i32, vp, vp, f32, vp, vp]
+    for name in RZT_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_rzt_required_scratch.restype = sz
+    lib.ibgs_rzt_required_scratch.argtypes = [i64] * 5
+    lib.ibgs_rzt_features_backward.restype = i32
+    # (stream, S, H, W, Hr, Wr, mode, render, warped, cam_feat, w1, b1, w2, b2, levels, grad_out, 6 gradients, scratch, bytes)
+    lib.ibgs_rzt_features_backward.argtypes = [vp, i32, i32, i32, i32, i32, i32] + [vp] * 16 + [sz]
+    lib.ibgs_rzt_upsample_backward.restype = i32
+    # (stream, H, W, Hr, Wr, grad_residual_out, grad_image_pred, grad_residual_r)
+    lib.ibgs_rzt_upsample_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.ibgs_grad_acc_offsets_fit32.restype = ctypes.c_int32
     lib.ibgs_grad_acc_offsets_fit32.argtypes = [ctypes.c_int64]
     lib.ibgs_clamp_free.restype = ctypes.c_int32

@@ -215,8 +215,8 @@ def fuse_color(render_pkg, net, nb_visible_src_frames=3, burned_in_gauss=1.0, no
     if asked for, the level count at FULL resolution, `resample.resized_features` (the masked features interpolated, align_corners=True, not the images),
     `hourglass_forward` there in the given `precision`, and `resample.upsample_residual`, which also forms image_pred = burned_in_gauss * render (or the
     corrected image) + residual at H x W.  The dictionary is the same: residual is the upsampled (3, H, W) one, valid_warp_mask and warped_image_list stay
-    at full resolution.  With a value == 1 the code above runs and every bit and every key is what it was.  Training at a reduced resolution is not
-    covered: `fuse_color_train` and `coloragg.fuse_color_inputs` have no such keyword.
+    at full resolution.  With a value == 1 the code above runs and every bit and every key is what it was.  Training at a reduced resolution is
+    `resample_train.fuse_color_train_scaled`: `fuse_color_train` and `coloragg.fuse_color_inputs` have no such keyword.
     Forward only: call it under torch.no_grad()."""
     name = "fuse_color"
     _check_precision(name, precision)
@@ -397,7 +397,7 @@ def hourglass_train(cnn_input, params, render_scale=None):
 
 
 def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, burn_start=None, burn_end=None, none_if_no_level=False, enable_exposure_correction=False):
-    """The reference's TRAINING fuse_color (color_aggregation_network.py:156-250; residual_resolution_scale 1) with a
+    """The reference's TRAINING fuse_color (color_aggregation_network.py:156-250; residual_resolution_scale 1 -- `resample_train.fuse_color_train_scaled` for another) with a
     `ColorAggregationNet`, differentiable end to end: the per-view front end (`PerViewFrontEnd`, forward and backward kernels), then `hourglass_train`.
     burned_in_gauss = (clamp((iter_count - burn_start) / (burn_end - burn_start), 0, 1) + 1) / 2, or 1.0 when one of the three is None; while it is below 1
     the five tensors of render_pkg are detached (no gradient reaches the rasterizer; the networks' parameters still train).  -> the dictionary of

@@ -7,8 +7,9 @@ its residual is interpolated back to H x W -- two kernels (C ABI include/ibgs_re
   upsample_residual   residual (3, Hr, Wr) -> (3, H, W), and image_pred = render_scale * render + that in the same pass
 
 Bilinear, align_corners=True, both ways, with the taps formed in integers (the header states the rule).  `hourglass.fuse_color(...,
-residual_resolution_scale=s)` composes them.  FORWARD ONLY: training at a reduced resolution is not covered (`fuse_color_train` and
-`coloragg.fuse_color_inputs` have no such keyword).  The contract is a tolerance against a float64 restatement (tests/resample_ref.py).
+residual_resolution_scale=s)` composes them.  FORWARD ONLY: training at a reduced resolution is ibgs_amd/resample_train.py (`resized_features_train`,
+`upsample_residual_train`, `fuse_color_train_scaled`: these forwards with the adjoint kernels of csrc/rsztrain.hip behind them); `fuse_color_train` and
+`coloragg.fuse_color_inputs` have no such keyword.  The contract is a tolerance against a float64 restatement (tests/resample_ref.py).
 
 HIP only: raises when the library or a GPU tensor is missing (no torch fallback in the product path)."""
 import math
@@ -47,7 +48,7 @@ def _size(name, size):
 def _forward_only(name, tensors):
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError("%s is forward only: call it under torch.no_grad() (an input or parameter requires grad and grad mode is on); training at a reduced "
-                           "residual resolution is not covered" % name)
+                           "residual resolution is ibgs_amd.resample_train" % name)
 
 
 def resized_features(render, warped_image, cam_feat, camera_ray, w1, b1, w2, b2, size, levels, mode="mean"):

@@ -5,6 +5,12 @@ process on one MI355X, at (3, 1080, 1920) and (3, 720, 1280) with 3 sources, in 
 reference renders).  Output: profiles/resample.txt.
 
     python tools/bench_resample.py [--out profiles/resample.txt] [--iters 5] [--repeats 7]
+    python tools/bench_resample.py --train [--out profiles/resample.txt]
+
+`--train` measures TRAINING at the reduced resolution instead (`resample_train.fuse_color_train_scaled`, forward + backward of `(image_pred g).sum()` with render,
+warped_image and all 22 parameters requiring grad) against the same torch composition with autograd and against `hourglass.fuse_color_train` at scale 1, then
+the two entry points of csrc/rsztrain.hip alone beside their byte floors, and that unit's resource report; it replaces the training section at the end of the
+output file and leaves the rest of it alone.
 
 Then each of the two kernels alone through the Python wrappers, beside its byte floor from the shapes at 8 TB/s, the hourglass alone at both resolutions
 (the expectation that its time falls with s^2 is only an expectation: the output says what was found), and hipcc's register / spill / LDS report of the unit.
@@ -24,7 +30,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _build, hourglass, resample  # noqa: E402
+from ibgs_amd import _build, _device, _lib, hourglass, resample, resample_train  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 ENQUEUE_BOUND_US = 12.0          # below this a back-to-back window measures the host's enqueue rate
@@ -91,10 +97,10 @@ def compare(fns, iters, repeats):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in t.items()}
 
 
-def resource_report():
-    """hipcc's kernel-resource-usage remarks of resample.hip with the unit's own flags -> lines."""
+def resource_report(unit="resample"):
+    """hipcc's kernel-resource-usage remarks of the unit's .hip with the unit's own flags -> lines."""
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [_build._hipcc()] + _build.compile_flags("resample") + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(_build.CSRC, "resample.hip"), "-o", os.path.join(tmp, "resample.o")]
+        cmd = [_build._hipcc()] + _build.compile_flags(unit) + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(_build.CSRC, unit + ".hip"), "-o", os.path.join(tmp, unit + ".o")]
         text = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, check=True).stdout
     out, cur = [], None
     for line in text.split("\n"):
@@ -108,8 +114,125 @@ def resource_report():
             m = re.search(pat, line)
             if m and cur is not None:
                 cur[key] = int(m.group(1))
-    return ["  %-36s VGPRs %3d  AGPRs %2d  SGPRs %3d  spills %d / %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
+    return ["  %-44s VGPRs %3d  AGPRs %2d  SGPRs %3d  spills %d / %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
             % (k["name"], k.get("vgpr", -1), k.get("agpr", 0), k.get("sgpr", -1), k.get("vspill", -1), k.get("sspill", -1), k.get("scratch", -1), k.get("lds", -1), k.get("occ", -1)) for k in out]
+
+
+TRAIN_MARK = "# ---- training at the reduced resolution (--train)"
+
+
+def scene(h, w, dev):
+    g = torch.Generator().manual_seed(h)
+    render = torch.rand((3, h, w), generator=g).to(dev)
+    feat = torch.rand((12, h, w), generator=g) * 0.5
+    feat = torch.where(torch.rand((3, 1, h, w), generator=g).expand(3, 4, h, w).reshape(12, h, w) < 0.7, feat, torch.zeros(())).to(dev)          # 30 % of the slots invalid
+    return {"render": render, "warped_image": (render[None] + 0.1 * torch.randn((3, 3, h, w), generator=g).to(dev)).clamp(0.01, 1).reshape(9, h, w).contiguous(),
+            "cam_feat": feat, "camera_ray": F.normalize(torch.randn((3, h, w), generator=g), dim=0).to(dev), "min_depth_diff": torch.rand((1, h, w), generator=g).to(dev)}
+
+
+def main_train(args):
+    dev = torch.device("cuda")
+    s = args.scale
+    lines = []
+
+    def say(text=""):
+        print(text, flush=True)
+        lines.append(text)
+
+    say(TRAIN_MARK)
+    say("# tools/bench_resample.py --train on one %s: fuse_color_train_scaled(..., %g), forward + backward of (image_pred g).sum() with render, warped_image and the 22" % (torch.cuda.get_device_name(0), s))
+    say("# parameters requiring grad, against the torch composition with autograd and against fuse_color_train at scale 1; 3 sources; float32; one process, hipEvents")
+    say("# around %d back-to-back steps, median [min .. max] of %d windows, the candidates alternating" % (args.iters, args.repeats))
+    torch.manual_seed(7)
+    net = hourglass.ColorAggregationNet().to(dev)
+    verdict = []
+    for (h, w) in ((1080, 1920), (720, 1280)):
+        pkg = scene(h, w, dev)
+        for k in ("render", "warped_image"):
+            pkg[k].requires_grad_(True)
+        leaves = [pkg["render"], pkg["warped_image"]] + list(net.parameters())
+        up = torch.randn((3, h, w), generator=torch.Generator().manual_seed(w)).to(dev)
+        hr, wr = resample.scaled_size(h, w, s)
+        plane, plane_r = h * w, hr * wr
+
+        def step(forward):
+            def run():
+                for t in leaves:
+                    t.grad = None
+                (forward() * up).sum().backward()
+            return run
+        fns = {"torch": step(lambda: composed(pkg, net, s, 3)[1]), "scaled": step(lambda: resample_train.fuse_color_train_scaled(pkg, net, s)["image_pred"]),
+               "full": step(lambda: hourglass.fuse_color_train(pkg, net)["image_pred"])}
+        say()
+        say("== (3, %d, %d), 3 sources; the CNN at %d x %d" % (h, w, hr, wr))
+        fns["scaled"]()
+        mine = [t.grad.clone() for t in leaves]
+        fns["torch"]()
+        names = ["render", "warped_image"] + [k for k, _ in net.named_parameters()]
+        l2 = max((float((a - t.grad).norm() / t.grad.norm()), k) for a, t, k in zip(mine, leaves, names))
+        top = max((float((a - t.grad).abs().max() / t.grad.abs().max()), k) for a, t, k in zip(mine, leaves, names))
+        # (a ReLU or pool decision that float32 rounding takes the other way changes single pixels of an image gradient by its own size: the max-abs figure of the images counts those)
+        say("same gradients (float32) over the 24 tensors: the largest |d grad|_2 / |grad|_2 %.2e (%s); the largest max |d grad| / max |grad| %.2e (%s)" % (l2 + top))
+        del mine
+        r = compare(fns, args.iters, args.repeats)
+        cheaper, faster = r["scaled"][0] < r["full"][0], r["scaled"][0] < r["torch"][0]
+        verdict.append(cheaper)
+        say("torch composition + autograd at s = %g %8.3f ms [%7.3f .. %7.3f]   fuse_color_train_scaled at s = %g %8.3f ms [%7.3f .. %7.3f]   torch / scaled %6.2f x   scaled faster: %s"
+            % ((s,) + r["torch"] + (s,) + r["scaled"] + (r["torch"][0] / r["scaled"][0], faster)))
+        say("fuse_color_train at s = 1             %8.3f ms [%7.3f .. %7.3f]   s = 1 / s = %g %6.2f x (pixels: %.2f x)   scaled faster than s = 1: %s"
+            % (r["full"] + (s, r["full"][0] / r["scaled"][0], plane / plane_r, cheaper)))
+        # the two entry points alone, on buffers made once
+        with torch.no_grad():
+            front = net.front_end
+            levels = resample.count_levels(pkg["warped_image"], 3)
+            imgs = [pkg[k].detach() for k in ("render", "warped_image", "cam_feat")]
+            pars = [t.detach().contiguous() for t in (front.w1, front.b1, front.w2, front.b2)]
+            go = torch.randn((38, hr, wr), device=dev)
+            grads = [torch.empty_like(t) for t in imgs[:2] + pars]
+            sc = _device.scratch(dev, _lib.load().ibgs_rzt_required_scratch(3, h, w, hr, wr))
+            g_res = torch.empty((3, hr, wr), device=dev)
+            ptrs = lambda ts: [None if t is None else t.data_ptr() for t in ts]
+            features = lambda outs: _device.call(dev, "ibgs_rzt_features_backward", 3, h, w, hr, wr, _lib.RSZ_MEAN, *ptrs(imgs + pars), levels.data_ptr(), go.data_ptr(), *ptrs(outs),
+                                                 sc.data_ptr(), sc.numel())
+            parts = {"rzt_features_backward, every gradient (3 kernels)": lambda: features(grads),
+                     "rzt_features_backward, parameters only (2 kernels)": lambda: features([None, None] + grads[2:]),
+                     "rzt_features_backward, images only (2 kernels)": lambda: features(grads[:2] + [None] * 4),
+                     "rzt_upsample_backward, one upstream": lambda: _device.call(dev, "ibgs_rzt_upsample_backward", h, w, hr, wr, None, up.data_ptr(), g_res.data_ptr()),
+                     "rzt_upsample_backward, both upstreams": lambda: _device.call(dev, "ibgs_rzt_upsample_backward", h, w, hr, wr, up.data_ptr(), up.data_ptr(), g_res.data_ptr())}
+            r = compare(parts, 2 * args.iters, args.repeats)
+            # reduced kernel: render, warped and cam_feat read about once (24 full planes), grad_out's 32 planes read, 9 planes of gx written; gather: cam_feat (12),
+            # gx (9 reduced) and grad_out's 3 colour planes read, 3 + 9 full planes written
+            reduced_kernel = 24 * 4 * plane + 32 * 4 * plane_r
+            gather = (12 + 12) * 4 * plane + (9 + 3) * 4 * plane_r
+            floors = {"rzt_features_backward, every gradient (3 kernels)": reduced_kernel + 9 * 4 * plane_r + gather, "rzt_features_backward, parameters only (2 kernels)": reduced_kernel,
+                      "rzt_features_backward, images only (2 kernels)": reduced_kernel + 9 * 4 * plane_r + gather,
+                      "rzt_upsample_backward, one upstream": 3 * 4 * (plane + plane_r), "rzt_upsample_backward, both upstreams": 3 * 4 * (2 * plane + plane_r)}
+            for name, (med, lo, hi) in r.items():
+                floor_us = floors[name] / HBM_BYTES_PER_S * 1e6
+                say("  %-52s %8.1f us [%7.1f .. %7.1f]%s   floor %6.1f MB at 8 TB/s = %5.1f us = %3.0f %% reached"
+                    % (name, med * 1e3, lo * 1e3, hi * 1e3, "  (the host's enqueue rate)" if med * 1e3 < ENQUEUE_BOUND_US else "", floors[name] / 1e6, floor_us, 100.0 * floor_us / (med * 1e3)))
+        del pkg, leaves, up, grads, sc, go, parts, fns
+        torch.cuda.empty_cache()
+    say()
+    if all(verdict):
+        say("fuse_color_train_scaled at s = %g faster than fuse_color_train at s = 1 at both sizes: True" % s)
+    else:
+        say("**fuse_color_train_scaled at s = %g is NOT faster than fuse_color_train at s = 1 at every size: the option misses its purpose there**" % s)
+    say()
+    say("hipcc -Rpass-analysis=kernel-resource-usage, %s:" % " ".join(_build.compile_flags("rsztrain")))
+    for line in resource_report("rsztrain"):
+        say(line)
+    kept = []
+    if os.path.exists(args.out):
+        kept = open(args.out).read().split("\n")
+        if TRAIN_MARK in kept:
+            kept = kept[:kept.index(TRAIN_MARK)]
+        while kept and not kept[-1].strip():
+            kept.pop()
+        kept.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(kept + lines) + "\n")
 
 
 def main():
@@ -118,9 +241,12 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--scale", type=float, default=0.5)
+    ap.add_argument("--train", action="store_true", help="measure training at the reduced resolution; replaces the training section at the end of --out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_resample.py measures on the GPU; there is none here")
+    if args.train:
+        return main_train(args)
     dev = torch.device("cuda")
     s = args.scale
     lines = []
