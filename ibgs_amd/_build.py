@@ -14,8 +14,9 @@ these three units), and lpips.hip (LPIPS on VGG16 for the image evaluation: a to
 are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
 the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
 (the reduced-resolution colour tail: a tolerance contract; its blends are written as fmaf, its MLP is the matrix-core chain it shares with coloragg.hip
-(csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves), and rsztrain.hip (that tail's backward: the same chain, the same
-blends, and a gather whose products and sums say themselves that they are not contracted).
+(csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves), and rsztrain.hip (that tail's backward: the same chain, the
+blends it shares with resample.hip (csrc/shared/rsz_taps.h), the per-slot backward it shares with coloragg.hip (csrc/shared/pv_mlp_bwd.h), and a gather whose
+products and sums say themselves that they are not contracted).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -49,30 +50,24 @@ def compile_flags(name):
     """Every flag a translation unit is compiled with, target included (tools/hot_loop_isa.py reads its assembly with the same list)."""
     return ["--offload-arch=" + ARCH] + BASE_FLAGS + EXTRA.get(name, [])
 # headers that not every unit includes: hashed into the profile stamps (tu_shas) of the units they are listed under and of no other, rebuild triggers like the
-# others.  Those under csrc/shared/ have two or three users each; they sit in a subdirectory because every csrc/*.h enters every unit's stamp.
-SSIM_WINDOW_H, PV_MLP_H, HG_NET_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "hg_net.h"))
+# others.  Those under csrc/shared/ have two or three users each; they sit in a subdirectory because every csrc/*.h enters every unit's stamp.  A unit's list
+# is every header it includes, directly or through another, outside csrc/*.h and include/ibgs_rast.h.
+SSIM_WINDOW_H, PV_MLP_H, PV_MLP_BWD_H, RSZ_TAPS_H, HG_NET_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "hg_net.h"))
 UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "mesh": [os.path.join(HERE, "..", "include", "ibgs_mesh.h")],
                 "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")],
                 "registration": [os.path.join(HERE, "..", "include", "ibgs_registration.h")],
                 "dtu": [os.path.join(HERE, "..", "include", "ibgs_dtu.h")],
                 "ssim": [os.path.join(HERE, "..", "include", "ibgs_ssim.h"), SSIM_WINDOW_H],
                 "geoloss": [os.path.join(HERE, "..", "include", "ibgs_geo_loss.h"), SSIM_WINDOW_H],
-                "coloragg": [os.path.join(HERE, "..", "include", "ibgs_color_agg.h"), PV_MLP_H],
+                "coloragg": [os.path.join(HERE, "..", "include", "ibgs_color_agg.h"), PV_MLP_H, PV_MLP_BWD_H],
                 "hourglass": [os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
                 "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
                 "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
                 "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")],
                 "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
-                "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H],
-                "rsztrain": [os.path.join(HERE, "..", "include", "ibgs_resample_train.h")]}
-# headers a unit includes besides its own, where UNIT_HEADERS lists only its own: rebuild triggers and part of the unit's stamp exactly like those above
-# (rsztrain.hip runs pv_mlp.h's chain and reads ibgs_resample.h's limits and modes)
-BORROWED_HEADERS = {"rsztrain": [PV_MLP_H, os.path.join(HERE, "..", "include", "ibgs_resample.h")]}
-
-
-def unit_headers(name):
-    """Every header outside csrc/*.h and include/ibgs_rast.h that translation unit `name` includes."""
-    return UNIT_HEADERS.get(name, []) + BORROWED_HEADERS.get(name, [])
+                "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, RSZ_TAPS_H],
+                "rsztrain": [os.path.join(HERE, "..", "include", "ibgs_resample_train.h"), os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, PV_MLP_BWD_H,
+                             RSZ_TAPS_H]}
 
 
 def _hipcc():
@@ -85,7 +80,7 @@ def _hipcc():
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "..", "include", "ibgs_rast.h"))
-    deps += [h for name in SOURCES for h in unit_headers(name)]
+    deps += [h for name in SOURCES for h in UNIT_HEADERS.get(name, [])]
     return max(os.path.getmtime(d) for d in deps)
 
 
@@ -141,7 +136,7 @@ def tu_shas():
     for name in SOURCES:
         h = hdr.copy()
         h.update(_code_only(open(os.path.join(CSRC, name + ".hip"), "r").read()).encode())
-        for u in unit_headers(name):
+        for u in UNIT_HEADERS.get(name, []):
             h.update(_code_only(open(u, "r").read()).encode())
         h.update(" ".join(EXTRA.get(name, [])).encode())
         out[name] = h.hexdigest()[:12]
@@ -165,7 +160,7 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(OBJ, name + ".o")
-        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in unit_headers(name)])
+        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
         cmd = [hipcc] + compile_flags(name) + ["-c", src, "-o", obj]

@@ -8,7 +8,7 @@
 // CONTRACT
 //   levels     min(slots of `warped` with any value != 0, nb_visible_src_frames, S), in a device word; the first `levels` slots are used.
 //   slot k     v = (((f0 + f1) + f2) + f3) > 0 in float32, in that order (cam_feat is signed); x = [(warped - render) v, f0 .. f3];
-//              h1 = relu(w1 x + b1), h2 = relu(w2 h1 + b2): shared/pv_mlp.h, which resample.hip runs too, states the chain and what its bits rest on.
+//              h1 = relu(w1 x + b1), h2 = relu(w2 h1 + b2): shared/pv_mlp.h, which resample.hip and rsztrain.hip run too, states the chain and what its bits rest on.
 //   agg        mean: ((h2_0 + h2_1) + ..) / levels; max: the maximum over k; zeros when levels == 0.  out = [agg, camera_ray, render].
 //   backward   recomputes h1 and h2 with the same instructions (the same bits), then dz2 = g (h2 > 0) with g = grad_out / levels (mean) or grad_out at the
 //              first slot attaining the maximum (max), dz1 = (w2^T dz2) (h1 > 0), dx = w1^T dz1; grad_warped[3k + c] = dx[c] v, grad_render[c] =
@@ -31,31 +31,24 @@
 //   cagg_bwd_kernel      the same over a capped grid that walks the frame in chunks of 128 pixels; 52 MFMA per wave and slot with parameter gradients.
 //   cagg_final_kernel    82 workgroups: 16 elements each.
 // What bounds them, storing against recomputing, and the matrix cores against the VALU: DESIGN.md section 14.
+//
+// WHO STATES WHAT: shared/pv_mlp.h the slot and both layers (resample.hip and rsztrain.hip run them too); shared/pv_mlp_bwd.h the backward's workgroup geometry,
+// the per-slot backward, the parameter sums and the layout of the partials, for cagg_bwd_kernel and for rsztrain.hip's rzt_features_bwd_kernel.  This file: the
+// level count, the forward, how the backward loads a slot (one pixel) and what it does with gx (times v, to grad_warped and grad_render), and cagg_final_kernel
+// with its launcher pv_launch_final, which rsztrain.hip calls too: the final pass has one owner.
 #include "common.h"
-#include "shared/pv_mlp.h"
+#include "shared/pv_mlp_bwd.h"
 #include "../../include/ibgs_color_agg.h"
 
 namespace ibgs {
 
-constexpr int CT = 256;                              // threads per workgroup
+constexpr int CT = 256;                              // the forward: threads per workgroup (the backward's geometry is shared/pv_mlp_bwd.h's)
 constexpr int CWAVES = CT / 64;
 constexpr int CB = 32;                               // pixels per wave
 constexpr int CHUNK = CWAVES * CB;                   // pixels per workgroup and step
-constexpr int CROW = 33;                             // row stride of the staged rows: the 32 lanes of a half store one column into 32 banks
-constexpr int CAGG_PARTIAL = PV_F * PV_INP + PV_F * PV_F + PV_F;          // a workgroup's sums: [dW1 | db1] (32 x 8), dW2 (32 x 32), db2 (32)
-constexpr int CAGG_MAX_GROUPS = 512;                 // workgroups of the backward (256 CUs x 2 resident): what bounds the arena
 constexpr int CAGG_FWD_MAX_GROUPS = 4096;
-constexpr int CAGG_WAVE_WORDS = PV_F * PV_F + PV_F * PV_INP + 2 * PV_F;   // a wave's accumulators as the cross-wave sum reads them
 constexpr int LV_THREADS = 256, LV_MAX_BLOCKS = 128; // level count: workgroups per slot
-constexpr int FIN_ELEMS = 16, FIN_SERIES = 16;       // final kernel: elements per workgroup, strided series per element
-static_assert(PV_F == IBGS_CAGG_FEATURES && CB == PV_F && CAGG_PARTIAL % FIN_ELEMS == 0 && FIN_ELEMS * FIN_SERIES == CT, "the lane maps below");
-static_assert(CWAVES * CAGG_WAVE_WORDS * sizeof(double) <= CWAVES * 3 * CB * CROW * sizeof(float), "the cross-wave sum reuses the staged rows");
-
-__device__ __forceinline__ int cagg_levels_of(const int32_t* __restrict__ levels, int S)
-{
-    const int l = *levels;          // (wave-uniform)
-    return l < 0 ? 0 : (l > S ? S : l);
-}
+static_assert(PV_F == IBGS_CAGG_FEATURES && CB == PV_F && IBGS_CAGG_MEAN == PV_MEAN && IBGS_CAGG_MAX == PV_MAX, "the lane maps below, and the shared backward's modes");
 
 // slot's grid: S x per_slot workgroups; state[0]: the slots that hold a value, state[1]: workgroups done (both zero on entry)
 __global__ void __launch_bounds__(LV_THREADS) cagg_levels_kernel(const float* __restrict__ warped, size_t slot_elems, int per_slot, int S, int nb, uint32_t* __restrict__ state,
@@ -88,7 +81,7 @@ __global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ 
     const PvFrag f(w1, w2, c, h);
     __shared__ PvBias bias;
     pv_stage_bias(bias, b1, b2);
-    const int L = cagg_levels_of(levels, S);
+    const int L = pv_levels_of(levels, S);
     const size_t blocks = (plane + CB - 1) / CB;
     for (size_t b = (size_t)blockIdx.x * CWAVES + wave; b < blocks; b += (size_t)gridDim.x * CWAVES) {
         const size_t q = b * CB + c;
@@ -123,40 +116,29 @@ __global__ void __launch_bounds__(CT) cagg_fwd_kernel(const float* __restrict__ 
     }
 }
 
-// IG: an image gradient is asked for; PG: a parameter gradient is.  go: 38 planes; partials: gridDim.x x CAGG_PARTIAL
+// IG: an image gradient is asked for; PG: a parameter gradient is.  go: 38 planes; partials: gridDim.x x PVB_PARTIAL
 template <int MODE, bool IG, bool PG>
-__global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict__ render, const float* __restrict__ warped, const float* __restrict__ feat,
-                                                      const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-                                                      const float* __restrict__ b2, const int32_t* __restrict__ levels, int S, size_t plane, const float* __restrict__ go,
-                                                      float* __restrict__ d_render, float* __restrict__ d_warped, double* __restrict__ partials)
+__global__ void __launch_bounds__(PVB_T, 2) cagg_bwd_kernel(const float* __restrict__ render, const float* __restrict__ warped, const float* __restrict__ feat,
+                                                         const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+                                                         const float* __restrict__ b2, const int32_t* __restrict__ levels, int S, size_t plane, const float* __restrict__ go,
+                                                         float* __restrict__ d_render, float* __restrict__ d_warped, double* __restrict__ partials)
 {
-    __shared__ __attribute__((aligned(16))) float s_t[PG ? CWAVES : 1][PG ? 3 : 1][PG ? CB : 1][PG ? CROW : 1];          // per wave: its pixels' dz2, h1, dz1 as rows
-    __shared__ __attribute__((aligned(16))) float s_x[PG ? CWAVES : 1][PG ? CB : 1][PV_INP];  // ... and [x | 1]
+    __shared__ PvBwdRows<PG> rows;
+    __shared__ PvBwdW1c w1c;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
     const PvFrag f(w1, w2, c, h);
     __shared__ PvBias bias;
     pv_stage_bias(bias, b1, b2);
-    float a2t[16];          // the A operand of w2^T dz2: row = this lane's input channel c, k-step kk = the output channels ch(kk, h)
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) a2t[kk] = w2[pv_ch(kk, h) * PV_F + c];
-    __shared__ float4 s_w1c[2][16];          // w1's first three columns at the 16 channels of each half (the same for every pixel: read as a broadcast)
-    if (IG && threadIdx.x < 32) {
-        const int r = threadIdx.x & 15, hh = threadIdx.x >> 4;
-        s_w1c[hh][r] = make_float4(w1[pv_ch(r, hh) * PV_IN], w1[pv_ch(r, hh) * PV_IN + 1], w1[pv_ch(r, hh) * PV_IN + 2], 0.0f);
-    }
-    __syncthreads();
-    const int L = cagg_levels_of(levels, S);
-    const int r1 = lane >> 1, c0 = (lane & 1) * 4;          // this lane's elements of [dW1 | db1]: row r1 (dz1), columns c0 .. c0 + 3 (x, 1)
-    pv_f32x16 acc2;          // dW2: register r = row ch(r, h) (dz2), column c (h1); the f32 chain of one chunk's pixels and slots, then added to acc2d
-    double acc2d[16], acc1[4] = {0.0, 0.0, 0.0, 0.0}, accb = 0.0;          // accb: db2 of channel c over the pixels 16 h .. 16 h + 15 of the wave
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc2[r] = 0.0f; acc2d[r] = 0.0; }
-    const size_t chunks = (plane + CHUNK - 1) / CHUNK;
-    for (size_t ck = blockIdx.x; ck < chunks; ck += gridDim.x) {          // (uniform over the workgroup: the barriers below are reached by every thread)
-        const size_t q = ck * CHUNK + (size_t)wave * CB + c;
+    PvBwdLane a;
+    pv_bwd_setup<IG>(w1c, a, w1, w2, c, h);
+    const int L = pv_levels_of(levels, S);
+    const size_t chunks = (plane + PVB_CHUNK - 1) / PVB_CHUNK;
+    for (size_t ck = blockIdx.x; ck < chunks; ck += gridDim.x) {          // (uniform over the workgroup: the barriers of the calls below are reached by every thread)
+        const size_t q = ck * PVB_CHUNK + (size_t)wave * PVB_B + c;
         const bool in = q < plane;
         const size_t p = in ? q : plane - 1;          // a lane past the frame recomputes the last pixel under a zero gradient: it adds zeros
         const float r[3] = {render[p], render[plane + p], render[2 * plane + p]};
+        const auto load = [&](int k, float (&x)[PV_INP]) { return pv_slot(warped, feat, r, plane, p, k, x); };          // -> v
         pv_f32x16 g;
 #pragma unroll
         for (int j = 0; j < 16; ++j) g[j] = in ? go[(size_t)pv_ch(j, h) * plane + p] : 0.0f;
@@ -166,84 +148,25 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
             for (int j = 0; j < 16; ++j) g[j] = g[j] / n;
         }
         pv_f32x16 hmax;
-        uint32_t taken = 0u;          // max mode: the channels whose maximum an earlier slot attained
-        if (MODE == IBGS_CAGG_MAX) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) hmax[j] = 0.0f;
-            for (int k = 0; k < L; ++k) {
-                float x[PV_INP];
-                pv_f32x16 h1, h2;
-                pv_slot(warped, feat, r, plane, p, k, x);
-                pv_mlp(f, bias, x, h, h1, h2);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) hmax[j] = fmaxf(hmax[j], h2[j]);
-            }
-        }
+        uint32_t taken = 0u;
+        pv_bwd_hmax<MODE>(f, bias, L, load, hmax, h);
         float dr[3] = {0.0f, 0.0f, 0.0f};
         for (int k = 0; k < L; ++k) {
-            float x[PV_INP];
-            pv_f32x16 h1, dz2, dz1;
-            const float v = pv_slot(warped, feat, r, plane, p, k, x);
+            float x[PV_INP], gx[3];
+            pv_f32x16 h1, dz2;
+            const float v = load(k, x);
             pv_mlp(f, bias, x, h, h1, dz2);          // dz2 = h2 for now
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                bool on = dz2[j] > 0.0f;
-                if (MODE == IBGS_CAGG_MAX) {
-                    const bool mine = dz2[j] == hmax[j] && !((taken >> j) & 1u);
-                    if (mine) taken |= 1u << j;
-                    on = on && mine;
-                }
-                dz2[j] = on ? g[j] : 0.0f;
-                dz1[j] = 0.0f;
-            }
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) dz1 = pv_mfma(a2t[kk], dz2[kk], dz1);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) dz1[j] = h1[j] > 0.0f ? dz1[j] : 0.0f;
+            pv_bwd_slot<MODE, IG>(rows, w1c, a, h1, dz2, g, hmax, taken, x, in, gx, lane, wave, c, h);
             if constexpr (IG) {
-                float dx[3] = {0.0f, 0.0f, 0.0f};          // the lane's 16 channels, then the other half's
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float4 w = s_w1c[h][j];
-                    dx[0] = fmaf(w.x, dz1[j], dx[0]); dx[1] = fmaf(w.y, dz1[j], dx[1]); dx[2] = fmaf(w.z, dz1[j], dx[2]);
-                }
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
-                    const float gx = (dx[ch] + __shfl_xor(dx[ch], 32, 64)) * v;
-                    dr[ch] -= gx;
-                    if (d_warped && in && h == 0) d_warped[((size_t)k * 3 + ch) * plane + p] = gx;
-                }
-            }
-            if constexpr (PG) {
-                // A wave writes and reads only its own rows (s_t[wave], s_x[wave]): what the data flow needs is that the wave's own stores have landed before its
-                // loads of other lanes' rows, and the reverse before the next slot's stores.  __syncthreads() is the construct that promises exactly that for
-                // LDS, at the price of lining the four waves up twice per slot; a wave-scope fence in its place was measured, not adopted
-                // (docs/EXPERIMENTS.md section 15).
-                __syncthreads();          // the rows of the slot before have been read
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    s_t[wave][0][c][pv_ch(j, h)] = dz2[j];
-                    s_t[wave][1][c][pv_ch(j, h)] = h1[j];
-                    s_t[wave][2][c][pv_ch(j, h)] = dz1[j];
-                }
-                *reinterpret_cast<float4*>(&s_x[wave][c][4 * h]) = h ? make_float4(x[4], x[5], x[6], in ? 1.0f : 0.0f) : make_float4(x[0], x[1], x[2], x[3]);
-                __syncthreads();
-#pragma unroll
-                for (int kk = 0; kk < 16; ++kk) acc2 = pv_mfma(s_t[wave][0][2 * kk + h][c], s_t[wave][1][2 * kk + h][c], acc2);          // pixels in order
-#pragma unroll 4
-                for (int t = 0; t < 16; ++t) accb += (double)s_t[wave][0][16 * h + t][c];
-#pragma unroll 4
-                for (int t = 0; t < CB; ++t) {
-                    const double d = (double)s_t[wave][2][t][r1];          // (a product of two floats is exact in f64)
-                    const float4 xe = *reinterpret_cast<const float4*>(&s_x[wave][t][c0]);
-                    acc1[0] = fma(d, (double)xe.x, acc1[0]); acc1[1] = fma(d, (double)xe.y, acc1[1]); acc1[2] = fma(d, (double)xe.z, acc1[2]); acc1[3] = fma(d, (double)xe.w, acc1[3]);
+                    const float gv = gx[ch] * v;
+                    dr[ch] -= gv;
+                    if (d_warped && in && h == 0) d_warped[((size_t)k * 3 + ch) * plane + p] = gv;
                 }
             }
         }
-        if constexpr (PG) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc2d[r] += (double)acc2[r]; acc2[r] = 0.0f; }
-        }
+        if constexpr (PG) pv_bwd_end_chunk(a);
         if (IG && in && h == 0) {
             if (d_render) {
 #pragma unroll
@@ -255,43 +178,23 @@ __global__ void __launch_bounds__(CT, 2) cagg_bwd_kernel(const float* __restrict
                     for (int ch = 0; ch < 3; ++ch) d_warped[((size_t)k * 3 + ch) * plane + p] = 0.0f;
         }
     }
-    if constexpr (PG) {
-        double* const buf = reinterpret_cast<double*>(&s_t[0][0][0][0]);
-        double* const mine = buf + wave * CAGG_WAVE_WORDS;          // [dW2 (32 x 32) | dW1, db1 (32 x 8) | db2 by half (2 x 32)]
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[pv_ch(r, h) * PV_F + c] = acc2d[r];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) mine[PV_F * PV_F + r1 * PV_INP + c0 + m] = acc1[m];
-        mine[PV_F * PV_F + PV_F * PV_INP + h * PV_F + c] = accb;
-        __syncthreads();
-        for (int e = threadIdx.x; e < CAGG_PARTIAL; e += CT) {          // the waves in order
-            double sum = 0.0;
-            for (int w = 0; w < CWAVES; ++w) {
-                const double* const src = buf + w * CAGG_WAVE_WORDS;
-                if (e < PV_F * PV_INP) sum += src[PV_F * PV_F + e];
-                else if (e < PV_F * PV_INP + PV_F * PV_F) sum += src[e - PV_F * PV_INP];
-                else sum += src[PV_F * PV_F + PV_F * PV_INP + (e - PV_F * PV_INP - PV_F * PV_F)] + src[PV_F * PV_F + PV_F * PV_INP + PV_F + (e - PV_F * PV_INP - PV_F * PV_F)];
-            }
-            partials[(size_t)blockIdx.x * CAGG_PARTIAL + e] = sum;
-        }
-    }
+    if constexpr (PG) pv_bwd_flush(rows, a, partials, lane, wave, c, h);
 }
 
 // element e of the workgroups' sums: series s adds the workgroups s, s + 16, .. in that order in f64, thread e adds the series in order
-__global__ void __launch_bounds__(CT) cagg_final_kernel(const double* __restrict__ partials, int groups, float* __restrict__ d_w1, float* __restrict__ d_b1,
-                                                        float* __restrict__ d_w2, float* __restrict__ d_b2)
+__global__ void __launch_bounds__(PVB_T) cagg_final_kernel(const double* __restrict__ partials, int groups, float* __restrict__ d_w1, float* __restrict__ d_b1,
+                                                           float* __restrict__ d_w2, float* __restrict__ d_b2)
 {
-    __shared__ double s_sum[FIN_SERIES][FIN_ELEMS];
-    const int el = threadIdx.x & (FIN_ELEMS - 1), series = threadIdx.x / FIN_ELEMS;
-    const int e = blockIdx.x * FIN_ELEMS + el;
+    __shared__ double s_sum[PVB_FIN_SERIES][PVB_FIN_ELEMS];
+    const int el = threadIdx.x & (PVB_FIN_ELEMS - 1), series = threadIdx.x / PVB_FIN_ELEMS;
+    const int e = blockIdx.x * PVB_FIN_ELEMS + el;
     double a = 0.0;
-    for (int g = series; g < groups; g += FIN_SERIES) a += partials[(size_t)g * CAGG_PARTIAL + e];
+    for (int g = series; g < groups; g += PVB_FIN_SERIES) a += partials[(size_t)g * PVB_PARTIAL + e];
     s_sum[series][el] = a;
     __syncthreads();
-    if (threadIdx.x < FIN_ELEMS) {
+    if (threadIdx.x < PVB_FIN_ELEMS) {
         double t = s_sum[0][el];
-        for (int k = 1; k < FIN_SERIES; ++k) t += s_sum[k][el];
+        for (int k = 1; k < PVB_FIN_SERIES; ++k) t += s_sum[k][el];
         const float v = (float)t;
         if (e < PV_F * PV_INP) {
             const int i = e >> 3, c = e & 7;
@@ -301,6 +204,11 @@ __global__ void __launch_bounds__(CT) cagg_final_kernel(const double* __restrict
             if (d_w2) d_w2[e - PV_F * PV_INP] = v;
         } else if (d_b2) d_b2[e - PV_F * PV_INP - PV_F * PV_F] = v;
     }
+}
+
+void pv_launch_final(hipStream_t st, const double* partials, int groups, float* d_w1, float* d_b1, float* d_w2, float* d_b2)
+{
+    hipLaunchKernelGGL(cagg_final_kernel, dim3(PVB_PARTIAL / PVB_FIN_ELEMS), dim3(PVB_T), 0, st, partials, groups, d_w1, d_b1, d_w2, d_b2);
 }
 
 // who == nullptr: silent (the size query)
@@ -322,21 +230,15 @@ static bool cagg_mode_ok(const char* who, int32_t mode)
     return false;
 }
 
-static unsigned cagg_bwd_groups(size_t plane)
-{
-    const size_t chunks = (plane + CHUNK - 1) / CHUNK;
-    return (unsigned)(chunks < (size_t)CAGG_MAX_GROUPS ? chunks : (size_t)CAGG_MAX_GROUPS);
-}
-
 struct CaggScratch {
     uint32_t* state;          // 2 words: the level count's flags and tickets
-    double* partials;         // workgroups of the backward x CAGG_PARTIAL
+    double* partials;         // workgroups of the backward x PVB_PARTIAL
     static CaggScratch carve(char* base, size_t plane, size_t* total)
     {
         CaggScratch d;
         Carver c(base);
         d.state = c.take<uint32_t>(2);
-        d.partials = c.take<double>((size_t)cagg_bwd_groups(plane) * CAGG_PARTIAL);
+        d.partials = c.take<double>((size_t)pv_bwd_groups(plane) * PVB_PARTIAL);
         if (total) *total = c.cur - reinterpret_cast<uintptr_t>(base) + 128;
         return d;
     }
@@ -346,9 +248,9 @@ template <int MODE>
 static void cagg_launch_bwd(hipStream_t st, unsigned groups, bool ig, bool pg, const float* render, const float* warped, const float* feat, const float* w1, const float* b1,
                             const float* w2, const float* b2, const int32_t* levels, int S, size_t plane, const float* go, float* d_render, float* d_warped, double* partials)
 {
-    if (ig && pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, true>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
-    else if (pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, false, true>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
-    else hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, false>), dim3(groups), dim3(CT), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+    if (ig && pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, true>), dim3(groups), dim3(PVB_T), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+    else if (pg) hipLaunchKernelGGL((cagg_bwd_kernel<MODE, false, true>), dim3(groups), dim3(PVB_T), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
+    else hipLaunchKernelGGL((cagg_bwd_kernel<MODE, true, false>), dim3(groups), dim3(PVB_T), 0, st, render, warped, feat, w1, b1, w2, b2, levels, S, plane, go, d_render, d_warped, partials);
 }
 
 }  // namespace ibgs
@@ -422,14 +324,14 @@ int32_t ibgs_cagg_backward(void* stream, int32_t S, int32_t H, int32_t W, int32_
     if (pg && !arena_ok("cagg_backward", "scratch", scratch, scratch_bytes, need)) return -IBGS_ERR_INVALID;
     if (!pg) sc.partials = nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const unsigned groups = cagg_bwd_groups(plane);
+    const unsigned groups = pv_bwd_groups(plane);
     if (mode == IBGS_CAGG_MEAN)
         cagg_launch_bwd<IBGS_CAGG_MEAN>(st, groups, ig, pg, render, warped, cam_feat, w1, b1, w2, b2, levels, (int)S, plane, grad_out, grad_render, grad_warped, sc.partials);
     else
         cagg_launch_bwd<IBGS_CAGG_MAX>(st, groups, ig, pg, render, warped, cam_feat, w1, b1, w2, b2, levels, (int)S, plane, grad_out, grad_render, grad_warped, sc.partials);
     IBGS_HIP(hipGetLastError());
     if (pg) {
-        hipLaunchKernelGGL(cagg_final_kernel, dim3(CAGG_PARTIAL / FIN_ELEMS), dim3(CT), 0, st, sc.partials, (int)groups, grad_w1, grad_b1, grad_w2, grad_b2);
+        pv_launch_final(st, sc.partials, (int)groups, grad_w1, grad_b1, grad_w2, grad_b2);
         IBGS_HIP(hipGetLastError());
     }
     return 0;

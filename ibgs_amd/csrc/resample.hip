@@ -12,7 +12,8 @@
 //   upsample   residual_out = value of residual_r; image_pred_out = render_scale * render + residual_out (product and sum rounded one after the other).
 //
 // THE SLOT AND THE 32 x 32 PRODUCTS are shared/pv_mlp.h's, the chain coloragg.hip runs: the lane and register map and what the bits rest on are stated there.
-// Of what it hands back this unit uses the slot's row (blended over the four taps before the layers) and h2.
+// Of what it hands back this unit uses the slot's row (blended over the four taps before the layers) and h2.  THE TAP AND VALUE RULE (rsz_tap, rsz_blend) and
+// the check of the sides are shared/rsz_taps.h's, which rsztrain.hip, this unit's backward, runs too.
 //
 // KERNELS
 //   rsz_features_kernel  256 threads = 4 waves of 32 reduced pixels, one block of pixels per wave (the grid is not capped); per slot 4 x 7 gathered loads,
@@ -22,6 +23,7 @@
 // What bounds them: DESIGN.md section 19.
 #include "common.h"
 #include "shared/pv_mlp.h"
+#include "shared/rsz_taps.h"
 #include "../../include/ibgs_resample.h"
 
 namespace ibgs {
@@ -32,27 +34,6 @@ constexpr int RB = 32;                               // reduced pixels per wave
 constexpr int RCHUNK = RWAVES * RB;                  // reduced pixels per workgroup
 constexpr int RQ = 4;                                // output columns per thread of the upsampling
 static_assert(PV_F == IBGS_RSZ_FEATURES && RB == PV_F, "the lane maps below");
-
-// One axis of the coordinate rule: the two taps of output index i of an `out`-long axis made of an `in`-long one, t and 1 - t.  (i (in - 1) < 2^32: both
-// sides are at most 65536.)
-struct RszTap { uint32_t i0, i1; float t, u; };
-__device__ __forceinline__ RszTap rsz_tap(uint32_t i, uint32_t in, uint32_t out)
-{
-    const uint32_t den = out > 1u ? out - 1u : 1u, num = out > 1u ? i * (in - 1u) : 0u;
-    RszTap r;
-    r.i0 = num / den;
-    r.i1 = min(r.i0 + 1u, in - 1u);
-    r.t = (float)(num - r.i0 * den) / (float)den;
-    r.u = 1.0f - r.t;
-    return r;
-}
-
-// the value rule on the taps a, b (row y0) and c, d (row y1)
-__device__ __forceinline__ float rsz_blend(float a, float b, float c, float d, const RszTap& ty, const RszTap& tx)
-{
-    const float top = fmaf(tx.t, b, tx.u * a), bottom = fmaf(tx.t, d, tx.u * c);
-    return fmaf(ty.t, bottom, ty.u * top);
-}
 
 __device__ __forceinline__ float rsz_norm3(float a, float b, float c)
 {
@@ -171,19 +152,6 @@ __global__ void __launch_bounds__(RT) rsz_upsample_kernel(const float* __restric
             }
         }
     }
-}
-
-static bool rsz_sides_ok(const char* who, int64_t H, int64_t W, int64_t Hr, int64_t Wr)
-{
-    if (H < 1 || W < 1 || H > IBGS_RSZ_MAX_SIDE || W > IBGS_RSZ_MAX_SIDE) {
-        set_error("%s: a frame of %lld x %lld is out of range (sides 1 .. %d)", who, (long long)H, (long long)W, IBGS_RSZ_MAX_SIDE);
-        return false;
-    }
-    if (Hr < 1 || Wr < 1 || Hr > IBGS_RSZ_MAX_SIDE || Wr > IBGS_RSZ_MAX_SIDE) {
-        set_error("%s: a reduced frame of %lld x %lld is out of range (sides 1 .. %d)", who, (long long)Hr, (long long)Wr, IBGS_RSZ_MAX_SIDE);
-        return false;
-    }
-    return true;
 }
 
 static bool rsz_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -1,7 +1,9 @@
 // The per-view MLP of the colour aggregation network on the matrix cores: one slot's seven inputs -> relu(w1 x + b1) -> relu(w2 h1 + b2), 32 wide, for the
-// 32 pixels of a wave.  The one statement of the chain that coloragg.hip (forward, and the backward's recomputation) and resample.hip (the forward at a reduced
-// resolution) run: the three are meant to be the same function of a slot, bit for bit.  ibgs_amd/_build.py lists this header under both units (UNIT_HEADERS),
-// and under no other: it sits in a subdirectory of csrc/ so that no other unit's profile stamp holds it.  Device code only.
+// 32 pixels of a wave.  The one statement of the chain that coloragg.hip (forward, and the backward's recomputation), resample.hip (the forward at a reduced
+// resolution) and rsztrain.hip (that forward's recomputation in its backward) run: all are meant to be the same function of a slot, bit for bit.  The backward
+// of the chain is pv_mlp_bwd.h's, which includes this header; resample.hip, forward only, does not compile it.  ibgs_amd/_build.py lists this header under the
+// three units (UNIT_HEADERS), and under no other: it sits in a subdirectory of csrc/ so that no other unit's profile stamp holds it.
+// Device code only.
 //
 // WHAT THE BITS REST ON
 //   slot k     v = (((f0 + f1) + f2) + f3) > 0 in float32, in that order (cam_feat is signed); x = [(warped - render) v, f0 .. f3, 0], each difference and

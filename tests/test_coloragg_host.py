@@ -60,16 +60,22 @@ def test_kernels_attributed_to_the_coloragg_unit():
     # the only atomics: the level count's two integer words; the float sums are per-workgroup partials and a fixed-order final pass
     assert sorted(set(re.findall(r"\b(\w*atomic\w*)\s*\(", code))) == ["__hip_atomic_fetch_add", "__hip_atomic_fetch_or", "__hip_atomic_load"]
     assert len(re.findall(r"atomic", code)) == 3
-    assert re.search(r"constexpr int CAGG_MAX_GROUPS = 512;", code) and re.search(r"constexpr int CAGG_FWD_MAX_GROUPS = 4096;", code)          # (tests/test_gpu_coloragg.py sizes two frames by them)
+    # the backward's geometry is stated in the header it shares with rsztrain.hip; the forward's stays here (tests/test_gpu_coloragg.py sizes its frames by both)
+    bwd = _build._code_only(open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "pv_mlp_bwd.h")).read())
+    assert re.search(r"constexpr int PVB_MAX_GROUPS = 512;", bwd) and re.search(r"constexpr int CAGG_FWD_MAX_GROUPS = 4096;", code)
+    assert re.search(r"constexpr int PVB_CHUNK = PVB_WAVES \* PVB_B;", bwd) and re.search(r"constexpr int PVB_T = 256;", bwd) and re.search(r"constexpr int PVB_B = 32;", bwd)
+    assert re.search(r"constexpr int PVB_WAVES = PVB_T / 64;", bwd) and re.search(r"const size_t chunks = \(pixels \+ PVB_CHUNK - 1\) / PVB_CHUNK;", bwd)
     assert re.search(r"constexpr int CHUNK = CWAVES \* CB;", code) and re.search(r"constexpr int CT = 256;", code) and re.search(r"constexpr int CB = 32;", code)
+    assert not re.search(r"constexpr int (CAGG_MAX_GROUPS|CAGG_PARTIAL|CROW|FIN_ELEMS)\b", code)          # stated once
     # no header of its own under csrc/ (every header there is hashed into every unit's profile stamp): the chain it shares with resample.hip lies a directory below
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if "coloragg" in f and not f.startswith("_")) == ["coloragg.hip"]
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp.h", "../../include/ibgs_color_agg.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp_bwd.h", "../../include/ibgs_color_agg.h"]          # (pv_mlp_bwd.h includes pv_mlp.h)
+    assert re.findall(r'#include "([^"]+)"', open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "pv_mlp_bwd.h")).read()) == ["pv_mlp.h"]
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["hg_net.h", "pv_mlp.h", "ssim_window.h"]
-    for unit, header in (("coloragg", "pv_mlp.h"), ("resample", "pv_mlp.h"), ("ssim", "ssim_window.h"), ("geoloss", "ssim_window.h")):
-        assert [os.path.basename(h) for h in _build.UNIT_HEADERS[unit]][1:] == [header], unit
-    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 7          # no other unit's stamp holds them
+    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
+    for unit, headers in (("coloragg", ["pv_mlp.h", "pv_mlp_bwd.h"]), ("resample", ["pv_mlp.h", "rsz_taps.h"]), ("ssim", ["ssim_window.h"]), ("geoloss", ["ssim_window.h"])):
+        assert [os.path.basename(h) for h in _build.UNIT_HEADERS[unit]][1:] == headers, unit
+    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 8          # no other unit's stamp holds them (rsztrain is the eighth)
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from ibgs_amd import exposure, hourglass, resample, resample_train
+from ibgs_amd import coloragg, exposure, hourglass, resample, resample_train
 from tests import dirty_alloc as da
 from tests import hourglass_ref
 from tests import resample_ref as ref
@@ -29,6 +29,7 @@ pytestmark = pytest.mark.gpu
 F64_K = 2.0
 FLOOR = 2.0 ** -22
 DEV = "cuda"
+OWN_SIZE_SEEDS = {(13, 20, 1.0): 1}          # decided like tr.SEEDS (the test that uses it asserts so): a frame resampled to its own size
 CNN_NAMES = [name + suffix for name, _, _, _ in hourglass_ref.LAYERS for suffix in ("_w", "_b")]
 
 
@@ -52,7 +53,7 @@ def _compare(tag, got, want, t32, twin, failed):
 # ---- the CPU evaluations, computed once and shared: nobody writes them -----------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _case(h, w, s, raised=False):
-    case, params = ref.seeded_case(h, w, seed=0 if raised else tr.SEEDS[(h, w, s)])
+    case, params = ref.seeded_case(h, w, seed=0 if raised else {**tr.SEEDS, **OWN_SIZE_SEEDS}[(h, w, s)])
     size = ref.scaled_size(h, w, s)
     if raised:
         params = tr.raised_biases(case, params, size)
@@ -121,6 +122,41 @@ def test_feature_gradients_against_float64(frame, mode):
 def test_a_frame_beyond_one_pass_of_the_capped_grid():
     h, w, s = tr.BIG
     _feature_parity(h, w, s, "mean", 3, raised=True)
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+@pytest.mark.parametrize("h,w,levels,raised,chunks", [(13, 20, 2, False, 3), (257, 256, 3, True, 514)], ids=["13x20_levels2", "257x256_levels3"])
+def test_at_the_frames_own_size_the_backward_is_the_front_ends(h, w, levels, raised, chunks, mode):
+    """rzt_features_bwd_kernel and cagg_bwd_kernel run ONE per-slot backward and ONE set of parameter sums (csrc/shared/pv_mlp_bwd.h) and one final pass
+    (cagg_final_kernel).  At size == (H, W) every tap has t = 0 and u = 1, and fma(0, b, 1 a) = a for finite inputs (a masked -0 becomes +0, which changes no
+    product's bits that torch.equal sees), so a slot's blended row is the pixel's own row; the two grids agree (pv_bwd_groups of the same H W), so every workgroup
+    adds the same chunks in the same order.  The gather's weight is 1 at the pixel itself and its G = fma(1, gx, 0) = gx, so grad_warped = gx v in both.  Hence
+    the same bits for grad_warped and the four parameter gradients.  grad_render is NOT compared bit for bit: the gather forms (go - gv0) - gv1 .. where the front
+    end forms go + ((0 - gv0) - gv1 ..), and the two associations round differently; both are held to this file's bar against the float64 arbiter.  The forwards
+    are not compared: channels 32 .. 34 differ by design (the reduced tail normalises the ray).
+    13 x 20, levels 2 of 3: three chunks of 128, the last with lanes past the frame, one slot zeroed.  257 x 256: 514 chunks against the cap of 512, so two
+    workgroups walk a second chunk; raised biases keep every ReLU away from zero."""
+    case, params, size, go = _case(h, w, 1.0, raised)
+    assert size == (h, w) and (h * w + 127) // 128 == chunks
+    if not raised:
+        assert tr.decided_seed(h, w, 1.0) == OWN_SIZE_SEEDS[(h, w, 1.0)]
+    go = go.to(DEV)
+    _, mine = _feature_run(case, params, size, levels, mode, go)
+    render, warped = _leaves(case[:2])
+    p = _leaves(params)
+    out, _ = coloragg.per_view_features(render, warped, _dev(case[2]), _dev(case[3]), *p, levels=levels, mode=mode)
+    (out * go).sum().backward()
+    theirs = dict(zip(tr.NAMES, [t.grad for t in [render, warped] + p]))
+    torch.cuda.synchronize()
+    for k in tr.NAMES[1:]:
+        assert mine[k].shape == theirs[k].shape and float(mine[k].abs().max()) > 0, k
+        assert torch.equal(mine[k], theirs[k]), (k, float((mine[k] - theirs[k]).abs().max()))
+    assert float(mine["warped"][levels:].abs().max() if levels < 3 else 0.0) == 0.0
+    want, t32, twin = _feature_cpu(h, w, 1.0, mode, levels, raised)
+    failed = []
+    for who, grads in (("reduced", mine), ("front end", theirs)):
+        _compare("%dx%d at its own size %s levels %d render (%s)" % (h, w, mode, levels, who), grads["render"], want["render"], t32["render"], twin["render"], failed)
+    assert not failed, failed
 
 
 def test_only_what_autograd_needs():

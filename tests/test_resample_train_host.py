@@ -1,6 +1,6 @@
 """Training at a reduced residual resolution on a CPU-only box: the C ABI (include/ibgs_resample_train.h <-> _lib.RZT_EXPORTS <-> the built library), the build
-registration (the kernels' attribution, no atomics, the borrowed headers in the unit's dependency and stamp lists, the restated tap and blend functions held to
-resample.hip's text, every other unit's stamp unchanged), the entry points' validation with null pointers and bad sizes, the refusals of
+registration (the kernels' attribution, no atomics, every header the unit includes in its dependency and stamp lists, the tap and value rule and the per-slot
+backward each defined once under csrc/shared/ and called by both of their units, every other unit's stamp unchanged), the entry points' validation with null pointers and bad sizes, the refusals of
 ibgs_amd.resample_train (which run before any GPU work), the arbiter (tests/resample_train_ref.py) against torch's own float64 F.interpolate composition with
 autograd and against the recorded gradients of the reference's fuse_color at residual_resolution_scale 0.5 (tests/golden/consumer_resized_train.npz), and the
 decided seeds of the device tests."""
@@ -21,13 +21,15 @@ CSRC = os.path.join(ROOT, "ibgs_amd", "csrc")
 SRC = os.path.join(CSRC, "rsztrain.hip")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 NAMES = ["ibgs_rzt_required_scratch", "ibgs_rzt_features_backward", "ibgs_rzt_upsample_backward"]
-KERNELS = ["rzt_features_bwd_kernel", "rzt_final_kernel", "rzt_gather_kernel", "rzt_upsample_bwd_kernel"]
-# _build.tu_shas() of the commit this unit was added to: no existing unit's source, headers or flags changed with it
+BWD_H, TAPS_H = os.path.join(CSRC, "shared", "pv_mlp_bwd.h"), os.path.join(CSRC, "shared", "rsz_taps.h")
+KERNELS = ["rzt_features_bwd_kernel", "rzt_gather_kernel", "rzt_upsample_bwd_kernel"]          # the final pass of the parameter gradients is coloragg.hip's cagg_final_kernel
+# _build.tu_shas() of the commit that gave coloragg, resample and rsztrain one definition of the tap rule and of the per-view backward: those three stamps are
+# that commit's, every other one is still that of the commit rsztrain was added to
 PARENT_SHAS = {"api": "d2cea40a3180", "preprocess": "de228898d0b1", "scan_sort": "01e63032a313", "binning": "f337b73e1959", "render_fwd": "6ae05116c8bc",
                "render_bwd": "052d2dbf3751", "preprocess_bwd": "a45a137dac86", "knn": "e9bfb2e02f4f", "adam": "6a3146aa7716", "compact": "99a39d9227b5",
                "deterministic": "a24d88fa046d", "loss": "1f16fa584baf", "depth_normal": "6cf4fb76b878", "activate": "62185582088c", "tsdf": "80be8448d09b",
                "mesh": "59c42111558a", "mesh_eval": "8214092e1449", "registration": "5a0bad737c95", "dtu": "f17c4e79d7ed", "ssim": "da26b26bfdb8",
-               "geoloss": "9a7cae8f65e6", "coloragg": "c3aecb87f33e", "exposure": "315be22df182", "resample": "655d436da260", "lpips": "05640a97575a",
+               "geoloss": "9a7cae8f65e6", "coloragg": "0e34556dbaa7", "exposure": "315be22df182", "resample": "7bb6e6901370", "rsztrain": "c66c6940738e", "lpips": "05640a97575a",
                "hgtrain": "0c20d9d41e82", "hghalf": "9a7893d70f16", "hourglass": "aca5b57bd418"}
 
 
@@ -62,54 +64,104 @@ def test_unit_is_registered_and_its_kernels_attributed():
                 assert "rzt_" not in k, (name, k)
     code = _build._code_only(src)
     assert "atomic" not in code.lower()          # sums in a fixed order: no atomics of any kind
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp.h", "../../include/ibgs_resample.h", "../../include/ibgs_resample_train.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp_bwd.h", "shared/rsz_taps.h", "../../include/ibgs_resample.h", "../../include/ibgs_resample_train.h"]
+    assert re.findall(r'#include "([^"]+)"', open(BWD_H).read()) == ["pv_mlp.h"] and re.findall(r'#include "([^"]+)"', open(TAPS_H).read()) == ["../common.h", "../../../include/ibgs_resample.h"]
     assert re.search(r"pv_mlp\(", code) and re.search(r"pv_slot\(", code) and not re.search(r"mfma", code.replace("pv_mfma", ""))          # the forward's own chain
     assert sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(CSRC, "shared"))) == ["hg_net.h", "pv_mlp.h", "ssim_window.h"]
+    assert sorted(os.listdir(os.path.join(CSRC, "shared"))) == ["hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
 
 
 def test_borrowed_headers_reach_the_rebuild_check_and_the_stamp(tmp_path, monkeypatch):
-    """UNIT_HEADERS lists the unit's own header only; pv_mlp.h and ibgs_resample.h come through BORROWED_HEADERS: an edit of either must change this unit's stamp
-    (and only the stamps of the units that include it) and count as a newer dependency."""
+    """UNIT_HEADERS lists, per unit, every header it includes outside csrc/*.h (there is no second table): an edit of a header must change the stamps of exactly
+    the units that include it and count as a newer dependency."""
     base = lambda hs: [os.path.basename(h) for h in hs]
-    assert base(_build.UNIT_HEADERS["rsztrain"]) == ["ibgs_resample_train.h"]
-    assert base(_build.BORROWED_HEADERS["rsztrain"]) == ["pv_mlp.h", "ibgs_resample.h"] and list(_build.BORROWED_HEADERS) == ["rsztrain"]
-    assert base(_build.unit_headers("rsztrain")) == ["ibgs_resample_train.h", "pv_mlp.h", "ibgs_resample.h"] and all(os.path.exists(h) for h in _build.unit_headers("rsztrain"))
-    assert _build.unit_headers("coloragg") == _build.UNIT_HEADERS["coloragg"] and _build.unit_headers("api") == []
+    assert base(_build.UNIT_HEADERS["rsztrain"]) == ["ibgs_resample_train.h", "ibgs_resample.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h"]
+    assert all(os.path.exists(h) for hs in _build.UNIT_HEADERS.values() for h in hs)
+    assert not hasattr(_build, "BORROWED_HEADERS") and not hasattr(_build, "unit_headers") and "api" not in _build.UNIT_HEADERS
     before = _build.tu_shas()
-    for header, users in (("pv_mlp.h", {"coloragg", "resample", "rsztrain"}), ("ibgs_resample.h", {"resample", "rsztrain"}), ("ibgs_resample_train.h", {"rsztrain"})):
-        real = [h for h in _build.unit_headers("rsztrain") if os.path.basename(h) == header][0]
+    for header, users in (("pv_mlp.h", {"coloragg", "resample", "rsztrain"}), ("pv_mlp_bwd.h", {"coloragg", "rsztrain"}), ("rsz_taps.h", {"resample", "rsztrain"}),
+                          ("ibgs_resample.h", {"resample", "rsztrain"}), ("ibgs_resample_train.h", {"rsztrain"})):
+        assert {k for k, hs in _build.UNIT_HEADERS.items() if header in base(hs)} == users, header
+        real = [h for h in _build.UNIT_HEADERS["rsztrain"] if os.path.basename(h) == header][0]
         edited = tmp_path / header
         edited.write_text(open(real).read() + "\nstatic const int edited_for_the_test = 1;\n")
         swap = lambda hs: [str(edited) if os.path.basename(h) == header else h for h in hs]
         monkeypatch.setattr(_build, "UNIT_HEADERS", {k: swap(v) for k, v in _build.UNIT_HEADERS.items()})
-        monkeypatch.setattr(_build, "BORROWED_HEADERS", {k: swap(v) for k, v in _build.BORROWED_HEADERS.items()})
         after = _build.tu_shas()
         assert {k for k in before if after[k] != before[k]} == users, header
         assert _build._newest_dep() >= os.path.getmtime(str(edited))
         monkeypatch.undo()
     assert _build.tu_shas() == before
+    # the table is the truth: what a unit's source and its shared headers include, outside csrc/*.h and include/ibgs_rast.h, is what it lists
+    for unit in ("coloragg", "resample", "rsztrain"):
+        seen, todo = set(), [os.path.join(CSRC, unit + ".hip")]
+        while todo:
+            f = todo.pop()
+            for inc in re.findall(r'#include "([^"]+)"', open(f).read()):
+                path = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+                if os.path.dirname(path) != CSRC and os.path.basename(path) != "ibgs_rast.h" and path not in seen:
+                    seen.add(path)
+                    todo.append(path)
+        assert seen == {os.path.normpath(h) for h in _build.UNIT_HEADERS[unit]}, unit
 
 
 def test_every_other_units_stamp_is_the_parents():
     now = _build.tu_shas()
-    assert sorted(now) == sorted(list(PARENT_SHAS) + ["rsztrain"])
+    assert sorted(now) == sorted(PARENT_SHAS)
     assert {k: now[k] for k in PARENT_SHAS} == PARENT_SHAS
 
 
-def _function(text, name):
-    """The text of the struct in front of it (if any) and of the function `name`, up to its closing brace at column 0."""
-    m = re.search(r"(?:struct \w+ \{[^\n]*\};\n)?__device__ __forceinline__ [^\n]*\b%s\([^\n]*\n\{\n.*?\n\}\n" % name, text, flags=re.S)
-    assert m, name
-    return m.group(0)
+def _csrc_code():
+    """{path relative to csrc/: its code without comments} for every .hip and .h under csrc/, shared/ included"""
+    files = [f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + ["shared/" + f for f in os.listdir(os.path.join(CSRC, "shared"))]
+    return {f: _build._code_only(open(os.path.join(CSRC, f)).read()) for f in files}
 
 
-def test_restated_tap_and_blend_are_resamples_text():
-    mine, theirs = _build._code_only(open(SRC).read()), _build._code_only(open(os.path.join(CSRC, "resample.hip")).read())
-    for name in ("tap", "blend"):
-        restated = _function(mine, "rzt_" + name).replace("rzt_", "rsz_").replace("RztTap", "RszTap")
-        assert restated == _function(theirs, "rsz_" + name), name
-    assert "struct RszTap { uint32_t i0, i1; float t, u; };" in _function(theirs, "rsz_tap")
+OURS = ["coloragg.hip", "resample.hip", "rsztrain.hip", "shared/pv_mlp.h", "shared/pv_mlp_bwd.h", "shared/rsz_taps.h"]          # the colour tail's units and their shared headers
+DEFINES = r"^(?:template[^\n]*\n)?(?:__device__|__host__|__global__|static|inline)[^\n;]*\b%s\s*\("          # a function's definition (these sources declare nothing ahead)
+
+
+def test_tap_and_blend_are_defined_once_and_both_units_call_them():
+    code = _csrc_code()
+    for what, pattern in (("struct RszTap", r"\bstruct RszTap\b"), ("rsz_tap(", DEFINES % "rsz_tap"), ("rsz_blend(", DEFINES % "rsz_blend"), ("rsz_sides_ok(", DEFINES % "rsz_sides_ok")):
+        assert [f for f, text in code.items() for _ in re.findall(pattern, text, re.M)] == ["shared/rsz_taps.h"], what
+    assert "struct RszTap { uint32_t i0, i1; float t, u; };" in code["shared/rsz_taps.h"]
+    for unit in ("resample.hip", "rsztrain.hip"):
+        assert not re.search(DEFINES % r"r[sz][zt]_(?:tap|blend|sides_ok)", code[unit], re.M) and not re.search(r"\bstruct\s+R[sz][zt]Tap\b", code[unit]), unit
+        assert not re.search(r"\br[z]t_(?:tap|blend|sides_ok)\b|\bRztTap\b", code[unit]), unit
+        assert re.search(r"= rsz_tap\(", code[unit]) and re.search(r"= rsz_blend\(", code[unit]) and re.search(r"!rsz_sides_ok\(who,", code[unit]), unit
+    assert sorted(f for f, text in code.items() if re.search(r"r[sz][zt]_tap\(", text)) == ["resample.hip", "rsztrain.hip", "shared/rsz_taps.h"]          # no other user
+
+
+def test_per_view_backward_is_defined_once_and_both_units_call_it():
+    code = _csrc_code()
+    for name in ("pv_bwd_setup", "pv_bwd_hmax", "pv_bwd_slot", "pv_bwd_end_chunk", "pv_bwd_flush", "pv_levels_of", "pv_bwd_groups"):
+        assert [f for f, text in code.items() for _ in re.findall(DEFINES % name, text, re.M)] == ["shared/pv_mlp_bwd.h"], name
+    assert "pv_bwd" not in code["resample.hip"] and "pv_mlp_bwd.h" not in open(os.path.join(CSRC, "resample.hip")).read()          # forward only
+    for unit in ("coloragg.hip", "rsztrain.hip"):
+        for name in ("pv_bwd_setup<IG>(", "pv_bwd_hmax<MODE>(", "pv_bwd_slot<MODE, IG>(", "pv_bwd_end_chunk(", "pv_bwd_flush(", "pv_launch_final(st,", "pv_bwd_groups("):
+            assert name in code[unit], (unit, name)
+        # the unit's own text touches none of the backward's state: with the calls into the shared header taken out, no cross-half exchange, no weight columns, no
+        # transposed operand, no accumulator, no staged row
+        rest = re.sub(r"\bpv_\w+(?:<[^>\n]*>)?\([^;]*\);", "", code[unit])
+        for word in ("__shfl_xor", "s_w1c", "a2t", "acc2", "acc1", "accb", "s_t[", "s_x[", ".t[", ".x[", ".at[") + (("__syncthreads",) if unit == "rsztrain.hip" else ()):
+            assert word not in rest, (unit, word)          # (coloragg.hip's level count and final pass have barriers of their own)
+        # the two statements of how a slot is loaded: one loader per kernel, called by the pre-pass and by the slot loop
+        assert len(re.findall(r"const auto load = \[&\]\(int k, float \(&x\)\[PV_INP\]\)", code[unit])) == 1 and "load(k, x);" in code[unit], unit
+    # one final pass: cagg_final_kernel is the only kernel under csrc/ whose body adds rows of PVB_PARTIAL partials, and coloragg.hip owns its launcher
+    adds = []
+    for f, text in code.items():
+        for m in re.finditer(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s+)?(\w+)\s*\(.*?\n\}\n", text, flags=re.S):
+            if re.search(r"\+=\s*partials\[", m.group(0)) and (f in OURS or "PVB_PARTIAL" in m.group(0)):          # (other units have partials and final passes
+                adds.append((f, m.group(1)))                                                                       # of their own: not rows of PVB_PARTIAL)
+    assert adds == [("coloragg.hip", "cagg_final_kernel")] and "PVB_PARTIAL + e]" in code["coloragg.hip"]
+    assert re.search(r"^void pv_launch_final\(hipStream_t st, const double\* partials, int groups, float\* d_w1, float\* d_b1, float\* d_w2, float\* d_b2\);$", code["shared/pv_mlp_bwd.h"], re.M)
+    assert len(re.findall(r"^void pv_launch_final\([^;]*\)\n\{", code["coloragg.hip"], re.M)) == 1 and code["coloragg.hip"].count("hipLaunchKernelGGL(cagg_final_kernel") == 1
+    assert "cagg_final_kernel" not in code["rsztrain.hip"] and "rzt_final" not in "".join(code.values())
+    # each of these lines of the backward is written in one file only
+    for line, where in ((r"mine\[PV_F \* PV_F", "shared/pv_mlp_bwd.h"), (r"taken \|= 1u", "shared/pv_mlp_bwd.h"), (r"__shfl_xor", "shared/pv_mlp_bwd.h"),
+                        (r"acc2d\[r\] \+=", "shared/pv_mlp_bwd.h"), (r"s_sum\[series\]", "coloragg.hip")):
+        assert [f for f in OURS if re.search(line, code[f])] == [where], line
 
 
 def test_validation_before_any_gpu_work(built_lib):
@@ -278,8 +330,10 @@ def test_every_frame_has_its_decided_seed():
 def test_the_frame_beyond_one_pass_is_decided_by_its_biases():
     h, w, s = tr.BIG
     size = ref.scaled_size(h, w, s)
-    assert size == (258, 256) and (size[0] * size[1] + 127) // 128 == 516 > 512          # the chunks against RZT_MAX_GROUPS
-    assert re.search(r"constexpr int RZT_MAX_GROUPS = 512;", open(SRC).read()) and re.search(r"constexpr int ZCHUNK = ZWAVES \* ZB;", open(SRC).read())
+    assert size == (258, 256) and (size[0] * size[1] + 127) // 128 == 516 > 512          # the chunks against PVB_MAX_GROUPS
+    assert re.search(r"constexpr int PVB_MAX_GROUPS = 512;", open(BWD_H).read()) and re.search(r"constexpr int PVB_CHUNK = PVB_WAVES \* PVB_B;", open(BWD_H).read())
+    assert re.search(r"constexpr int PVB_WAVES = PVB_T / 64;", open(BWD_H).read()) and re.search(r"constexpr int PVB_T = 256;", open(BWD_H).read()) and re.search(r"constexpr int PVB_B = 32;", open(BWD_H).read())
+    assert "pv_bwd_groups(plane_r)" in open(SRC).read()
     case, params = ref.seeded_case(h, w)
     raised = tr.raised_biases(case, params, size)
     with torch.no_grad():
