@@ -11,7 +11,8 @@ themselves (#pragma clang fp contract(off)); geoloss.hip, which runs the same pa
 (the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains), and hourglass.hip (the CNN behind it, forward only: the same), and hgtrain.hip (that CNN's backward: the same),
 and hghalf.hip (that CNN's forward in half precision: the same; csrc/shared/hg_net.h states the network -- its layers, its stage arena, its host-side checks -- once for
 these three units), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
-are the same matrix-core fma chains; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
+are the same matrix-core fma chains -- csrc/shared/conv_tile.h states their 16 x 16 tile and the rule by which a layer reads its source once for it and the three
+hourglass units; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
 the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
 (the reduced-resolution colour tail: a tolerance contract; its blends are written as fmaf, its MLP is the matrix-core chain it shares with coloragg.hip
 (csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves), and rsztrain.hip (that tail's backward: the same chain, the
@@ -50,9 +51,9 @@ def compile_flags(name):
     """Every flag a translation unit is compiled with, target included (tools/hot_loop_isa.py reads its assembly with the same list)."""
     return ["--offload-arch=" + ARCH] + BASE_FLAGS + EXTRA.get(name, [])
 # headers that not every unit includes: hashed into the profile stamps (tu_shas) of the units they are listed under and of no other, rebuild triggers like the
-# others.  Those under csrc/shared/ have two or three users each; they sit in a subdirectory because every csrc/*.h enters every unit's stamp.  A unit's list
+# others.  Those under csrc/shared/ have two to four users each; they sit in a subdirectory because every csrc/*.h enters every unit's stamp.  A unit's list
 # is every header it includes, directly or through another, outside csrc/*.h and include/ibgs_rast.h.
-SSIM_WINDOW_H, PV_MLP_H, PV_MLP_BWD_H, RSZ_TAPS_H, HG_NET_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "hg_net.h"))
+SSIM_WINDOW_H, PV_MLP_H, PV_MLP_BWD_H, RSZ_TAPS_H, HG_NET_H, CONV_TILE_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "hg_net.h", "conv_tile.h"))
 UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "mesh": [os.path.join(HERE, "..", "include", "ibgs_mesh.h")],
                 "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")],
                 "registration": [os.path.join(HERE, "..", "include", "ibgs_registration.h")],
@@ -60,10 +61,10 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "ssim": [os.path.join(HERE, "..", "include", "ibgs_ssim.h"), SSIM_WINDOW_H],
                 "geoloss": [os.path.join(HERE, "..", "include", "ibgs_geo_loss.h"), SSIM_WINDOW_H],
                 "coloragg": [os.path.join(HERE, "..", "include", "ibgs_color_agg.h"), PV_MLP_H, PV_MLP_BWD_H],
-                "hourglass": [os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
-                "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
-                "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H],
-                "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h")],
+                "hourglass": [os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
+                "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
+                "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
+                "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h"), CONV_TILE_H],
                 "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
                 "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, RSZ_TAPS_H],
                 "rsztrain": [os.path.join(HERE, "..", "include", "ibgs_resample_train.h"), os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, PV_MLP_BWD_H,

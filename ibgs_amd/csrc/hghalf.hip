@@ -21,6 +21,7 @@
 // j of a lane being channel 16 (2 s + (j >> 2)) + 4 kq + (j & 3), and hgh_pack_kernel lays the 1 x 1 weights out in that order.
 #include "common.h"
 #include "shared/hg_net.h"
+#include "shared/conv_tile.h"
 #include "../../include/ibgs_hourglass.h"
 #include "../../include/ibgs_hg_half.h"
 
@@ -147,7 +148,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
     constexpr int NOA = hgh_octets(CA), NOB = hgh_octets(CB), NO = NOA + NOB, NC = (NO + 3) / 4, MT = (COUT + 15) / 16, CPOUT = 8 * hgh_octets(COUT);
     constexpr int NWF = 9 * MT * 64;          // weight fragments of a chunk
     constexpr int NPOS = (HGH_NPIX * 4 + HGH_THREADS - 1) / HGH_THREADS, NW = (NWF + HGH_THREADS - 1) / HGH_THREADS;
-    static_assert(CB == 0 || MODE == HG_PLAIN, "a second input is read plain, at the first one's resolution");
+    static_assert(CB == 0 || MODE == CT_PLAIN, "a second input is read plain, at the first one's resolution");
     static_assert(!FUSE || (COUT == HG_C && MT == 3), "the last launch is dec1");
     __shared__ hgh_h8 s_in[HGH_NPIX * HGH_PSTRIDE];
     __shared__ hgh_h8 s_w[NWF];
@@ -176,11 +177,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
         const int p = (tid >> 2) + r * (HGH_THREADS / 4), pc = p < HGH_NPIX ? p : 0;
         const int yy = pc / HGH_WIN, xx = pc - yy * HGH_WIN, y = ty0 + yy - 1, x = tx0 + xx - 1;
         pos_in[r] = p < HGH_NPIX && y >= 0 && y < h && x >= 0 && x < w;
-        const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
-        // a holds hs x ws pixels: (h, w) itself (plain), >= (2 h, 2 w) (pool: the 2 x 2 maximum; an odd last row or column is never read) or (h / 2, w / 2) (up)
-        if (MODE == HG_PLAIN) pos[r] = yc * a.ws + xc;
-        else if (MODE == HG_POOL) pos[r] = 2 * yc * a.ws + 2 * xc;          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
-        else pos[r] = min(yc * a.hs / h, a.hs - 1) * a.ws + min(xc * a.ws / w, a.ws - 1);          // (yc hs < 2^26)
+        pos[r] = ct_source_offset<MODE>(y, x, h, w, a.hs, a.ws);          // a holds hs x ws pixels, read as MODE says
     }
     hgh_h8 iv[NPOS], wv[NW];
     const hgh_h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -193,7 +190,7 @@ __global__ void __launch_bounds__(HGH_THREADS, 2) hgh_conv3_kernel(const HghArgs
         for (int r = 0; r < NPOS; ++r) {
             const _Float16* const q = base + (size_t)pos[r] * cp;
             hgh_h8 v = *reinterpret_cast<const hgh_h8*>(q);
-            if (MODE == HG_POOL) {
+            if (MODE == CT_POOL) {
                 const hgh_h8 v1 = *reinterpret_cast<const hgh_h8*>(q + cp), v2 = *reinterpret_cast<const hgh_h8*>(q + (size_t)a.ws * cp),
                              v3 = *reinterpret_cast<const hgh_h8*>(q + ((size_t)a.ws + 1) * cp);
                 v = __builtin_elementwise_max(__builtin_elementwise_max(v, v1), __builtin_elementwise_max(v2, v3));
@@ -380,16 +377,16 @@ int32_t ibgs_hgh_forward(void* stream, int32_t H, int32_t W, const float* x, con
     for (int i = 0; i < HG_LAYER_COUNT; ++i) pk.layer[i] = {params[2 * i], HG_LAYERS[i].cout, HG_LAYERS[i].ca, HG_LAYERS[i].cb, hgh_at(i), hgh_kind(i)};
     hipLaunchKernelGGL(hgh_pack_kernel, dim3(pk.x_blocks + grid_for(HGH_FRAGS, HGH_THREADS)), dim3(HGH_THREADS), 0, st, pk);
 
-    hgh_launch<38, 0, 38, HG_PLAIN, false>(st, hgh_layer(sc.xh, nullptr, sc.packed + hgh_at(HG_ENC1), enc1_b, s.e1, H, W, H, W));
-    hgh_launch<38, 0, 19, HG_POOL, false>(st, hgh_layer(s.e1, nullptr, sc.packed + hgh_at(HG_ENC2), enc2_b, s.e2, H2, W2, H, W));
-    hgh_launch<19, 0, 9, HG_POOL, false>(st, hgh_layer(s.e2, nullptr, sc.packed + hgh_at(HG_ENC3), enc3_b, s.b, H4, W4, H2, W2));
-    hgh_launch<9, 0, 19, HG_UP, false>(st, hgh_layer(s.b, nullptr, sc.packed + hgh_at(HG_UP2_CONV), up2_conv_b, s.u2, H2, W2, H4, W4));
-    hgh_launch<19, 19, 19, HG_PLAIN, false>(st, hgh_layer(s.u2, s.e2, sc.packed + hgh_at(HG_DEC2), dec2_b, s.d2, H2, W2, H2, W2));
-    hgh_launch<19, 0, 38, HG_UP, false>(st, hgh_layer(s.d2, nullptr, sc.packed + hgh_at(HG_UP1_CONV), up1_conv_b, s.u1, H, W, H2, W2));
+    hgh_launch<38, 0, 38, CT_PLAIN, false>(st, hgh_layer(sc.xh, nullptr, sc.packed + hgh_at(HG_ENC1), enc1_b, s.e1, H, W, H, W));
+    hgh_launch<38, 0, 19, CT_POOL, false>(st, hgh_layer(s.e1, nullptr, sc.packed + hgh_at(HG_ENC2), enc2_b, s.e2, H2, W2, H, W));
+    hgh_launch<19, 0, 9, CT_POOL, false>(st, hgh_layer(s.e2, nullptr, sc.packed + hgh_at(HG_ENC3), enc3_b, s.b, H4, W4, H2, W2));
+    hgh_launch<9, 0, 19, CT_UP, false>(st, hgh_layer(s.b, nullptr, sc.packed + hgh_at(HG_UP2_CONV), up2_conv_b, s.u2, H2, W2, H4, W4));
+    hgh_launch<19, 19, 19, CT_PLAIN, false>(st, hgh_layer(s.u2, s.e2, sc.packed + hgh_at(HG_DEC2), dec2_b, s.d2, H2, W2, H2, W2));
+    hgh_launch<19, 0, 38, CT_UP, false>(st, hgh_layer(s.d2, nullptr, sc.packed + hgh_at(HG_UP1_CONV), up1_conv_b, s.u1, H, W, H2, W2));
     HghArgs last = hgh_layer(s.u1, s.e1, sc.packed + hgh_at(HG_DEC1), dec1_b, nullptr, H, W, H, W);
     last.xh = sc.xh; last.x = x; last.fuse_frag = sc.packed + hgh_at(HG_FUSE_INPUT); last.fuse_b = fuse_input_b; last.final_frag = sc.packed + hgh_at(HG_FINAL); last.final_b = final_b;
     last.burned = burned_in_gauss; last.residual = residual; last.image_pred = image_pred;
-    hgh_launch<38, 38, 38, HG_PLAIN, true>(st, last);
+    hgh_launch<38, 38, 38, CT_PLAIN, true>(st, last);
     IBGS_HIP(hipGetLastError());
     return 0;
 }

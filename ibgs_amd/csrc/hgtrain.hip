@@ -6,8 +6,8 @@
 // every call and stream: nothing is summed in an order that depends on scheduling -- a weight gradient is one partial per workgroup, summed by a last pass
 // in the order of the workgroups -- and grad_x does not depend on whether parameter gradients are asked for.
 //
-// THE PRODUCTS are v_mfma_f32_16x16x4_f32, lane l = (column l & 15, kq = l >> 4) as in hourglass.hip.
-//   hgb_conv_kernel<CA, CB, COUT, TAPS, TRANS>  the implicit GEMM of the forward on a 16 x 16 tile per workgroup (M = output channels, N = 16 pixels of a
+// THE PRODUCTS are v_mfma_f32_16x16x4_f32, lane l = (column l & 15, kq = l >> 4): the lane map of shared/conv_tile.h.
+//   hgb_conv_kernel<CA, CB, COUT, TAPS, TRANS>  the implicit GEMM of the forward on the 16 x 16 tile of that header (M = output channels, N = 16 pixels of a
 //     row, K = (channel, tap)), for 3 x 3 and 1 x 1 layers.  TRANS reads the weight transposed and flipped: the staged input is G, k = TAPS (output channel
 //     of the layer) + (TAPS - 1 - tap), M = the layer's input channels (a window [m0, m0 + COUT) of them: the two halves of a concatenation are two
 //     launches), no bias.  It serves the recomputed dec1 and fuse_input (forward form), final^T, fuse_input^T and the seven 3 x 3 input gradients.  The
@@ -19,28 +19,24 @@
 //     upsampled while it is staged, as the forward reads it: no concatenated, pooled or upsampled tensor exists.
 //   hgb_unpool_kernel, hgb_unup_kernel, hgb_add_kernel  the routing (pool^T with the skip sum and mask, up^T with the mask, g = g_res + g_ip): plain VALU,
 //     gathers in a fixed order.
-// STAGING keeps the forward's discipline: coordinates are clamped into the frame before an offset is formed, every load is unconditional and from a valid
-// address, and what lies outside the frame or past the last channel is replaced by zero afterwards.
+// STAGING keeps the forward's discipline (shared/conv_tile.h states it, and the rule by which a layer's source is read): coordinates are clamped into the
+// frame before an offset is formed, every load is unconditional and from a valid address, and what lies outside the frame or past the last channel is
+// replaced by zero afterwards.
 #include "common.h"
 #include "shared/hg_net.h"
+#include "shared/conv_tile.h"
 #include "../../include/ibgs_hourglass.h"
 #include "../../include/ibgs_hg_train.h"
 
 namespace ibgs {
 
-typedef float hgb_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int HGB_THREADS = 256;
-constexpr int HGB_TILE = 16;                         // hgb_conv_kernel: side of a workgroup's output tile
-constexpr int HGB_ROWS = 4;                          // rows of that tile per wave
+constexpr int HGB_THREADS = CT_THREADS;              // of every kernel here; hgb_conv_kernel's tile is conv_tile.h's
 constexpr int HGB_CHUNK = 8;                         // input channels per staged chunk
 constexpr int HGB_WT_H = 8;                          // hgb_wgrad_kernel: rows of a tile of its strip
 constexpr int HGB_WT_W = 16;                         // ... and columns
 constexpr int HGB_MAX_STRIPS = 128;                  // strips (partials) per weight gradient, at most
 constexpr int HGB_MIN_STRIP_TILES = 2;               // tiles of a strip, at least
 constexpr int HGB_GPLANE = HGB_WT_H * HGB_WT_W + 4;  // floats per staged channel of G: the 64 lanes of a read fall into 64 banks
-
-__device__ __forceinline__ hgb_f32x4 hgb_mfma(float a, float b, hgb_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // ---- the 16 x 16-tile implicit GEMM ----------------------------------------------------------------------------------------------------------------------
 struct HgbConv {
@@ -60,39 +56,29 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_conv_kernel(const HgbConv 
 {
     constexpr int CIN = CA + CB, MT = (COUT + 15) / 16, COUTP = MT * 16;
     constexpr int RUN = HGB_CHUNK * TAPS, STEPS = RUN / 4;
-    constexpr int PAD = TAPS == 9 ? 1 : 0, WIN = HGB_TILE + 2 * PAD, PLANE = TAPS == 9 ? 336 : 272;          // (both 16 mod 32)
+    constexpr int PAD = TAPS == 9 ? 1 : 0, WIN = CT_TILE + 2 * PAD, PLANE = TAPS == 9 ? CT_PLANE : 272;          // (both 16 mod 32)
     constexpr int WROW = COUTP + 1;
     static_assert(TAPS == 9 || TAPS == 1, "3 x 3 or 1 x 1");
-    static_assert(WIN * WIN <= PLANE && RUN % 4 == 0, "the staged window");
+    static_assert(WIN * WIN <= PLANE && PLANE % 32 == 16 && RUN % 4 == 0, "the staged window");
     __shared__ float s_in[HGB_CHUNK * PLANE];
     __shared__ float s_w[RUN * WROW];
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
-    const int tx0 = blockIdx.x * HGB_TILE, ty0 = blockIdx.y * HGB_TILE;
+    const int tx0 = blockIdx.x * CT_TILE, ty0 = blockIdx.y * CT_TILE;
     const int h = a.h, w = a.w;
     const size_t plane = (size_t)h * (size_t)w;
 
     // sum: the bias and the finished groups.  A multiply-add chain on the matrix cores runs over ONE group of two k-steps (eight products) from zero and is
     // then added to sum: a chain of 342 or 684 products in one accumulator loses about four times as much to rounding as these short ones and their sum
-    hgb_f32x4 sum[MT][HGB_ROWS];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        hgb_f32x4 start;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int ch = mt * 16 + kq * 4 + r;
-            start[r] = (a.bias && ch < COUT) ? a.bias[min(ch, COUT - 1)] : 0.0f;
-        }
-#pragma unroll
-        for (int nt = 0; nt < HGB_ROWS; ++nt) sum[mt][nt] = start;
-    }
+    ct_f32x4 sum[MT][CT_ROWS];
+    ct_start<COUT>(sum, a.bias, kq);
     int off[STEPS];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
         const int kk = 4 * s + kq, cl = kk / TAPS, t = kk - TAPS * cl, dy = t / 3;
         off[s] = cl * PLANE + dy * WIN + (t - 3 * dy);
     }
-    const int window_at = wave * HGB_ROWS * WIN + col;
+    const int window_at = wave * CT_ROWS * WIN + col;
 
 #pragma unroll 1
     for (int c0 = 0; c0 < CIN; c0 += HGB_CHUNK) {          // (uniform over the workgroup: every thread reaches the barriers)
@@ -100,7 +86,7 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_conv_kernel(const HgbConv 
         for (int p = threadIdx.x; p < WIN * WIN; p += HGB_THREADS) {
             const int yy = p / WIN, xx = p - yy * WIN, y = ty0 + yy - PAD, x = tx0 + xx - PAD;
             const bool in = y >= 0 && y < h && x >= 0 && x < w;
-            const int o = min(max(y, 0), h - 1) * w + min(max(x, 0), w - 1);
+            const int o = ct_source_offset<CT_PLAIN>(y, x, h, w, h, w);
 #pragma unroll
             for (int cl = 0; cl < HGB_CHUNK; ++cl) {
                 const int c = c0 + cl, cc = c < CIN ? c : CIN - 1;
@@ -121,7 +107,7 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_conv_kernel(const HgbConv 
 #pragma unroll
         for (int s0 = 0; s0 < STEPS; s0 += 2) {
             if (s0 < limit) {
-                hgb_f32x4 acc[MT][HGB_ROWS];
+                ct_f32x4 acc[MT][CT_ROWS];
 #pragma unroll
                 for (int s = s0; s < s0 + 2; ++s) {
                     {          // (a group's second step past `limit` multiplies staged zeros)
@@ -129,27 +115,29 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_conv_kernel(const HgbConv 
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) av[mt] = s_w[(4 * s + kq) * WROW + mt * 16 + col];
 #pragma unroll
-                        for (int nt = 0; nt < HGB_ROWS; ++nt) {
+                        for (int nt = 0; nt < CT_ROWS; ++nt) {
                             const float bv = s_in[window_at + nt * WIN + off[s]];
 #pragma unroll
-                            for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = hgb_mfma(av[mt], bv, s == s0 ? hgb_f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[mt][nt]);
+                            for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = ct_mfma(av[mt], bv, s == s0 ? ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[mt][nt]);
                         }
                     }
                 }
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < HGB_ROWS; ++nt) sum[mt][nt] += acc[mt][nt];
+                    for (int nt = 0; nt < CT_ROWS; ++nt) sum[mt][nt] += acc[mt][nt];
             }
         }
     }
 
+    // (the output walk is written out, not ct_for_each_output: with the epilogue as its callback the 19 -> 9 input gradient takes 74 registers for 72 and
+    // loses a wave per SIMD)
     const int x = tx0 + col;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < HGB_ROWS; ++nt) {
-            const int y = ty0 + wave * HGB_ROWS + nt;
+        for (int nt = 0; nt < CT_ROWS; ++nt) {
+            const int y = ty0 + wave * CT_ROWS + nt;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ch = mt * 16 + kq * 4 + r;
@@ -190,7 +178,7 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_wgrad_kernel(const HgbWgra
     constexpr int CIN = CA + CB, MT = (COUT + 15) / 16, COUTP = MT * 16, NT = S::NT, CI = S::CI;
     constexpr int PAD = TAPS == 9 ? 1 : 0, WINW = HGB_WT_W + 2 * PAD, WINH = HGB_WT_H + 2 * PAD, IPL = WINW * WINH;
     constexpr int ROWS = HGB_WT_H / 4;          // rows of a tile per wave
-    static_assert(CB == 0 || MODE == HG_PLAIN, "a second input is read plain, at the first one's resolution");
+    static_assert(CB == 0 || MODE == CT_PLAIN, "a second input is read plain, at the first one's resolution");
     constexpr int G_WORDS = COUTP * HGB_GPLANE, I_WORDS = CI * IPL, RED_WORDS = 2 * 4 * NT * 256;          // the last: one row of result tiles of the four waves, in double
     __shared__ __attribute__((aligned(16))) float s_mem[G_WORDS + I_WORDS > RED_WORDS ? G_WORDS + I_WORDS : RED_WORDS];
     float* const s_g = s_mem;
@@ -236,21 +224,15 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_wgrad_kernel(const HgbWgra
             const int cl = i / IPL, p = i - cl * IPL, yy = p / WINW, xx = p - yy * WINW;
             const int y = ty0 + yy - PAD, x = tx0 + xx - PAD, c = c0 + cl, cc = min(c, CIN - 1);
             const bool in = c < CIN && y >= 0 && y < h && x >= 0 && x < w;
-            const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
             const float* const base = (CB == 0 || cc < CA) ? a.a + (size_t)cc * plane_a : a.b + (size_t)(cc - CA) * plane_a;
-            float v;
-            if (MODE == HG_PLAIN) v = base[yc * a.ws + xc];
-            else if (MODE == HG_POOL) {          // 2 yc + 1 <= 2 h - 1 <= hs - 1, and the columns alike
-                const float* const q = base + 2 * yc * a.ws + 2 * xc;
-                v = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[a.ws], q[a.ws + 1]));
-            } else v = base[min(yc * a.hs / h, a.hs - 1) * a.ws + min(xc * a.ws / w, a.ws - 1)];
+            const float v = ct_read<MODE>(base + ct_source_offset<MODE>(y, x, h, w, a.hs, a.ws), a.ws);
             s_i[i] = in ? v : 0.0f;
         }
         __syncthreads();
 #pragma unroll
         for (int rr = 0; rr < ROWS; ++rr) {
             const int yy = wave * ROWS + rr;
-            hgb_f32x4 acc[MT][NT];
+            ct_f32x4 acc[MT][NT];
 #pragma unroll
             for (int gx = 0; gx < HGB_WT_W / 4; ++gx) {
                 const int px = 4 * gx + kq;
@@ -265,7 +247,7 @@ __global__ void __launch_bounds__(HGB_THREADS, 2) hgb_wgrad_kernel(const HgbWgra
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = hgb_mfma(av[mt], bv[nt], gx == 0 ? hgb_f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[mt][nt]);
+                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = ct_mfma(av[mt], bv[nt], gx == 0 ? ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[mt][nt]);
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
@@ -422,7 +404,7 @@ static void hgb_conv(hipStream_t st, const float* in_a, const float* in_b, const
     HgbConv a = {};
     a.a = in_a; a.b = in_b; a.weight = weight; a.bias = bias; a.wcin = wcin; a.m0 = m0; a.out = out; a.add = add; a.tail = tail; a.tail_scale = tail_scale;
     a.mask = mask; a.relu = relu ? 1 : 0; a.h = h; a.w = w;
-    const dim3 grid((unsigned)((w + HGB_TILE - 1) / HGB_TILE), (unsigned)((h + HGB_TILE - 1) / HGB_TILE));
+    const dim3 grid((unsigned)((w + CT_TILE - 1) / CT_TILE), (unsigned)((h + CT_TILE - 1) / CT_TILE));
     hipLaunchKernelGGL((hgb_conv_kernel<CA, CB, COUT, TAPS, TRANS>), grid, dim3(HGB_THREADS), 0, st, a);
 }
 
@@ -512,35 +494,35 @@ int32_t ibgs_hgb_backward(void* stream, int32_t H, int32_t W, const float* x, co
     hgb_conv<38, 0, 38, 1, true>(st, sc.C, nullptr, fuse_input_w, nullptr, 76, 0, sc.D, nullptr, nullptr, 0.0f, sc.A, false, H, W);
     if (want_x) hgb_conv<38, 0, 38, 1, true>(st, sc.C, nullptr, fuse_input_w, nullptr, 76, 38, grad_x, nullptr, grad_image_pred, burned_in_gauss, nullptr, false, H, W);
     if (want_params) {
-        hgb_wgrad<38, 0, 3, HG_PLAIN, 1>(st, g, sc.B, nullptr, sc.partial, grad_final_w, grad_final_b, H, W, H, W);
-        hgb_wgrad<38, 38, 38, HG_PLAIN, 1>(st, sc.C, sc.A, x, sc.partial, grad_fuse_input_w, grad_fuse_input_b, H, W, H, W);
-        hgb_wgrad<38, 38, 38, HG_PLAIN, 9>(st, sc.D, sg.u1, sg.e1, sc.partial, grad_dec1_w, grad_dec1_b, H, W, H, W);
+        hgb_wgrad<38, 0, 3, CT_PLAIN, 1>(st, g, sc.B, nullptr, sc.partial, grad_final_w, grad_final_b, H, W, H, W);
+        hgb_wgrad<38, 38, 38, CT_PLAIN, 1>(st, sc.C, sc.A, x, sc.partial, grad_fuse_input_w, grad_fuse_input_b, H, W, H, W);
+        hgb_wgrad<38, 38, 38, CT_PLAIN, 9>(st, sc.D, sg.u1, sg.e1, sc.partial, grad_dec1_w, grad_dec1_b, H, W, H, W);
     }
     // dec1: G_u1 -> A, g_e1a -> B
     hgb_dgrad<38, 38>(st, sc.D, dec1_w, 76, 0, sc.A, nullptr, sg.u1, H, W);
     hgb_dgrad<38, 38>(st, sc.D, dec1_w, 76, 38, sc.B, nullptr, nullptr, H, W);
     // up1_conv: its g_I -> C, G_d2
-    if (want_params) hgb_wgrad<19, 0, 38, HG_UP, 9>(st, sc.A, sg.d2, nullptr, sc.partial, grad_up1_conv_w, grad_up1_conv_b, H, W, H2, W2);
+    if (want_params) hgb_wgrad<19, 0, 38, CT_UP, 9>(st, sc.A, sg.d2, nullptr, sc.partial, grad_up1_conv_w, grad_up1_conv_b, H, W, H2, W2);
     hgb_dgrad<38, 19>(st, sc.A, up1_conv_w, 19, 0, sc.C, nullptr, nullptr, H, W);
     hipLaunchKernelGGL(hgb_unup_kernel, dim3(grid_for(19 * p2, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.C, sg.d2, sc.Gd2, 19, H, W, H2, W2);
     // dec2: G_u2, g_e2a -> E2
-    if (want_params) hgb_wgrad<19, 19, 19, HG_PLAIN, 9>(st, sc.Gd2, sg.u2, sg.e2, sc.partial, grad_dec2_w, grad_dec2_b, H2, W2, H2, W2);
+    if (want_params) hgb_wgrad<19, 19, 19, CT_PLAIN, 9>(st, sc.Gd2, sg.u2, sg.e2, sc.partial, grad_dec2_w, grad_dec2_b, H2, W2, H2, W2);
     hgb_dgrad<19, 19>(st, sc.Gd2, dec2_w, 38, 0, sc.Gu2, nullptr, sg.u2, H2, W2);
     hgb_dgrad<19, 19>(st, sc.Gd2, dec2_w, 38, 19, sc.E2, nullptr, nullptr, H2, W2);
     // up2_conv: G_b
-    if (want_params) hgb_wgrad<9, 0, 19, HG_UP, 9>(st, sc.Gu2, sg.b, nullptr, sc.partial, grad_up2_conv_w, grad_up2_conv_b, H2, W2, H4, W4);
+    if (want_params) hgb_wgrad<9, 0, 19, CT_UP, 9>(st, sc.Gu2, sg.b, nullptr, sc.partial, grad_up2_conv_w, grad_up2_conv_b, H2, W2, H4, W4);
     hgb_dgrad<19, 9>(st, sc.Gu2, up2_conv_w, 9, 0, sc.Iup2, nullptr, nullptr, H2, W2);
     hipLaunchKernelGGL(hgb_unup_kernel, dim3(grid_for(9 * p4, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Iup2, sg.b, sc.Gb, 9, H2, W2, H4, W4);
     // enc3: G_e2 (in E2)
-    if (want_params) hgb_wgrad<19, 0, 9, HG_POOL, 9>(st, sc.Gb, sg.e2, nullptr, sc.partial, grad_enc3_w, grad_enc3_b, H4, W4, H2, W2);
+    if (want_params) hgb_wgrad<19, 0, 9, CT_POOL, 9>(st, sc.Gb, sg.e2, nullptr, sc.partial, grad_enc3_w, grad_enc3_b, H4, W4, H2, W2);
     hgb_dgrad<9, 19>(st, sc.Gb, enc3_w, 19, 0, sc.Ienc3, nullptr, nullptr, H4, W4);
     hipLaunchKernelGGL(hgb_unpool_kernel, dim3(grid_for(19 * p2, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Ienc3, sg.e2, sc.E2, sc.E2, 19, H2, W2, H4, W4);
     // enc2: G_e1 (in B)
-    if (want_params) hgb_wgrad<38, 0, 19, HG_POOL, 9>(st, sc.E2, sg.e1, nullptr, sc.partial, grad_enc2_w, grad_enc2_b, H2, W2, H, W);
+    if (want_params) hgb_wgrad<38, 0, 19, CT_POOL, 9>(st, sc.E2, sg.e1, nullptr, sc.partial, grad_enc2_w, grad_enc2_b, H2, W2, H, W);
     hgb_dgrad<19, 38>(st, sc.E2, enc2_w, 38, 0, sc.Ienc2, nullptr, nullptr, H2, W2);
     hipLaunchKernelGGL(hgb_unpool_kernel, dim3(grid_for(38 * p1, HGB_THREADS)), dim3(HGB_THREADS), 0, st, sc.Ienc2, sg.e1, sc.B, sc.B, 38, H, W, H2, W2);
     // enc1
-    if (want_params) hgb_wgrad<38, 0, 38, HG_PLAIN, 9>(st, sc.B, x, nullptr, sc.partial, grad_enc1_w, grad_enc1_b, H, W, H, W);
+    if (want_params) hgb_wgrad<38, 0, 38, CT_PLAIN, 9>(st, sc.B, x, nullptr, sc.partial, grad_enc1_w, grad_enc1_b, H, W, H, W);
     if (want_x) hgb_dgrad<38, 38>(st, sc.B, enc1_w, 38, 0, grad_x, grad_x, nullptr, H, W);
     IBGS_HIP(hipGetLastError());
     return 0;

@@ -8,9 +8,8 @@
 //   layout.  The contract is a tolerance against a float64 restatement (tests/lpips_ref.py), not this order.  The same arguments give
 //   the same bits on every call and stream: no atomics; the only thing that crosses a workgroup is the head's partial sums, added in a fixed order.
 //
-// THE PRODUCTS are v_mfma_f32_16x16x4_f32, with the lane maps of hourglass.hip: output channels are M, 16 pixels of one row N, K runs over k = 9 (input
-// channel) + tap, four consecutive k per instruction.  Lane l = (column l & 15, kq = l >> 4) holds A[row l & 15][k = kq] and B[k = kq][column l & 15];
-// register r of a result tile is channel 4 kq + r of pixel l & 15.
+// THE PRODUCTS are v_mfma_f32_16x16x4_f32 on the 16 x 16 tile of shared/conv_tile.h, which states the lane map and the staging: output channels are M, 16
+// pixels of one row N, K runs over k = 9 (input channel) + tap, four consecutive k per instruction.
 //
 // KERNEL  lpips_conv3_kernel<POOL, FIRST>: 256 threads = 4 waves per 16 x 16 output tile and block of 64 output channels of one image; grid = (tiles across,
 // tiles down, 2 images x Cout / 64).  A wave owns four rows of the tile and the block's 64 channels: 4 x 4 accumulator tiles (64 registers).  The input
@@ -24,34 +23,24 @@
 // KERNEL  lpips_head_kernel: a thread per pixel of a tap; lpips_final_kernel: one workgroup.  What bounds each and what was measured: DESIGN.md section 17.
 #include "common.h"
 #include "block_ops.h"
+#include "shared/conv_tile.h"
 #include "../../include/ibgs_lpips.h"
 
 namespace ibgs {
 
-typedef float lp_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int LP_TILE = 16;                          // side of a workgroup's output tile
-constexpr int LP_THREADS = 256;
-constexpr int LP_WAVES = LP_THREADS / 64;
-constexpr int LP_ROWS = LP_TILE / LP_WAVES;          // rows of the tile per wave
-constexpr int LP_WIN = LP_TILE + 2;                  // the staged window: tile and halo
-constexpr int LP_PLANE = 336;                        // floats per staged channel (18 x 18 = 324, padded to 16 mod 32)
 constexpr int LP_CHUNK = 4;                          // input channels per staged chunk
 constexpr int LP_MT = 4;                             // result tiles of 16 channels per wave
 constexpr int LP_COB = 16 * LP_MT;                   // output channels per workgroup
 constexpr int LP_RUN = LP_CHUNK * 9;                 // k of a chunk
 constexpr int LP_STEPS = LP_RUN / 4;                 // k-steps of a chunk
 constexpr int LP_WROW = LP_COB + 1;                  // floats per k of the staged weights: consecutive k fall into different banks
-constexpr int LP_NPOS = (LP_WIN * LP_WIN + LP_THREADS - 1) / LP_THREADS;          // window positions per thread
-constexpr int LP_NW = LP_COB * LP_RUN / LP_THREADS;                               // weights per thread and chunk
+constexpr int LP_NW = LP_COB * LP_RUN / CT_THREADS;  // weights per thread and chunk
 constexpr int LP_HEAD_THREADS = 256;
-static_assert(LP_ROWS == 4 && LP_WIN * LP_WIN <= LP_PLANE && LP_PLANE % 32 == 16 && LP_COB * LP_RUN % LP_THREADS == 0, "the lane maps and the staging below");
+static_assert(LP_COB * LP_RUN % CT_THREADS == 0, "the staging below");
 
 static const int LP_CHANNELS[IBGS_LPIPS_CONVS + 1] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
 static const int LP_LEVEL[IBGS_LPIPS_CONVS] = {0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4};          // resolution level of a convolution's output
 static const int LP_TAP_CONV[IBGS_LPIPS_TAPS] = {1, 3, 6, 9, 12};                               // the convolution whose ReLU is tap k
-
-__device__ __forceinline__ lp_f32x4 lp_mfma(float a, float b, lp_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // networks.py:41-51: (v - mean) / std of channel c, as two float32 operations
 __device__ __forceinline__ float lp_zscore(float v, int c)
@@ -70,92 +59,60 @@ struct LpArgs {
 };
 
 template <bool POOL, bool FIRST>
-__global__ void __launch_bounds__(LP_THREADS, 2) lpips_conv3_kernel(const LpArgs a)
+__global__ void __launch_bounds__(CT_THREADS, 2) lpips_conv3_kernel(const LpArgs a)
 {
-    __shared__ float s_mem[LP_CHUNK * LP_PLANE + LP_RUN * LP_WROW];
-    float* const s_in = s_mem;
-    float* const s_w = s_mem + LP_CHUNK * LP_PLANE;
+    constexpr int MODE = POOL ? CT_POOL : CT_PLAIN;
+    __shared__ float s_mem[LP_CHUNK * CT_PLANE + LP_RUN * LP_WROW];
+    ct_lds* const s_in = (ct_lds*)s_mem;
+    ct_lds* const s_w = s_in + LP_CHUNK * CT_PLANE;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
-    const int tx0 = blockIdx.x * LP_TILE, ty0 = blockIdx.y * LP_TILE;
+    const int tx0 = blockIdx.x * CT_TILE, ty0 = blockIdx.y * CT_TILE;
     const int blocks = a.cout / LP_COB, img = (int)blockIdx.z / blocks, co0 = ((int)blockIdx.z - img * blocks) * LP_COB;          // (uniform)
     const int h = a.h, w = a.w, cin = a.cin, ktot = cin * 9;
     const float* const src = img ? a.in_y : a.in_x;
     const float* const wsrc = a.weight + (size_t)co0 * ktot;
 
-    lp_f32x4 acc[LP_MT][LP_ROWS];
-#pragma unroll
-    for (int mt = 0; mt < LP_MT; ++mt) {
-        lp_f32x4 start;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) start[r] = a.bias[co0 + mt * 16 + kq * 4 + r];
-#pragma unroll
-        for (int nt = 0; nt < LP_ROWS; ++nt) acc[mt][nt] = start;
-    }
-
-    // This lane's k of step s of a chunk is 4 s + kq: its channel of the chunk and tap, as an offset into the staged window.
+    ct_f32x4 acc[LP_MT][CT_ROWS];
+    ct_start<LP_COB>(acc, a.bias + co0, kq);
+    // This lane's k of step s of a chunk is 4 s + kq: its channel of the chunk and tap, as an offset into the staged window.  (The table and the k-steps that
+    // read it stay in the kernel: as helpers of conv_tile.h they cost hg_conv3_kernel 0.4 - 0.8 % of its time.)
     int off[LP_STEPS];
 #pragma unroll
     for (int s = 0; s < LP_STEPS; ++s) {
         const int kk = 4 * s + kq, cl = kk / 9, t = kk - 9 * cl, dy = t / 3;
-        off[s] = cl * LP_PLANE + dy * LP_WIN + (t - 3 * dy);
+        off[s] = cl * CT_PLANE + dy * CT_WIN + (t - 3 * dy);
     }
-    const int window_at = wave * LP_ROWS * LP_WIN + col;
+    const int window_at = wave * CT_ROWS * CT_WIN + col;
 
-    // What a thread stages does not depend on the chunk: window positions tid and tid + 256 (of 324) of each of the chunk's channels, and LP_NW weights.  A
-    // position's offset into a plane is formed once, from coordinates clamped INTO the frame: every load below is unconditional and from a valid address,
-    // and what lies outside the frame or past the last channel is replaced by zero afterwards.
+    // the input holds planes of hs x ws: (h, w) itself, or with POOL >= (2 h, 2 w)
     const size_t plane_in = (size_t)a.hs * (size_t)a.ws;
-    int pos_off[LP_NPOS], pos_lds[LP_NPOS];
-    bool pos_in[LP_NPOS];
-#pragma unroll
-    for (int r = 0; r < LP_NPOS; ++r) {
-        const int p = (int)threadIdx.x + r * LP_THREADS, pc = p < LP_WIN * LP_WIN ? p : 0;
-        const int yy = pc / LP_WIN, xx = pc - yy * LP_WIN, y = ty0 + yy - 1, x = tx0 + xx - 1;
-        pos_in[r] = p < LP_WIN * LP_WIN && y >= 0 && y < h && x >= 0 && x < w;
-        pos_lds[r] = p < LP_WIN * LP_WIN ? p : -1;
-        const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
-        // the input holds planes of hs x ws: (h, w) itself, or with POOL >= (2 h, 2 w): 2 yc + 1 <= 2 h - 1 <= hs - 1 and the columns alike (an odd last
-        // row or column is never read)
-        pos_off[r] = POOL ? 2 * yc * a.ws + 2 * xc : yc * a.ws + xc;
-    }
-    float iv[LP_CHUNK][LP_NPOS], wv[LP_NW];
+    int pos_off[CT_NPOS], pos_lds[CT_NPOS];
+    bool pos_in[CT_NPOS];
+    ct_window_positions<MODE>(pos_off, pos_lds, pos_in, tx0, ty0, h, w, a.hs, a.ws);
+    float iv[LP_CHUNK][CT_NPOS], wv[LP_NW];
     auto load_chunk = [&](const int c0) {
 #pragma unroll
         for (int cl = 0; cl < LP_CHUNK; ++cl) {
             if (FIRST && cl >= 3) {          // the first layer: three channels, the fourth of the chunk is padding
 #pragma unroll
-                for (int r = 0; r < LP_NPOS; ++r) iv[cl][r] = 0.0f;
+                for (int r = 0; r < CT_NPOS; ++r) iv[cl][r] = 0.0f;
                 continue;
             }
             const int c = c0 + cl, cc = c < cin ? c : cin - 1;          // (uniform)
             const float* const base = src + (size_t)cc * plane_in;
 #pragma unroll
-            for (int r = 0; r < LP_NPOS; ++r) {
-                const float* const q = base + pos_off[r];
-                float v = q[0];
-                if (POOL) v = fmaxf(fmaxf(v, q[1]), fmaxf(q[a.ws], q[a.ws + 1]));
+            for (int r = 0; r < CT_NPOS; ++r) {
+                float v = ct_read<MODE>(base + pos_off[r], a.ws);
                 if (FIRST) v = lp_zscore(v, cc);          // in frame only: the padding is zero in z-space
                 iv[cl][r] = (c < cin && pos_in[r]) ? v : 0.0f;
             }
         }
 #pragma unroll
         for (int n = 0; n < LP_NW; ++n) {          // runs of LP_RUN consecutive floats of one output channel's row
-            const int i = (int)threadIdx.x + n * LP_THREADS, m = i / LP_RUN, j = i - m * LP_RUN, kk = c0 * 9 + j;
+            const int i = (int)threadIdx.x + n * CT_THREADS, m = i / LP_RUN, j = i - m * LP_RUN, kk = c0 * 9 + j;
             const float v = wsrc[(size_t)m * ktot + min(kk, ktot - 1)];
             wv[n] = kk < ktot ? v : 0.0f;
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int cl = 0; cl < LP_CHUNK; ++cl)
-#pragma unroll
-            for (int r = 0; r < LP_NPOS; ++r)
-                if (pos_lds[r] >= 0) s_in[cl * LP_PLANE + pos_lds[r]] = iv[cl][r];
-#pragma unroll
-        for (int n = 0; n < LP_NW; ++n) {
-            const int i = (int)threadIdx.x + n * LP_THREADS, m = i / LP_RUN, j = i - m * LP_RUN;
-            s_w[j * LP_WROW + m] = wv[n];
         }
     };
     auto run_steps = [&](const int limit) {
@@ -166,38 +123,30 @@ __global__ void __launch_bounds__(LP_THREADS, 2) lpips_conv3_kernel(const LpArgs
 #pragma unroll
                 for (int mt = 0; mt < LP_MT; ++mt) av[mt] = s_w[(4 * s + kq) * LP_WROW + mt * 16 + col];
 #pragma unroll
-                for (int nt = 0; nt < LP_ROWS; ++nt) {
-                    const float bv = s_in[window_at + nt * LP_WIN + off[s]];
+                for (int nt = 0; nt < CT_ROWS; ++nt) {
+                    const float bv = s_in[window_at + nt * CT_WIN + off[s]];
 #pragma unroll
-                    for (int mt = 0; mt < LP_MT; ++mt) acc[mt][nt] = lp_mfma(av[mt], bv, acc[mt][nt]);
+                    for (int mt = 0; mt < LP_MT; ++mt) acc[mt][nt] = ct_mfma(av[mt], bv, acc[mt][nt]);
                 }
             }
         }
     };
-    for (int c0 = 0; c0 < cin; c0 += LP_CHUNK) {          // (uniform over the workgroup: every thread reaches the barriers)
+#pragma unroll 1
+    for (int c0 = 0; c0 < cin; c0 += LP_CHUNK) {          // (uniform over the workgroup: every thread reaches the barriers; one copy of the body: not peeled)
         load_chunk(c0);           // (into registers: in flight while the other waves finish the chunk before)
         __syncthreads();          // the chunk before has been read
-        store_chunk();
+        ct_store_window(s_in, iv, pos_lds);
+        ct_store_weights<LP_COB, LP_RUN, LP_WROW>(s_w, wv);
         __syncthreads();
         if (FIRST) run_steps((27 + 3) / 4);          // K = 27 -> 28
         else run_steps(LP_STEPS);                    // (cin is a multiple of LP_CHUNK: the host checks)
     }
 
-    const int x = tx0 + col;
     const size_t plane = (size_t)h * (size_t)w;
     float* const dst = a.out + ((size_t)img * a.cout + co0) * plane;
-#pragma unroll
-    for (int mt = 0; mt < LP_MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < LP_ROWS; ++nt) {
-            const int y = ty0 + wave * LP_ROWS + nt;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ch = mt * 16 + kq * 4 + r;
-                const float v = acc[mt][nt][r];
-                if (y < h && x < w) dst[(size_t)ch * plane + (size_t)y * w + x] = v > 0.0f ? v : 0.0f;
-            }
-        }
+    ct_for_each_output(acc, tx0, ty0, wave, col, kq, [=](int ch, int y, int x, float v) {
+        if (y < h && x < w) dst[(size_t)ch * plane + (size_t)y * w + x] = v > 0.0f ? v : 0.0f;
+    });
 }
 
 // utils.py:6-8 and lpips.py:30-36 on one tap: a thread per pixel.  Two passes over the channels (the norms, then the weighted squared differences), in
@@ -307,10 +256,10 @@ struct LpScratch {          // the arena of the header
 
 static void lp_launch(hipStream_t st, const LpArgs& a, bool pool, bool first)
 {
-    const dim3 grid((unsigned)((a.w + LP_TILE - 1) / LP_TILE), (unsigned)((a.h + LP_TILE - 1) / LP_TILE), (unsigned)(2 * (a.cout / LP_COB)));
-    if (first) hipLaunchKernelGGL((lpips_conv3_kernel<false, true>), grid, dim3(LP_THREADS), 0, st, a);
-    else if (pool) hipLaunchKernelGGL((lpips_conv3_kernel<true, false>), grid, dim3(LP_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((lpips_conv3_kernel<false, false>), grid, dim3(LP_THREADS), 0, st, a);
+    const dim3 grid((unsigned)((a.w + CT_TILE - 1) / CT_TILE), (unsigned)((a.h + CT_TILE - 1) / CT_TILE), (unsigned)(2 * (a.cout / LP_COB)));
+    if (first) hipLaunchKernelGGL((lpips_conv3_kernel<false, true>), grid, dim3(CT_THREADS), 0, st, a);
+    else if (pool) hipLaunchKernelGGL((lpips_conv3_kernel<true, false>), grid, dim3(CT_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((lpips_conv3_kernel<false, false>), grid, dim3(CT_THREADS), 0, st, a);
 }
 
 static LpArgs lp_layer(const float* in_x, const float* in_y, const float* weight, const float* bias, float* out, int cin, int cout, int h, int w, int hs, int ws)

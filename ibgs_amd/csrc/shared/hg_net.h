@@ -5,8 +5,10 @@
 //   d1 = relu(conv3([u1, e1]; dec1 76 -> 38))     f = relu(conv1([d1, x]; fuse_input 76 -> 38))   residual = conv1(f; final 38 -> 3)
 // e1, e2, u2, d2, u1 and b are the STAGES: the outputs of the first six layers, at level 0 (H x W), 1 (H / 2 x W / 2) or 2 (H / 2 / 2 x W / 2 / 2).  THE ARENA
 // of a forward holds them in the order of their layers -- e1, e2, b, u2, d2, u1 -- each at the next multiple of 128 bytes; d1 and f never reach memory.
-// Host code and what lies outside a kernel body only: a kernel's geometry (tile, threads, window, staged planes) is its own unit's.  ibgs_amd/_build.py lists
-// this header under the three units (UNIT_HEADERS) and no other: it sits in a subdirectory of csrc/ so that no other unit's profile stamp holds it.
+// Host code and what lies outside a kernel body only.  The geometry of the float32 kernels (tile, threads, window, staged planes), their lane map and the rule
+// by which a layer reads its first input (a kernel's MODE: CT_PLAIN, CT_POOL, CT_UP) are conv_tile.h's, next to this file; the half-precision kernel's staging
+// is its own unit's.  ibgs_amd/_build.py lists this header under the three units (UNIT_HEADERS) and no other: it sits in a subdirectory of csrc/ so that no
+// other unit's profile stamp holds it.
 #pragma once
 #include "../common.h"
 #include "../../../include/ibgs_hourglass.h"
@@ -14,7 +16,6 @@
 namespace ibgs {
 
 constexpr int HG_C = IBGS_HG_CHANNELS;
-enum { HG_PLAIN = 0, HG_POOL = 1, HG_UP = 2 };          // how a layer reads its first input (a kernel's MODE)
 
 // the nine layers in the order of the C ABI: the rows of the weight, the channels of its two inputs ([a | b] along Cin), the kernel's side, the output's level
 struct HgLayer { const char* name; int cout, ca, cb, side, level; };

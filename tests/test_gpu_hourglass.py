@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 F64_K = 2.0
 FLOOR = 2.0 ** -22
-T = 16          # side of a workgroup's output tile (csrc/hourglass.hip: HG_TILE; tests/test_hourglass_host.py checks the constant).  The grid is not capped.
+T = 16          # side of a workgroup's output tile (csrc/shared/conv_tile.h: CT_TILE; tests/test_hourglass_host.py checks the constant).  The grid is not capped.
 FRAMES = [(4, 4), (5, 7), (16, 24), (17, 67), (4, T + 1), (T + 1, 4), (2 * T + 3, 2 * T + 5)]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hourglass.npz")
 CHECKED = ref.STAGES + ("residual",)

@@ -60,7 +60,7 @@ def test_build_registration_and_the_kernels():
     assert _build.SOURCES[-1] == "hourglass" and _build.SOURCES.index("hghalf") < _build.SOURCES.index("hourglass")
     assert "hghalf" in _build.UNIT_HEADERS and "hghalf" in _build.tu_shas() and "hghalf" not in _build.EXTRA
     assert _build.compile_flags("hghalf") == _build.compile_flags("hourglass")
-    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h"]
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h", "conv_tile.h"]
     assert all(os.path.exists(h) for h in _build.UNIT_HEADERS["hghalf"])
     # the float32 unit's kernel still goes where it went
     assert _build.tu_of("hg_conv3_kernel") == "hourglass" and _build.tu_of("hgb_wgrad_kernel") == "hgtrain"
@@ -72,7 +72,7 @@ def test_build_registration_and_the_kernels():
     assert re.search(r"constexpr int HGH_TILE = 16;", code) and re.search(r"constexpr int HGH_THREADS = 256;", code)
     assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ HGH_TILE - 1\) / HGH_TILE\), \(unsigned\)\(\(a\.h \+ HGH_TILE - 1\) / HGH_TILE\)\);", code)
     assert len(re.findall(r"hgh_launch<", code)) == 7 and len(re.findall(r"hipLaunchKernelGGL\(hgh_pack_kernel", code)) == 1
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h"]
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

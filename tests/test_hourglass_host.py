@@ -17,6 +17,7 @@ from tests import hourglass_ref as ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ibgs_amd", "csrc", "hourglass.hip")
 NET_H = os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "hg_net.h")          # the network as hourglass.hip, hgtrain.hip and hghalf.hip share it
+TILE_H = os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "conv_tile.h")       # the 16 x 16 tile as hourglass.hip, hgtrain.hip and lpips.hip share it
 GOLDEN = os.path.join(ROOT, "tests", "golden", "hourglass.npz")
 
 
@@ -72,15 +73,20 @@ def test_kernels_attributed_to_the_hourglass_unit():
     code = _build._code_only(src)
     assert "atomic" not in code.lower()          # nothing crosses a workgroup
     # the constants the GPU tests size their frames by; the grid is two-dimensional and uncapped
-    assert re.search(r"constexpr int HG_TILE = 16;", code) and re.search(r"constexpr int HG_THREADS = 256;", code)
-    assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ HG_TILE - 1\) / HG_TILE\), \(unsigned\)\(\(a\.h \+ HG_TILE - 1\) / HG_TILE\)\);", code)
+    # (they are the shared tile's, and this unit launches by them)
+    tile = _build._code_only(open(TILE_H).read())
+    assert re.search(r"constexpr int CT_TILE = 16;", tile) and re.search(r"constexpr int CT_THREADS = 256;", tile)
+    assert not re.search(r"constexpr int \w*(TILE|THREADS) =", code) and re.search(r"__launch_bounds__\(CT_THREADS, 2\) hg_conv3_kernel", code)
+    assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ CT_TILE - 1\) / CT_TILE\), \(unsigned\)\(\(a\.h \+ CT_TILE - 1\) / CT_TILE\)\);", code)
+    assert re.search(r"hipLaunchKernelGGL\(\(hg_conv3_kernel<CA, CB, COUT, MODE, FUSE>\), grid, dim3\(CT_THREADS\), 0, st, a\);", code)
     assert len(re.findall(r"hg_launch<", code)) == 7          # seven launches
-    assert "mfma_f32_16x16x4f32" in code
+    assert re.findall(r"__builtin_amdgcn_mfma_\w+", tile) == ["__builtin_amdgcn_mfma_f32_16x16x4f32"] and "ct_mfma(" in code and "__builtin_amdgcn_mfma" not in code
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if "hourglass" in f and not f.startswith("_")) == ["hourglass.hip"]
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "../../include/ibgs_hourglass.h"]
-    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hourglass"]] == ["ibgs_hourglass.h", "hg_net.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "../../include/ibgs_hourglass.h"]
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hourglass"]] == ["ibgs_hourglass.h", "hg_net.h", "conv_tile.h"]
     shared = _build._code_only(open(NET_H).read())
-    assert re.search(r"enum \{ HG_PLAIN = 0, HG_POOL = 1, HG_UP = 2 \};", shared) and re.search(r"constexpr int HG_C = IBGS_HG_CHANNELS;", shared)
+    assert re.search(r"enum \{ CT_PLAIN = 0, CT_POOL = 1, CT_UP = 2 \};", tile) and re.search(r"constexpr int HG_C = IBGS_HG_CHANNELS;", shared)
+    assert not re.search(r"_PLAIN = 0", shared)
     for unit in ("hourglass", "hgtrain", "hghalf"):          # ... and nobody keeps a copy of what the header holds
         code = _build._code_only(open(os.path.join(ROOT, "ibgs_amd", "csrc", unit + ".hip")).read())
         assert not re.search(r"_PLAIN = 0|_shape_ok\(const char|names\[9\]|_blend\(float", code), unit

@@ -55,16 +55,21 @@ def test_build_registration_and_the_kernels():
         assert not any(sub in k for sub, _ in _build.KERNEL_TU[:at[0]]), k
     assert "lpips" in _build.SOURCES and "lpips" in _build.tu_shas() and "lpips" not in _build.EXTRA
     assert _build.compile_flags("lpips") == _build.compile_flags("hourglass")
-    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["lpips"]] == ["ibgs_lpips.h"] and all(os.path.exists(h) for h in _build.UNIT_HEADERS["lpips"])
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["lpips"]] == ["ibgs_lpips.h", "conv_tile.h"] and all(os.path.exists(h) for h in _build.UNIT_HEADERS["lpips"])
     # the other units' kernels still go where they went
     assert _build.tu_of("hg_conv3_kernel") == "hourglass" and _build.tu_of("hgh_conv3_kernel") == "hghalf" and _build.tu_of("ssim_forward_kernel") == "ssim"
     assert _build.tu_of("l1_loss_kernel") == "loss" and _build.tu_of("meval_cell_count") == "mesh_eval"
     code = _build._code_only(src)
     assert "atomic" not in code.lower() and "asm" not in code.lower()          # nothing crosses a workgroup but the partials; builtins only
-    assert re.findall(r"__builtin_amdgcn_mfma_\w+", code) == ["__builtin_amdgcn_mfma_f32_16x16x4f32"]          # the exact f32 form, once
-    assert re.search(r"constexpr int LP_TILE = 16;", code) and re.search(r"constexpr int LP_THREADS = 256;", code)
+    tile = _build._code_only(open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "conv_tile.h")).read())          # the 16 x 16 tile it shares with the hourglass units
+    assert re.findall(r"__builtin_amdgcn_mfma_\w+", tile) == ["__builtin_amdgcn_mfma_f32_16x16x4f32"]          # the exact f32 form, once
+    assert "__builtin_amdgcn_mfma" not in code and "ct_mfma(" in code
+    assert re.search(r"constexpr int CT_TILE = 16;", tile) and re.search(r"constexpr int CT_THREADS = 256;", tile)
+    assert not re.search(r"constexpr int (\w*TILE|LP_THREADS) =", code) and re.search(r"__launch_bounds__\(CT_THREADS, 2\) lpips_conv3_kernel", code)
+    assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ CT_TILE - 1\) / CT_TILE\), \(unsigned\)\(\(a\.h \+ CT_TILE - 1\) / CT_TILE\), ", code)
+    assert len(re.findall(r"grid, dim3\(CT_THREADS\), 0, st, a\)", code)) == 3
     assert len(re.findall(r"lpips_conv3_kernel<\w+, \w+>", code)) == 3          # three instantiations: plain, pooled, first
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "block_ops.h", "../../include/ibgs_lpips.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "block_ops.h", "shared/conv_tile.h", "../../include/ibgs_lpips.h"]
 
 
 def test_no_code_path_opens_a_url():
