@@ -17,7 +17,8 @@ the colour network: a tolerance contract too; its moments add exact f64 products
 (the reduced-resolution colour tail: a tolerance contract; its blends are written as fmaf, its MLP is the matrix-core chain it shares with coloragg.hip
 (csrc/shared/pv_mlp.h), and the expressions that must not be contracted say so themselves), and rsztrain.hip (that tail's backward: the same chain, the
 blends it shares with resample.hip (csrc/shared/rsz_taps.h), the per-slot backward it shares with coloragg.hip (csrc/shared/pv_mlp_bwd.h), and a gather whose
-products and sums say themselves that they are not contracted).
+products and sums say themselves that they are not contracted), and export.hip (the frame export: a contract of equal bytes, and no flag either: the unit
+states at file scope that none of its operations is contracted).
 csrc/block_ops.h holds the workgroup reduce / scan helpers of knn, tsdf, mesh, mesh_eval, registration and dtu (no multiply-add in them: the flag above does
 not bear on them); ibgs_amd/_device.py is the Python side those six units share.
 """
@@ -30,7 +31,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "resample", "rsztrain", "lpips", "hgtrain", "hghalf", "hourglass"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "export", "resample", "rsztrain", "lpips", "hgtrain", "hghalf", "hourglass"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -66,6 +67,7 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
                 "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h"), CONV_TILE_H],
                 "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
+                "export": [os.path.join(HERE, "..", "include", "ibgs_export.h")],
                 "resample": [os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, RSZ_TAPS_H],
                 "rsztrain": [os.path.join(HERE, "..", "include", "ibgs_resample_train.h"), os.path.join(HERE, "..", "include", "ibgs_resample.h"), PV_MLP_H, PV_MLP_BWD_H,
                              RSZ_TAPS_H]}
@@ -111,8 +113,8 @@ def csrc_sha():
 # unit (and the headers) are unchanged -- a host-only edit of api.hip does not make the blend kernels' counters stale
 # ("meval_" first: the later entries match by substring, and a meval_cell_count would otherwise be credited to binning; "dtu_" before "mesh_" and "scan_":
 # a dtu_emit_mesh_* or dtu_scan_* would otherwise go to those units; "lpips_" ahead of every entry that could claim one of its kernels by substring -- all but
-# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel; the same holds for "rsz_" and "rzt_")
-KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("rsz_", "resample"), ("rzt_", "rsztrain"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
+# "meval_", which no lpips_* name holds; no other unit's substring occurs in an expo_* name, and "expo_" in no other unit's kernel; the same holds for "rsz_" and "rzt_", and for "fexp_")
+KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("fexp_", "export"), ("rsz_", "resample"), ("rzt_", "rsztrain"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
              ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))
@@ -125,8 +127,14 @@ def tu_of(kernel_name):
     return None
 
 
+# units that are built and attributed like the others but carry no profile stamp: no committed rocprofv3 summary holds a kernel of theirs and bench.py quotes
+# none (the frame export runs after the step, outside everything bench.py measures; its numbers are tools/bench_export.py's own text, profiles/export.txt).
+# tu_of() still names the unit for such a kernel, and bench.py's tu_shas().get(unit) then finds no stamp: nothing stale can be quoted for it.
+UNSTAMPED = ("export",)
+
+
 def tu_shas():
-    """{translation unit: fingerprint of its .hip + every header (csrc/*.h, include/ibgs_rast.h)}, comments and blank lines excluded."""
+    """{translation unit: fingerprint of its .hip + every header (csrc/*.h, include/ibgs_rast.h)}, comments and blank lines excluded; the units of UNSTAMPED have none."""
     import hashlib
     hdr = hashlib.sha1()
     for f in sorted(os.listdir(CSRC)):
@@ -135,6 +143,8 @@ def tu_shas():
     hdr.update(_code_only(open(os.path.join(HERE, "..", "include", "ibgs_rast.h"), "r").read()).encode())
     out = {}
     for name in SOURCES:
+        if name in UNSTAMPED:
+            continue
         h = hdr.copy()
         h.update(_code_only(open(os.path.join(CSRC, name + ".hip"), "r").read()).encode())
         for u in UNIT_HEADERS.get(name, []):

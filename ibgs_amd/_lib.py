@@ -240,6 +240,29 @@ EXPO_PIXELS_PER_THREAD = 4
 EXPO_MOMENTS, EXPO_SOLVE, EXPO_FIT = 1, 2, 3
 EXPO_PIVOT_MIN = 1e-11
 
+# every symbol include/ibgs_export.h declares (tests/test_frame_export_host.py compares the two)
+FEXP_EXPORTS = ["ibgs_fexp_sizeof_frame", "ibgs_required_export", "ibgs_fexp_frame_u8", "ibgs_fexp_percentile", "ibgs_fexp_quantize"]
+FEXP_MAX_SIDE = 65536
+FEXP_MAX_PIXELS = 1 << 30
+FEXP_MAX_SELECT = 1 << 24
+FEXP_MAX_IMAGES = 8
+FEXP_MAX_Q = 4
+FEXP_ROUND, FEXP_TRUNCATE, FEXP_NORMAL, FEXP_RESIDUAL, FEXP_COLORIZE = range(5)
+FEXP_ZERO_RESIDUAL, FEXP_NO_VALID = 1, 2
+
+
+class FexpImage(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("mode", ctypes.c_int32), ("channels", ctypes.c_int32), ("bgr", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class FexpFrame(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("n_images", ctypes.c_int32), ("reserved", ctypes.c_int32), ("images", FexpImage * 8),
+                ("lut", ctypes.c_void_p), ("invalid_mask", ctypes.c_void_p), ("use_invalid_val", ctypes.c_int32), ("invalid_val", ctypes.c_float),
+                ("have_vmin", ctypes.c_int32), ("have_vmax", ctypes.c_int32), ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("q32", ctypes.c_float * 2),
+                ("background", ctypes.c_uint8 * 4), ("status", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
 # every symbol include/ibgs_resample.h declares (tests/test_resample_host.py compares the two)
 RSZ_EXPORTS = ["ibgs_rsz_features_forward", "ibgs_rsz_residual_upsample"]
 RSZ_MAX_SRC = 5
@@ -508,6 +531,22 @@ def load():
     for f in (lib.ibgs_expo_apply, lib.ibgs_expo_apply_backward):          # (stream, H, W, affine, status, image, out)
         f.restype = i32
         f.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    for name in FEXP_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_fexp_sizeof_frame.restype = sz
+    lib.ibgs_fexp_sizeof_frame.argtypes = []
+    lib.ibgs_required_export.restype = sz
+    lib.ibgs_required_export.argtypes = [i64, i64]
+    lib.ibgs_fexp_frame_u8.restype = i32
+    lib.ibgs_fexp_frame_u8.argtypes = [vp, ctypes.POINTER(FexpFrame)]
+    lib.ibgs_fexp_percentile.restype = i32
+    # (stream, n, values, invalid_mask, use_invalid_val, invalid_val, nq, q32 (host), out, status, scratch, bytes)
+    lib.ibgs_fexp_percentile.argtypes = [vp, i64, vp, vp, i32, f32, i32, ctypes.POINTER(f32), vp, vp, vp, sz]
+    lib.ibgs_fexp_quantize.restype = i32
+    lib.ibgs_fexp_quantize.argtypes = [vp, i64, vp, vp]
+    if lib.ibgs_fexp_sizeof_frame() != ctypes.sizeof(FexpFrame):
+        raise RasterizerLibraryError("ctypes frame-export struct layout does not match libibgs_rast.so (stale build?)")
     for name in RSZ_EXPORTS:
         if not hasattr(lib, name):
             raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)

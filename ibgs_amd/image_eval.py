@@ -12,15 +12,19 @@ before it existed.
 HIP only: raises for CPU tensors (there is no CPU path)."""
 import torch
 
-from . import losses
+from . import frame_export, losses
 from . import lpips as _lpips
 
 
-def image_metrics(renders, gts, lpips_net=None):
+def image_metrics(renders, gts, lpips_net=None, quantize=False):
     """renders, gts: (N, C, H, W) (or (C, H, W): one image).  -> {"ssim": (N,), "psnr": (N,), "l1": (N,)} float32 on the device, nothing waits for it.
     ssim = `ssim(render, gt)` per image, psnr = 20 log10(1 / sqrt(mse)) per image, l1 = mean |render - gt| per image.
-    With `lpips_net` (an `LPIPSNet`; C = 3, sides 16 .. 4096) also "lpips": (N,), `lpips.lpips(renders, gts, lpips_net)`."""
+    With `lpips_net` (an `LPIPSNet`; C = 3, sides 16 .. 4096) also "lpips": (N,), `lpips.lpips(renders, gts, lpips_net)`.
+    With `quantize=True` both images first go through `frame_export.quantize` -- save_image's rounding to a byte, then / 255 -- which is what the
+    reference's metrics.py measures: it reads back the 8-bit PNGs render.py wrote (metrics.py:24-34).  Without the keyword every call keeps its bits."""
     dims = losses._ssim_check("image_metrics", renders, gts, 11, (3, 4))
+    if quantize:
+        renders, gts = frame_export.quantize(renders), frame_export.quantize(gts)
     x = renders.detach().float().contiguous()
     y = gts.detach().float().contiguous()
     n = dims[0]
@@ -34,11 +38,12 @@ def image_metrics(renders, gts, lpips_net=None):
     return out
 
 
-def evaluate_images(renders, gts, names=None, lpips_net=None):
+def evaluate_images(renders, gts, names=None, lpips_net=None, quantize=False):
     """What metrics.py:75-98 computes for SSIM and PSNR, and with `lpips_net` (an `LPIPSNet`) for LPIPS too.  renders, gts: a 4-D tensor each, or lists of (3, H, W) / (1, 3, H, W) tensors whose sizes may differ
     from view to view (views of one size go into one launch).  names: one per view (default "00000", "00001", ..).
     -> {"SSIM": mean, "PSNR": mean, "per_view": {"SSIM": {name: value}, "PSNR": {name: value}}}, Python floats, after ONE device-to-host copy.
-    With `lpips_net` the dictionary also holds "LPIPS": mean and per_view["LPIPS"]: {name: value} -- still after ONE copy; without it, neither."""
+    With `lpips_net` the dictionary also holds "LPIPS": mean and per_view["LPIPS"]: {name: value} -- still after ONE copy; without it, neither.
+    `quantize=True`: every view is measured as `image_metrics(..., quantize=True)` measures it (the reference's protocol on 8-bit images)."""
     def views(t, what):
         if torch.is_tensor(t):
             if t.dim() != 4:
@@ -64,7 +69,7 @@ def evaluate_images(renders, gts, names=None, lpips_net=None):
         groups.setdefault((tuple(a.shape), a.device), []).append(i)
     order, parts = [], []
     for idx in groups.values():
-        m = image_metrics(torch.stack([r[i] for i in idx]), torch.stack([g[i] for i in idx]), lpips_net)
+        m = image_metrics(torch.stack([r[i] for i in idx]), torch.stack([g[i] for i in idx]), lpips_net, quantize)
         order += idx
         parts.append(torch.stack([m["ssim"], m["psnr"]] + ([m["lpips"]] if lpips_net is not None else [])).to(parts[0].device if parts else m["ssim"].device))
     table = torch.cat(parts, dim=1)
