@@ -10,7 +10,7 @@ ssim.hip takes no such flag: its contract is a tolerance, its filter passes are 
 themselves (#pragma clang fp contract(off)); geoloss.hip, which runs the same passes and forms (csrc/shared/ssim_window.h), is built the same way, and so is coloragg.hip
 (the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains), and hourglass.hip (the CNN behind it, forward only: the same), and hgtrain.hip (that CNN's backward: the same),
 and hghalf.hip (that CNN's forward in half precision: the same; csrc/shared/hg_net.h states the network -- its layers, its stage arena, its host-side checks -- once for
-these three units), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
+these units), and hghtrain.hip (that CNN's backward in half precision: the same), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
 are the same matrix-core fma chains -- csrc/shared/conv_tile.h states their 16 x 16 tile and the rule by which a layer reads its source once for it and the three
 hourglass units; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
 the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
@@ -83,7 +83,7 @@ def _hipcc():
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "..", "include", "ibgs_rast.h"))
-    deps += [h for name in SOURCES for h in UNIT_HEADERS.get(name, [])]
+    deps += [h for name in SOURCES for h in UNIT_HEADERS.get(name, [])] + [h for hs in SIDE_UNITS.values() for h in hs]
     return max(os.path.getmtime(d) for d in deps)
 
 
@@ -117,7 +117,7 @@ def csrc_sha():
 KERNEL_TU = (("meval_", "mesh_eval"), ("lpips_", "lpips"), ("geoloss_", "geoloss"), ("cagg_", "coloragg"), ("expo_", "exposure"), ("fexp_", "export"), ("rsz_", "resample"), ("rzt_", "rsztrain"), ("pcreg_", "registration"), ("dtu_", "dtu"), ("ssim_", "ssim"), ("tsdf_", "tsdf"), ("mesh_", "mesh"), ("render_fwd", "render_fwd"), ("pack_rgba", "render_fwd"), ("render_bwd", "render_bwd"), ("geo_window", "render_bwd"), ("tile_order", "render_bwd"),
              ("preprocess_bwd", "preprocess_bwd"), ("sh_grad", "preprocess_bwd"), ("preprocess_kernel", "preprocess"), ("sh_color", "preprocess"), ("mark_visible", "preprocess"),
              ("onesweep", "scan_sort"), ("radix", "scan_sort"), ("scan_", "scan_sort"), ("cell_", "binning"), ("expand_", "binning"), ("tile_ranges", "binning"),
-             ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))
+             ("rendered_note", "api"), ("l1_", "loss"), ("depth_normal", "depth_normal"), ("activate_", "activate"), ("adam", "adam"), ("compact", "compact"), ("det_", "deterministic"), ("knn", "knn"), ("hght_", "hghtrain"), ("hgh_", "hghalf"), ("hgb_", "hgtrain"), ("hg_", "hourglass"))
 
 
 def tu_of(kernel_name):
@@ -131,6 +131,17 @@ def tu_of(kernel_name):
 # none (the frame export runs after the step, outside everything bench.py measures; its numbers are tools/bench_export.py's own text, profiles/export.txt).
 # tu_of() still names the unit for such a kernel, and bench.py's tu_shas().get(unit) then finds no stamp: nothing stale can be quoted for it.
 UNSTAMPED = ("export",)
+# units outside the stamped set altogether: SOURCES, UNIT_HEADERS and tu_shas() are the tables the committed profile summaries were stamped against, and a unit
+# that no summary and no bench.py figure refers to does not enter them.  Such a unit is compiled with the same flags, rebuilt on an edit of any header it lists
+# (every header it includes outside csrc/*.h and include/ibgs_rast.h) and linked into the same library; KERNEL_TU attributes its kernels.  hghtrain.hip is the
+# half-precision backward of the hourglass (tools/bench_hourglass.py --train measures it; its text is profiles/hourglass.txt).
+SIDE_UNITS = {"hghtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_half_train.h"), os.path.join(HERE, "..", "include", "ibgs_hg_half.h"),
+                           os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H]}
+
+
+def _headers_of(name):
+    """The headers a translation unit is rebuilt for, beyond csrc/*.h and include/ibgs_rast.h"""
+    return SIDE_UNITS[name] if name in SIDE_UNITS else UNIT_HEADERS.get(name, [])
 
 
 def tu_shas():
@@ -158,7 +169,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     newest = _newest_dep()
-    objs = [os.path.join(OBJ, n + ".o") for n in SOURCES]
+    objs = [os.path.join(OBJ, n + ".o") for n in SOURCES + list(SIDE_UNITS)]
     return any((not os.path.exists(o)) or os.path.getmtime(o) < newest for o in objs) or os.path.getmtime(LIB) < newest
 
 
@@ -171,7 +182,7 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(OBJ, name + ".o")
-        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
+        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in _headers_of(name)])
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
         cmd = [hipcc] + compile_flags(name) + ["-c", src, "-o", obj]
@@ -181,7 +192,7 @@ def build(force=False, verbose=False):
         return obj
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(compile_one, SOURCES))
+        objs = list(ex.map(compile_one, SOURCES + list(SIDE_UNITS)))
     if force or (not os.path.exists(LIB)) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:

@@ -219,6 +219,12 @@ HGB_EXPORTS = ["ibgs_hgb_required_scratch", "ibgs_hgb_backward"]
 HGH_EXPORTS = ["ibgs_hgh_required_scratch", "ibgs_hgh_forward"]
 HGH_PACKED_WEIGHT_BYTES = 281600
 
+# every symbol include/ibgs_hg_half_train.h declares (tests/test_hghtrain_host.py compares the two), and its constants
+HGHT_EXPORTS = ["ibgs_hgh_train_required_scratch", "ibgs_hgh_train_backward"]
+HGHT_E_TARGET = 10
+HGHT_SCALE_AUTO, HGHT_SCALE_FIXED = 0, 1
+HGHT_PACKED_WEIGHT_BYTES = 405504
+
 # every symbol include/ibgs_lpips.h declares (tests/test_lpips_host.py compares the two)
 LPIPS_EXPORTS = ["ibgs_lpips_required_scratch", "ibgs_lpips_conv3", "ibgs_lpips_forward"]
 LPIPS_MIN_SIDE = 16
@@ -509,6 +515,14 @@ def load():
     lib.ibgs_hgh_required_scratch.argtypes = [i64, i64]
     lib.ibgs_hgh_forward.restype = i32
     lib.ibgs_hgh_forward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, sz]
+    for name in HGHT_EXPORTS:
+        if not hasattr(lib, name):
+            raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)
+    lib.ibgs_hgh_train_required_scratch.restype = sz
+    lib.ibgs_hgh_train_required_scratch.argtypes = [i64, i64]
+    lib.ibgs_hgh_train_backward.restype = i32
+    # (stream, H, W, x, 18 parameters, burned, forward arena, grad_residual, grad_image_pred, scale mode, grad_scale_log2, status, grad_x, 18 gradients, scratch, bytes)
+    lib.ibgs_hgh_train_backward.argtypes = [vp, i32, i32, vp] + [vp] * 18 + [f32, vp, vp, vp, i32, i32, vp, vp] + [vp] * 18 + [vp, sz]
     for name in LPIPS_EXPORTS:
         if not hasattr(lib, name):
             raise RasterizerLibraryError("libibgs_rast.so lacks symbol %s" % name)

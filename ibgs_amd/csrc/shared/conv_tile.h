@@ -1,6 +1,6 @@
 // The 16 x 16-tile implicit GEMM on v_mfma_f32_16x16x4_f32, stated once for the three kernels that run it: hg_conv3_kernel (hourglass.hip), hgb_conv_kernel
 // (hgtrain.hip) and lpips_conv3_kernel (lpips.hip); and the rule by which a layer reads its source (plain, the 2 x 2 maximum, the nearest upsample), which
-// hgb_wgrad_kernel (hgtrain.hip) and hgh_conv3_kernel (hghalf.hip) follow too.  Device code and constants only.  A kernel keeps what is its own: its chunk
+// hgb_wgrad_kernel (hgtrain.hip), hgh_conv3_kernel (hghalf.hip) and the kernels of hghtrain.hip follow too.  Device code and constants only.  A kernel keeps what is its own: its chunk
 // loop with the two barriers, its loads of a chunk, its table of tap offsets and the k-steps that read it, its epilogue.
 //
 // THE TILE  256 threads = 4 waves per 16 x 16 output tile; a wave owns four rows of it and MT result tiles of 16 output channels.  Output channels are M, 16
@@ -12,7 +12,7 @@
 // THE STAGING DISCIPLINE (tests/test_gpu_dirty_buffers.py)  coordinates are clamped INTO the frame before an offset is formed, every
 // load is unconditional and from a valid address (so the loads of a chunk are all in flight together), and what lies outside the frame or past the last
 // channel is replaced by zero afterwards.
-// ibgs_amd/_build.py lists this header under the four units (UNIT_HEADERS) and no other.
+// ibgs_amd/_build.py lists this header under the five units (UNIT_HEADERS; SIDE_UNITS for hghtrain.hip) and no other.
 #pragma once
 #include "../common.h"
 

@@ -1,5 +1,5 @@
-// The hourglass CNN of the colour aggregation network, stated once for the three units that run it: hourglass.hip (the float32 forward), hgtrain.hip (the
-// backward, which reads the forward's arena) and hghalf.hip (the half-precision forward).  The definition is include/ibgs_hourglass.h:
+// The hourglass CNN of the colour aggregation network, stated once for the four units that run it: hourglass.hip (the float32 forward), hgtrain.hip (the
+// backward, which reads the forward's arena), hghalf.hip (the half-precision forward) and hghtrain.hip (the half-precision backward, which reads that one's arena).  The definition is include/ibgs_hourglass.h:
 //   e1 = relu(conv3(x; enc1 38 -> 38))            e2 = relu(conv3(pool(e1); enc2 38 -> 19))       b = relu(conv3(pool(e2); enc3 19 -> 9))
 //   u2 = relu(conv3(up(b); up2_conv 9 -> 19))     d2 = relu(conv3([u2, e2]; dec2 38 -> 19))       u1 = relu(conv3(up(d2); up1_conv 19 -> 38))
 //   d1 = relu(conv3([u1, e1]; dec1 76 -> 38))     f = relu(conv1([d1, x]; fuse_input 76 -> 38))   residual = conv1(f; final 38 -> 3)
@@ -7,7 +7,7 @@
 // of a forward holds them in the order of their layers -- e1, e2, b, u2, d2, u1 -- each at the next multiple of 128 bytes; d1 and f never reach memory.
 // Host code and what lies outside a kernel body only.  The geometry of the float32 kernels (tile, threads, window, staged planes), their lane map and the rule
 // by which a layer reads its first input (a kernel's MODE: CT_PLAIN, CT_POOL, CT_UP) are conv_tile.h's, next to this file; the half-precision kernel's staging
-// is its own unit's.  ibgs_amd/_build.py lists this header under the three units (UNIT_HEADERS) and no other: it sits in a subdirectory of csrc/ so that no
+// is its own unit's.  ibgs_amd/_build.py lists this header under the four units (UNIT_HEADERS; SIDE_UNITS for hghtrain.hip) and no other: it sits in a subdirectory of csrc/ so that no
 // other unit's profile stamp holds it.
 #pragma once
 #include "../common.h"

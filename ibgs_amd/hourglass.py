@@ -10,9 +10,13 @@ out -- runs on this library's kernels, and a `ColorFusionResidualNet` checkpoint
 
 FORWARD ONLY (inference, under torch.no_grad()), hidden_dim 38, float32 by default.  `precision="float16"` selects the half-precision forward (C ABI
 include/ibgs_hg_half.h, csrc/hghalf.hip): the roundings of the reference's test-time run under torch.autocast(float16), on the f16 matrix-core instruction.
-Training keeps torch's CNN behind `coloragg.fuse_color_inputs`.  The contract is a tolerance against a float64 restatement (tests/hourglass_ref.py).
+Training (`hourglass_train`, `fuse_color_train`) runs in float32 or, with `precision="float16"` / inside `train_precision("float16")`, in half precision on the same instruction (C ABI
+include/ibgs_hg_half_train.h, csrc/hghtrain.hip).  The contract is a tolerance against a float64 restatement (tests/hourglass_ref.py).
 
 HIP only: raises when the library or a GPU tensor is missing (no torch fallback in the product path)."""
+import contextlib
+import threading
+
 import torch
 from torch import nn
 
@@ -59,6 +63,32 @@ PRECISIONS = ("float32", "float16")
 def _check_precision(name, precision):
     if precision not in PRECISIONS:
         raise ValueError("%s: precision must be \"float32\" or \"float16\", got %r" % (name, precision))
+
+
+_TRAINING = threading.local()          # .precision: what `train_precision` set on this thread
+
+
+@contextlib.contextmanager
+def train_precision(precision):
+    """`with train_precision("float16"):` -- the training calls made inside the block on this thread (`hourglass_train`, `fuse_color_train`,
+    `resample_train.fuse_color_train_scaled`) build their forward in that precision, as torch.autocast does for torch's ops; a graph built inside keeps its
+    precision when its backward runs outside.  `hourglass_train(..., precision=...)` overrides it for one call.  The test-time calls have their own keyword
+    and `hourglass_backward` its own option: neither looks here.  Outside a block, and by default, training is float32 and every call keeps its bits."""
+    _check_precision("train_precision", precision)
+    before = getattr(_TRAINING, "precision", "float32")
+    _TRAINING.precision = precision
+    try:
+        yield
+    finally:
+        _TRAINING.precision = before
+
+
+def _options(name, given, allowed):
+    """The keyword-only options of a training call: anything else is the TypeError Python itself would raise.  -> `given`"""
+    for key in given:
+        if key not in allowed:
+            raise TypeError("%s() got an unexpected keyword argument %r" % (name, key))
+    return given
 
 
 def hourglass_forward(cnn_input, params, render_scale=None, return_stages=False, precision="float32"):
@@ -295,6 +325,56 @@ def _backward_call(dev, h, w, x, flat, burned, arena, g_res, g_ip, need_x, need_
     return grad_x, grads
 
 
+def _check_scale(name, precision, grad_scale_log2, status, return_decisions=False):
+    """The checks of the half-precision training keywords, before any GPU work.  -> the scale as an int or None"""
+    if precision != "float16":
+        if grad_scale_log2 is not None or status is not None or return_decisions:
+            raise ValueError("%s: grad_scale_log2, status and return_decisions belong to precision=\"float16\"" % name)
+        return None
+    if grad_scale_log2 is not None:
+        if isinstance(grad_scale_log2, bool) or not isinstance(grad_scale_log2, int):
+            raise TypeError("%s: grad_scale_log2 must be None (automatic) or an int, got %r" % (name, grad_scale_log2))
+        if abs(grad_scale_log2) > 300:
+            raise ValueError("%s: grad_scale_log2 %d is out of range (-300 .. 300)" % (name, grad_scale_log2))
+    if status is not None:
+        if not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() != 2 or not status.is_contiguous():
+            raise ValueError("%s: status must be a contiguous int32 tensor of two words (the scale's k, the count of non-finite binary16 gradient values)" % name)
+    return grad_scale_log2
+
+
+def _status_on(name, status, dev):
+    if status is not None:
+        _device.refuse_cpu("hourglass", "%s's status" % name, status)
+        if status.device != dev:
+            raise ValueError("%s: cnn_input is on %s, status on %s" % (name, dev, status.device))
+
+
+def _backward_call_half(dev, h, w, x, flat, burned, arena, g_res, g_ip, need_x, need_params, grad_scale_log2, status):
+    """`_backward_call` for the half-precision unit (C ABI include/ibgs_hg_half_train.h); arena: that of ibgs_hgh_forward.  -> (grad_x, grads, the backward's arena)"""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        grad_x = torch.empty((C, h, w), dtype=torch.float32, device=dev) if need_x else None
+        grads = [torch.empty_like(t) for t in flat] if need_params else None
+    sc = _device.scratch(dev, _lib.load().ibgs_hgh_train_required_scratch(h, w))
+    fixed = grad_scale_log2 is not None
+    _device.call(dev, "ibgs_hgh_train_backward", h, w, x.data_ptr(), *[t.data_ptr() for t in flat], float(burned), arena.data_ptr(), ptr(g_res), ptr(g_ip),
+                 _lib.HGHT_SCALE_FIXED if fixed else _lib.HGHT_SCALE_AUTO, grad_scale_log2 if fixed else 0, ptr(status), ptr(grad_x),
+                 *([g.data_ptr() for g in grads] if need_params else [None] * 18), sc.data_ptr(), sc.numel())
+    return grad_x, grads, sc
+
+
+def _head_stages(sc, h, w):
+    """d1 and f as the backward that filled the arena `sc` recomputed them (include/ibgs_hg_half_train.h: they follow the control words): (38, h, w) float16 views"""
+    n = 80 * h * w
+    at = 128 + (n + 127) // 128 * 128
+    return tuple(sc[o:o + n].view(torch.float16).view(h, w, 40).permute(2, 0, 1)[:C] for o in (128, at))
+
+
+def _decisions(sc, h, w):
+    """The planes d1 > 0 and f > 0 the backward used, (38, h, w) bool each"""
+    return tuple(v > 0 for v in _head_stages(sc, h, w))
+
+
 def _upstream(name, what, g, h, w, dev):
     if g is None:
         return None
@@ -306,28 +386,47 @@ def _upstream(name, what, g, h, w, dev):
     return _f32(g).view(3, h, w)
 
 
-def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image_pred=None, render_scale=1.0, need_input_grad=True, need_param_grads=True):
+def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image_pred=None, render_scale=1.0, need_input_grad=True, need_param_grads=True, **half):
     """The raw backward of the hourglass: cnn_input and params as for `hourglass_forward`; `stages` the six intermediates of the forward on them -- either the
     arena of ibgs_hg_forward as a uint8 tensor (what `hourglass_train` keeps) or a dict of the tensors e1, e2, b, u2, d2, u1 (packed into one here);
     grad_residual and / or grad_image_pred (3, H, W): the upstream gradients (either may be None, not both); render_scale: the burned_in_gauss image_pred was
     formed with.  -> (grad_x (38, H, W) or None, {"enc1_w": ..., ...} or None): a group that is not needed is not computed (no weight-gradient kernel runs
     without need_param_grads; enc1's input gradient does not without need_input_grad).  d1 and f are recomputed.  Float32; the same arguments give the same
-    bits; nothing waits for the host and no argument is written.  It refuses what `hourglass_forward` refuses."""
+    bits; nothing waits for the host and no argument is written.  It refuses what `hourglass_forward` refuses.
+    `**half` are four keyword-only options: precision="float32", grad_scale_log2=None, status=None, return_decisions=False.
+    `precision="float16"` (without the keyword every bit is what it was) runs the half-precision backward (C ABI include/ibgs_hg_half_train.h,
+    csrc/hghtrain.hip): `stages` is then the arena of ibgs_hgh_forward (what the half `hourglass_train` keeps) or a dict of the six binary16 stages of
+    `hourglass_forward(..., return_stages=True, precision="float16")`; products have binary16 operands and float32 accumulation, each pre-activation gradient
+    is rounded to binary16 once, and the gradients returned are float32, unrounded.  The upstream is scaled by an exact 2^k inside and the results by 2^-k:
+    `grad_scale_log2=None` chooses k on the device from max |upstream| (no synchronisation), an int fixes it; the caller needs no loss scaling.  `status`:
+    an optional int32 device tensor of two words, written with the k that was used and the number of non-finite binary16 gradient values that were stored
+    (overflow is not hidden: it reaches the outputs).  `return_decisions=True` appends the boolean planes (d1 > 0, f > 0), (38, H, W) each, that the
+    backward used."""
     name = "hourglass_backward"
+    _options(name, half, ("precision", "grad_scale_log2", "status", "return_decisions"))
+    precision, grad_scale_log2, status = half.get("precision", "float32"), half.get("grad_scale_log2"), half.get("status")
+    return_decisions = half.get("return_decisions", False)
+    _check_precision(name, precision)
     x, h, w, tensors = _checked(name, cnn_input, params)
+    grad_scale_log2 = _check_scale(name, precision, grad_scale_log2, status, return_decisions)
     _on_one_device(name, x, tensors)
     dev = x.device
+    is_half = precision == "float16"
     if grad_residual is None and grad_image_pred is None:
         raise ValueError("%s: grad_residual and grad_image_pred are both None" % name)
     if not (need_input_grad or need_param_grads):
         raise ValueError("%s: neither the input gradient nor the parameter gradients are asked for" % name)
     g_res = _upstream(name, "grad_residual", grad_residual, h, w, dev)
     g_ip = _upstream(name, "grad_image_pred", grad_image_pred, h, w, dev)
-    need = _lib.load().ibgs_hg_required_scratch(h, w)
+    _status_on(name, status, dev)
+    need = (_lib.load().ibgs_hgh_required_scratch if is_half else _lib.load().ibgs_hg_required_scratch)(h, w)
     if isinstance(stages, dict):
         sides = ((h, w), (h // 2, w // 2), (h // 2 // 2, w // 2 // 2))
         arena = _device.scratch(dev, need)
-        views = _arena_views(arena, h, w)
+        if is_half:          # the padding channels of a binary16 stage are zeros, and h(x) leads the arena
+            arena.zero_()
+            arena[:80 * h * w].view(torch.float16).view(h, w, 40)[:, :, :C].copy_(_f32(x).view(C, h, w).permute(1, 2, 0))
+        views = _arena_views(arena, h, w, is_half)
         for stage, ch, level in STAGES:
             if stage not in stages or not torch.is_tensor(stages[stage]) or tuple(stages[stage].shape[-3:]) != (ch,) + sides[level] or stages[stage].numel() != views[stage].numel():
                 raise ValueError("%s: stages[%r] must be a (%d, %d, %d) tensor" % (name, stage, ch, sides[level][0], sides[level][1]))
@@ -341,6 +440,11 @@ def hourglass_backward(cnn_input, params, stages, grad_residual=None, grad_image
             raise ValueError("%s: cnn_input is on %s, stages on %s" % (name, dev, stages.device))
         arena = stages
     flat = [_f32(t) for _, t in tensors]
+    if is_half:
+        grad_x, grads, sc = _backward_call_half(dev, h, w, _f32(x), flat, float(render_scale), arena, g_res, g_ip, bool(need_input_grad), bool(need_param_grads),
+                                                grad_scale_log2, status)
+        out = (grad_x, (None if grads is None else {what: g for (what, _), g in zip(tensors, grads)}))
+        return out + (_decisions(sc, h, w),) if return_decisions else out
     grad_x, grads = _backward_call(dev, h, w, _f32(x), flat, float(render_scale), arena, g_res, g_ip, bool(need_input_grad), bool(need_param_grads))
     return grad_x, (None if grads is None else {what: g for (what, _), g in zip(tensors, grads)})
 
@@ -383,16 +487,70 @@ class _HourglassTrain(torch.autograd.Function):
         return (grad_x, None, None) + tuple(grads)
 
 
-def hourglass_train(cnn_input, params, render_scale=None):
+class _HourglassTrainHalf(torch.autograd.Function):
+    """`_HourglassTrain` in half precision: the forward is ibgs_hgh_forward on an arena this node owns (its six binary16 stages are the kept activations),
+    the backward ibgs_hgh_train_backward."""
+
+    @staticmethod
+    def forward(ctx, x, dims, burned, grad_scale_log2, status, *params):
+        h, w = dims
+        dev = x.device
+        x32 = _f32(x).view(C, h, w)
+        flat = [_f32(t) for t in params]
+        arena = torch.empty(_lib.load().ibgs_hgh_required_scratch(h, w), dtype=torch.uint8, device=dev)          # owned: the backward reads it
+        residual, image_pred = _forward_call(dev, h, w, x32, flat, burned, arena, True)
+        ctx.dims, ctx.burned, ctx.x_shape, ctx.x_dtype, ctx.grad_scale_log2, ctx.status = dims, burned, x.shape, x.dtype, grad_scale_log2, status
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x32, arena, *flat)
+        if image_pred is None:
+            return residual
+        return residual, image_pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_res, g_ip=None):
+        need_x, need_params = ctx.needs_input_grad[0], any(ctx.needs_input_grad[5:])
+        if not (need_x or need_params) or (g_res is None and g_ip is None):
+            return (None,) * (5 + 18)
+        x32, arena = ctx.saved_tensors[:2]
+        flat = list(ctx.saved_tensors[2:])
+        h, w = ctx.dims
+        dev = x32.device
+        g_res = None if g_res is None else _f32(g_res.to(dev))
+        g_ip = None if g_ip is None else _f32(g_ip.to(dev))
+        grad_x, grads, _ = _backward_call_half(dev, h, w, x32, flat, 1.0 if ctx.burned is None else ctx.burned, arena, g_res, g_ip, need_x, need_params,
+                                               ctx.grad_scale_log2, ctx.status)
+        if grad_x is not None:
+            grad_x = grad_x.view(ctx.x_shape).to(ctx.x_dtype)
+        if grads is None:
+            grads = [None] * 18
+        else:
+            grads = [g if k else None for g, k in zip(grads, ctx.needs_input_grad[5:])]
+        return (grad_x, None, None, None, None) + tuple(grads)
+
+
+def hourglass_train(cnn_input, params, render_scale=None, **half):
     """`hourglass_forward` for training: differentiable in cnn_input and the eighteen parameters.  -> residual, or (residual, image_pred) with
     `render_scale=float`; both bit for bit what `hourglass_forward` returns.  The forward runs ibgs_hg_forward on an arena this node owns (the six stages are
     the kept activations; d1 and f are recomputed by the backward); the backward is `hourglass_backward` and computes only the groups autograd needs (a frozen
-    CNN: no weight gradient runs; a detached input: no enc1 input gradient).  Double backward raises.  Nothing waits for the host."""
+    CNN: no weight gradient runs; a detached input: no enc1 input gradient).  Double backward raises.  Nothing waits for the host.
+    `**half` are three keyword-only options: precision (default: what `train_precision` set on this thread, else "float32"), grad_scale_log2=None, status=None.
+    `precision="float16"` is mixed-precision training: the forward is `hourglass_forward(..., precision="float16")` bit for bit (the network is trained
+    against the roundings it is rendered with), the kept activations are its binary16 stages, and the backward is `hourglass_backward(...,
+    precision="float16")` with its `grad_scale_log2` and `status`.  The gradients are float32 and true to scale: no torch.amp.GradScaler is needed.  Without
+    the keyword every bit is what it was."""
     name = "hourglass_train"
+    _options(name, half, ("precision", "grad_scale_log2", "status"))
+    precision, grad_scale_log2, status = half.get("precision", getattr(_TRAINING, "precision", "float32")), half.get("grad_scale_log2"), half.get("status")
+    _check_precision(name, precision)
     x, h, w, tensors = _checked(name, cnn_input, params)
+    grad_scale_log2 = _check_scale(name, precision, grad_scale_log2, status)
     _on_one_device(name, x, tensors)
+    _status_on(name, status, x.device)
     if render_scale is not None:
         render_scale = float(render_scale)
+    if precision == "float16":
+        return _HourglassTrainHalf.apply(cnn_input, (h, w), render_scale, grad_scale_log2, status, *[t for _, t in tensors])
     return _HourglassTrain.apply(cnn_input, (h, w), render_scale, *[t for _, t in tensors])
 
 
@@ -403,7 +561,9 @@ def fuse_color_train(render_pkg, net, nb_visible_src_frames=3, iter_count=None, 
     the five tensors of render_pkg are detached (no gradient reaches the rasterizer; the networks' parameters still train).  -> the dictionary of
     `fuse_color`.  Nothing waits for the host unless `none_if_no_level` (which reads the level count back and returns None when it is 0).
     `enable_exposure_correction`: as in `fuse_color`, after the detaching, in the reference's order; "render" receives its gradient through the correction
-    (the affine map is a constant of the backward), "warped_image" only the front end's.  Without the keyword every bit and every key is what it was."""
+    (the affine map is a constant of the backward), "warped_image" only the front end's.  Without the keyword every bit and every key is what it was.
+    Inside `with train_precision("float16"):` the hourglass is trained in half precision (`hourglass_train`, automatic scale); the per-view front end and the exposure correction
+    stay float32, as at test time, and the forward's image_pred is `fuse_color(..., precision="float16")`'s bit for bit."""
     name = "fuse_color_train"
     render, h, w = _checked_package(name, render_pkg, net)
     if iter_count is None or burn_start is None or burn_end is None:

@@ -145,7 +145,9 @@ def fuse_color_train_scaled(render_pkg, net, residual_resolution_scale, nb_visib
     `resized_features_train`, `hourglass_train` at Hr x Wr = int(H s) x int(W s), `upsample_residual_train` (which forms image_pred = burned_in_gauss * render
     (or the corrected image) + residual at H x W).  -> the dictionary of `hourglass.fuse_color`: residual is the upsampled (3, H, W) one.
     A scale whose sizes lie outside the hourglass's range, or above the frame's own, raises ValueError before any GPU work.  A scale == 1 returns
-    `fuse_color_train(...)` itself: every bit and every key.  Nothing waits for the host unless `none_if_no_level`."""
+    `fuse_color_train(...)` itself: every bit and every key.  Nothing waits for the host unless `none_if_no_level`.
+    Inside `with hourglass.train_precision("float16"):` the hourglass is trained in half precision (`hourglass.hourglass_train`); the resized features, the
+    exposure correction and the upsampling adjoint stay float32.  Outside such a block every bit is what it was."""
     name = "fuse_color_train_scaled"
     if residual_resolution_scale == 1:
         return fuse_color_train(render_pkg, net, nb_visible_src_frames, iter_count, burn_start, burn_end, none_if_no_level, enable_exposure_correction)

@@ -23,8 +23,10 @@ and spill report per instantiation of the kernel.  A measurement needs the GPU: 
 
 measures TRAINING by the same method, grad mode on: `hourglass_train` + backward (csrc/hgtrain.hip) against the torch float32 composition + autograd
 (MIOpen) in the same process, with all nineteen gradients, with the parameter gradients only (a detached input) and with the input gradient only (a frozen
-CNN); then the whole training tail, `fuse_color_train` + backward against front end + torch CNN + backward.  Its report REPLACES the part of --out from the
-line "# --train" on and leaves the forward's report above it as it is."""
+CNN); then the whole training tail, `fuse_color_train` + backward against front end + torch CNN + backward.  Beside them, alternating in the same windows, the
+HALF-PRECISION rows (`hourglass_train(..., precision="float16")` and the two tails inside `hourglass.train_precision("float16")`; csrc/hghtrain.hip): `hourglass_train` with all gradients, parameters only and input only, `fuse_color_train`, and
+`fuse_color_train_scaled` at 0.5; their yardsticks are the float32 rows and torch autocast(float16) + autograd on the device with the loss scaled by 2^10 and
+the gradients divided by it.  Its report REPLACES the part of --out from the line "# --train" on and leaves the forward's report above it as it is."""
 import argparse
 import os
 import re
@@ -39,7 +41,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ibgs_amd import _build, coloragg, hourglass  # noqa: E402
+from ibgs_amd import _build, coloragg, hourglass, resample_train  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 FP32_FLOPS = 157.3e12
@@ -135,10 +137,19 @@ TRAIN_MARK = "# --train"
 BWD_MACS = 2 * MACS + (38 * 76 * 9 + 38 * 76)
 
 
-def train_resource_report(say):
-    src = os.path.join(_build.CSRC, "hgtrain.hip")
+def min_bytes_half_train(h, w):
+    """The minimum traffic of the half-precision backward's launches, from the shapes (bytes per pixel of each level: what every launch must read and write
+    once, binary16 stages and G_* at 80 / 48 / 32 bytes per pixel, float32 input gradients at 160 / 96 / 64): without and with the weight gradients' reads."""
+    p1, p2, p4 = h * w, (h // 2) * (w // 2), (h // 4) * (w // 4)
+    routing = 2208 * p1 + 1120 * p2 + 320 * p4          # the head, the nine input gradients, the four gathers, grad_x
+    wgrad = 816 * p1 + 656 * p2 + 256 * p4             # G and the layer's input, once per layer
+    return routing, routing + wgrad
+
+
+def train_resource_report(say, unit="hgtrain", prefix="hgb_"):
+    src = os.path.join(_build.CSRC, unit + ".hip")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([_build._hipcc()] + _build.compile_flags("hgtrain") + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hgb.o")],
+        r = subprocess.run([_build._hipcc()] + _build.compile_flags(unit) + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hgb.o")],
                            capture_output=True, text=True)
     if r.returncode != 0:
         say("hipcc's resource report could not be produced (exit %d)" % r.returncode)
@@ -150,13 +161,16 @@ def train_resource_report(say):
             continue
         if m.group(1):
             name = m.group(1)
-            k = re.search(r"(hgb_[a-z_]+)", name)
-            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EL[ib]([0-9]+)E", name)
-            cur = {"name": (k.group(1) if k else name) + ("<%s>" % ", ".join(t.groups()) if t else "")}
+            k = re.search(r"(%s[a-z0-9_]+?)(?:I|E)" % prefix, name)
+            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)(?:EL[ib]([0-9]+))?E", name)
+            cur = {"name": (k.group(1) if k else name) + ("<%s>" % ", ".join(v for v in t.groups() if v is not None) if t else "")}
             rows.append(cur)
         elif cur is not None:
             cur[m.group(2).strip()] = int(m.group(3))
-    say("hipcc's report per instantiation of hgtrain.hip (hgb_conv_kernel<channels of A, of B, Cout, taps, transposed>; hgb_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
+    if unit == "hgtrain":
+        say("hipcc's report per instantiation of hgtrain.hip (hgb_conv_kernel<channels of A, of B, Cout, taps, transposed>; hgb_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
+    else:
+        say("hipcc's report per instantiation of hghtrain.hip (hght_conv3_kernel<channels of A, of B, rows, epilogue: 0 float32, 1 masked binary16, 2 grad_x, 3 head>; hght_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
     for c in rows:
         say("  %-44s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
             % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
@@ -177,7 +191,7 @@ def main_train(args):
     net = hourglass.ColorAggregationNet().to(dev)
     cnn = net.cnn
     params = list(cnn.parameters())
-    verdict = {}
+    verdict, verdict16 = {}, {}
     for size in args.sizes.split(","):
         h, w = (int(v) for v in size.split("x"))
         g = torch.Generator().manual_seed(h)
@@ -195,32 +209,74 @@ def main_train(args):
         say()
         say("== (38, %d, %d)" % (h, w))
 
-        def step(forward, x_grad, p_grad):
+        def step(forward, x_grad, p_grad, scale=None):
             def run():
                 x = x0.detach().requires_grad_(x_grad)
                 for q in params:
                     q.requires_grad_(p_grad)
                     q.grad = None
                 _, ip = forward(x)
-                (ip * up).sum().backward()
-                return x.grad, [q.grad for q in params]
+                if scale is None:
+                    (ip * up).sum().backward()
+                    return x.grad, [q.grad for q in params]
+                ((ip.float() * up).sum() * scale).backward()          # torch autocast: the loss scaled, the gradients divided in float32
+                return (None if x.grad is None else x.grad / scale), [None if q.grad is None else q.grad.div_(scale) for q in params]
             return run
         hip = lambda x: hourglass.hourglass_train(x, cnn, render_scale=1.0)
+        half = lambda x: hourglass.hourglass_train(x, cnn, render_scale=1.0, precision="float16")
         tor = lambda x: composed(x, cnn, 1.0)
+
+        def auto(x):
+            with torch.autocast("cuda", dtype=torch.float16):
+                return composed(x, cnn, 1.0)
+        LOSS_SCALE = 2.0 ** 10
         gx_h, gp_h = step(hip, True, True)()
         gx_t, gp_t = step(tor, True, True)()
         say("same gradients: max |d grad_x| %.2e of max %.2e; worst parameter gradient %.2e of its max"
             % (float((gx_h - gx_t).abs().max()), float(gx_t.abs().max()), max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(gp_h, gp_t))))
-        del gx_h, gp_h, gx_t, gp_t
-        r = compare({"hip all": step(hip, True, True), "torch all": step(tor, True, True), "hip params only": step(hip, False, True), "torch params only": step(tor, False, True),
-                     "hip input only": step(hip, True, False), "torch input only": step(tor, True, False)}, args.iters, args.repeats, args.warmup)
+        gx_f, gp_f = step(half, True, True)()
+        gx_a, gp_a = step(auto, True, True, LOSS_SCALE)()
+        rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
+        names = [n for n, _ in cnn.named_parameters()]
+        worst = max(zip(names, gp_f, gp_t), key=lambda t: rel(t[1], t[2]))[0]
+        say("hip float16 against the torch float32 gradients: grad_x %.2e of its max, worst parameter gradient %.2e of its max (%s) (torch autocast with the loss scaled by 2^10: %.2e, %.2e)"
+            % (rel(gx_f, gx_t), max(rel(a, b) for a, b in zip(gp_f, gp_t)), worst, rel(gx_a, gx_t), max(rel(a, b) for a, b in zip(gp_a, gp_t))))
+        # the same ReLU and pool decisions in the six stages: the float32 unit on the half forward's stages.  What is left is the roundings and the d1 / f decisions;
+        # a weight-gradient workgroup of the half unit walks a strip of (tiles of 8 x 16) / 128 tiles here, two in the test frames
+        with torch.no_grad():
+            _, st16 = hourglass.hourglass_forward(x0, cnn, return_stages=True, precision="float16")
+            st16 = {k: v.clone() for k, v in st16.items()}
+        hx, hp = hourglass.hourglass_backward(x0, cnn, st16, None, up, precision="float16")
+        fx, fp = hourglass.hourglass_backward(x0, cnn, {k: v.float().contiguous() for k, v in st16.items()}, None, up)
+        per = {k: rel(hp[k], fp[k]) for k in hp}
+        say("hip float16 against the float32 unit on the half forward's stages (strips of %d tiles): grad_x %.2e of its max; parameter gradients %.2e (%s) .. %.2e (%s) of their maxima"
+            % (-(-(-(-h // 8) * -(-w // 16)) // 128), rel(hx, fx), min(per.values()), min(per, key=per.get), max(per.values()), max(per, key=per.get)))
+        del st16, hx, hp, fx, fp
+        del gx_h, gp_h, gx_t, gp_t, gx_f, gp_f, gx_a, gp_a
+        r = compare({"hip all": step(hip, True, True), "hip float16 all": step(half, True, True), "torch all": step(tor, True, True), "torch autocast all": step(auto, True, True, LOSS_SCALE),
+                     "hip params only": step(hip, False, True), "hip float16 params only": step(half, False, True), "torch params only": step(tor, False, True),
+                     "hip input only": step(hip, True, False), "hip float16 input only": step(half, True, False), "torch input only": step(tor, True, False)},
+                    args.iters, args.repeats, args.warmup)
         for k in r:
-            say("%-20s %8.3f ms [%7.3f .. %7.3f]" % (k, r[k][0], r[k][1], r[k][2]))
+            say("%-26s %8.3f ms [%7.3f .. %7.3f]" % (k, r[k][0], r[k][1], r[k][2]))
+        for what in ("all", "params only", "input only"):
+            f16, f32 = r["hip float16 " + what], r["hip " + what]
+            faster = f16[0] < f32[0]
+            verdict16["%s %s" % (size, what)] = faster
+            say("forward + backward, %-11s hip float32 / hip float16 %5.2f x (float32 range [%7.3f .. %7.3f])   hip float16 faster: %s%s"
+                % (what + ":", f32[0] / f16[0], f32[1], f32[2], faster, "   torch autocast / hip float16 %5.2f x" % (r["torch autocast all"][0] / f16[0]) if what == "all" else ""))
         for what in ("all", "params only", "input only"):
             faster = r["hip " + what][0] < r["torch " + what][0]
             verdict["%s %s" % (size, what)] = faster
             say("forward + backward, %-11s torch float32 / hip %5.2f x   hip faster: %s" % (what + ":", r["torch " + what][0] / r["hip " + what][0], faster))
         lib = hourglass._lib.load()
+        flop16_ms = 2 * (MACS + BWD_MACS) * h * w / FP16_FLOPS * 1e3
+        route_b, all_b = min_bytes_half_train(h, w)
+        byte16_ms = (min_bytes_half(h, w) + all_b) / HBM_BYTES_PER_S * 1e3
+        say("floors of hip float16, forward + backward with all gradients: arithmetic (at 2.5 PFLOP/s) %.3f ms = %.0f %% of its time reached; bytes (%.2f GB at 8 TB/s: the forward's "
+            "%.2f, the backward's %.2f of which %.2f without the weight gradients' reads) %.3f ms = %.0f %%; kept activations (the half forward's arena) %.2f GB, the backward's arena %.2f GB"
+            % (flop16_ms, 100.0 * flop16_ms / r["hip float16 all"][0], (min_bytes_half(h, w) + all_b) / 1e9, min_bytes_half(h, w) / 1e9, all_b / 1e9, route_b / 1e9, byte16_ms,
+               100.0 * byte16_ms / r["hip float16 all"][0], lib.ibgs_hgh_required_scratch(h, w) / 1e9, lib.ibgs_hgh_train_required_scratch(h, w) / 1e9))
         floor_ms = 2 * (MACS + BWD_MACS) * h * w / FP32_FLOPS * 1e3
         say("arithmetic floor, forward + backward (%d fma per pixel at 157.3 TFLOP/s) %.3f ms = %.0f %% of the hip time reached; kept activations (the forward's arena) %.2f GB, "
             "the backward's arena %.2f GB" % (round(MACS + BWD_MACS), floor_ms, 100.0 * floor_ms / r["hip all"][0], lib.ibgs_hg_required_scratch(h, w) / 1e9,
@@ -234,22 +290,37 @@ def main_train(args):
                 render.grad = warped.grad = None
                 if cnn_forward is None:
                     ip = hourglass.fuse_color_train(pkg, net, 3)["image_pred"]
+                elif cnn_forward == "float16":
+                    with hourglass.train_precision("float16"):
+                        ip = hourglass.fuse_color_train(pkg, net, 3)["image_pred"]
+                elif cnn_forward in ("scaled", "scaled float16"):
+                    with hourglass.train_precision("float16" if cnn_forward == "scaled float16" else "float32"):
+                        ip = resample_train.fuse_color_train_scaled(pkg, net, 0.5, 3)["image_pred"]
                 else:
                     xi, _ = coloragg.fuse_color_inputs(pkg, net.front_end, 3)
                     ip = cnn_forward(xi)[1]
                 (ip * up).sum().backward()
             return run
-        r = compare({"fuse_color_train": tail(None), "front end + torch CNN": tail(tor)}, args.iters, args.repeats, 3)
+        r = compare({"fuse_color_train": tail(None), "fuse_color_train float16": tail("float16"), "front end + torch CNN": tail(tor), "scaled 0.5": tail("scaled"),
+                     "scaled 0.5 float16": tail("scaled float16")}, args.iters, args.repeats, 3)
         say("the training tail from the rasterizer's planes, forward + backward: fuse_color_train %8.3f ms [%7.3f .. %7.3f]   front end + torch float32 CNN %8.3f ms [%7.3f .. %7.3f]   ratio %5.2f x"
             % (r["fuse_color_train"] + r["front end + torch CNN"] + (r["front end + torch CNN"][0] / r["fuse_color_train"][0],)))
+        say("the same tail inside train_precision(\"float16\") %8.3f ms [%7.3f .. %7.3f]   fuse_color_train / float16 %5.2f x"
+            % (r["fuse_color_train float16"] + (r["fuse_color_train"][0] / r["fuse_color_train float16"][0],)))
+        say("fuse_color_train_scaled at 0.5: float32 %8.3f ms [%7.3f .. %7.3f]   inside train_precision(\"float16\") %8.3f ms [%7.3f .. %7.3f]   float32 / float16 %5.2f x"
+            % (r["scaled 0.5"] + r["scaled 0.5 float16"] + (r["scaled 0.5"][0] / r["scaled 0.5 float16"][0],)))
+        verdict16["%s fuse_color_train" % size] = r["fuse_color_train float16"][0] < r["fuse_color_train"][0]
+        verdict16["%s scaled 0.5" % size] = r["scaled 0.5 float16"][0] < r["scaled 0.5"][0]
         del x0, pkg, render, warped, feat, ray, mask, up
         for q in net.parameters():
             q.grad = None
         torch.cuda.empty_cache()
     say()
     say("hourglass_train + backward faster than the torch float32 composition + autograd: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
+    say("precision=\"float16\" faster than the float32 unit: %s" % ", ".join("%s %s" % kv for kv in verdict16.items()))
     say()
     train_resource_report(say)
+    train_resource_report(say, "hghtrain", "hght_")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     kept = []
     if os.path.exists(args.out):
