@@ -10,7 +10,8 @@ ssim.hip takes no such flag: its contract is a tolerance, its filter passes are 
 themselves (#pragma clang fp contract(off)); geoloss.hip, which runs the same passes and forms (csrc/shared/ssim_window.h), is built the same way, and so is coloragg.hip
 (the colour aggregation front end: a tolerance contract, its products are matrix-core fma chains), and hourglass.hip (the CNN behind it, forward only: the same), and hgtrain.hip (that CNN's backward: the same),
 and hghalf.hip (that CNN's forward in half precision: the same; csrc/shared/hg_net.h states the network -- its layers, its stage arena, its host-side checks -- once for
-these units), and hghtrain.hip (that CNN's backward in half precision: the same), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
+these units), and hghtrain.hip (that CNN's backward in half precision: the same; csrc/shared/conv_tile_f16.h states the f16 matrix-core convolution, the octet read and
+the recomputed head once for these two), and lpips.hip (LPIPS on VGG16 for the image evaluation: a tolerance contract as well, its convolutions
 are the same matrix-core fma chains -- csrc/shared/conv_tile.h states their 16 x 16 tile and the rule by which a layer reads its source once for it and the three
 hourglass units; the z-score's two operations say themselves that they are not contracted), and exposure.hip (the exposure correction of
 the colour network: a tolerance contract too; its moments add exact f64 products of f32 values, so contraction cannot change them, and its application is an fma chain), and resample.hip
@@ -31,7 +32,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libibgs_rast.so")
-SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "export", "resample", "rsztrain", "lpips", "hgtrain", "hghalf", "hourglass"]
+SOURCES = ["api", "preprocess", "scan_sort", "binning", "render_fwd", "render_bwd", "preprocess_bwd", "knn", "adam", "compact", "deterministic", "loss", "depth_normal", "activate", "tsdf", "mesh", "mesh_eval", "registration", "dtu", "ssim", "geoloss", "coloragg", "exposure", "export", "resample", "rsztrain", "lpips", "hgtrain", "hghalf", "hghtrain", "hourglass"]
 EXTRA = {
     "preprocess": ["-ffp-contract=off"],           # bit-identical to the oracle (see preprocess.hip)
     "scan_sort": ["-ffp-contract=off"],            # runs the SH colours of sh_color.h too (the sort itself has no float arithmetic)
@@ -54,7 +55,7 @@ def compile_flags(name):
 # headers that not every unit includes: hashed into the profile stamps (tu_shas) of the units they are listed under and of no other, rebuild triggers like the
 # others.  Those under csrc/shared/ have two to four users each; they sit in a subdirectory because every csrc/*.h enters every unit's stamp.  A unit's list
 # is every header it includes, directly or through another, outside csrc/*.h and include/ibgs_rast.h.
-SSIM_WINDOW_H, PV_MLP_H, PV_MLP_BWD_H, RSZ_TAPS_H, HG_NET_H, CONV_TILE_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "hg_net.h", "conv_tile.h"))
+SSIM_WINDOW_H, PV_MLP_H, PV_MLP_BWD_H, RSZ_TAPS_H, HG_NET_H, CONV_TILE_H, CONV_TILE_F16_H = (os.path.join(CSRC, "shared", f) for f in ("ssim_window.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "hg_net.h", "conv_tile.h", "conv_tile_f16.h"))
 UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "mesh": [os.path.join(HERE, "..", "include", "ibgs_mesh.h")],
                 "mesh_eval": [os.path.join(HERE, "..", "include", "ibgs_mesh_eval.h")],
                 "registration": [os.path.join(HERE, "..", "include", "ibgs_registration.h")],
@@ -64,7 +65,9 @@ UNIT_HEADERS = {"tsdf": [os.path.join(HERE, "..", "include", "ibgs_tsdf.h")], "m
                 "coloragg": [os.path.join(HERE, "..", "include", "ibgs_color_agg.h"), PV_MLP_H, PV_MLP_BWD_H],
                 "hourglass": [os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
                 "hgtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_train.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
-                "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H],
+                "hghalf": [os.path.join(HERE, "..", "include", "ibgs_hg_half.h"), os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H, CONV_TILE_F16_H],
+                "hghtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_half_train.h"), os.path.join(HERE, "..", "include", "ibgs_hg_half.h"),
+                             os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H, CONV_TILE_F16_H],
                 "lpips": [os.path.join(HERE, "..", "include", "ibgs_lpips.h"), CONV_TILE_H],
                 "exposure": [os.path.join(HERE, "..", "include", "ibgs_exposure.h")],
                 "export": [os.path.join(HERE, "..", "include", "ibgs_export.h")],
@@ -83,7 +86,7 @@ def _hipcc():
 def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "..", "include", "ibgs_rast.h"))
-    deps += [h for name in SOURCES for h in UNIT_HEADERS.get(name, [])] + [h for hs in SIDE_UNITS.values() for h in hs]
+    deps += [h for name in SOURCES for h in UNIT_HEADERS.get(name, [])]
     return max(os.path.getmtime(d) for d in deps)
 
 
@@ -131,17 +134,6 @@ def tu_of(kernel_name):
 # none (the frame export runs after the step, outside everything bench.py measures; its numbers are tools/bench_export.py's own text, profiles/export.txt).
 # tu_of() still names the unit for such a kernel, and bench.py's tu_shas().get(unit) then finds no stamp: nothing stale can be quoted for it.
 UNSTAMPED = ("export",)
-# units outside the stamped set altogether: SOURCES, UNIT_HEADERS and tu_shas() are the tables the committed profile summaries were stamped against, and a unit
-# that no summary and no bench.py figure refers to does not enter them.  Such a unit is compiled with the same flags, rebuilt on an edit of any header it lists
-# (every header it includes outside csrc/*.h and include/ibgs_rast.h) and linked into the same library; KERNEL_TU attributes its kernels.  hghtrain.hip is the
-# half-precision backward of the hourglass (tools/bench_hourglass.py --train measures it; its text is profiles/hourglass.txt).
-SIDE_UNITS = {"hghtrain": [os.path.join(HERE, "..", "include", "ibgs_hg_half_train.h"), os.path.join(HERE, "..", "include", "ibgs_hg_half.h"),
-                           os.path.join(HERE, "..", "include", "ibgs_hourglass.h"), HG_NET_H, CONV_TILE_H]}
-
-
-def _headers_of(name):
-    """The headers a translation unit is rebuilt for, beyond csrc/*.h and include/ibgs_rast.h"""
-    return SIDE_UNITS[name] if name in SIDE_UNITS else UNIT_HEADERS.get(name, [])
 
 
 def tu_shas():
@@ -169,7 +161,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     newest = _newest_dep()
-    objs = [os.path.join(OBJ, n + ".o") for n in SOURCES + list(SIDE_UNITS)]
+    objs = [os.path.join(OBJ, n + ".o") for n in SOURCES]
     return any((not os.path.exists(o)) or os.path.getmtime(o) < newest for o in objs) or os.path.getmtime(LIB) < newest
 
 
@@ -182,7 +174,7 @@ def build(force=False, verbose=False):
     def compile_one(name):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(OBJ, name + ".o")
-        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in _headers_of(name)])
+        newest = max([os.path.getmtime(src), hdr_time] + [os.path.getmtime(h) for h in UNIT_HEADERS.get(name, [])])
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj
         cmd = [hipcc] + compile_flags(name) + ["-c", src, "-o", obj]
@@ -192,7 +184,7 @@ def build(force=False, verbose=False):
         return obj
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(compile_one, SOURCES + list(SIDE_UNITS)))
+        objs = list(ex.map(compile_one, SOURCES))
     if force or (not os.path.exists(LIB)) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:

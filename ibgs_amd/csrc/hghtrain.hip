@@ -7,14 +7,14 @@
 // partial per workgroup, summed by a last pass in the order of the workgroups; the only atomics are INTEGER ones (the maximum of the upstream's magnitude as
 // bits, the count of non-finite values, the reduction's ticket), whose results do not depend on their order.
 //
-// THE PRODUCTS are v_mfma_f32_16x16x32_f16 with the lane map of hghalf.hip: lane l = (col = l & 15, kq = l >> 4) holds A[row col][k = 8 kq + j] and
-// B[k = 8 kq + j][column col], j = 0 .. 7; register r of a result tile is row 4 kq + r of column col.  Every tensor between two launches is PIXEL-MAJOR with
+// THE PRODUCTS are v_mfma_f32_16x16x32_f16 with the lane map of csrc/shared/conv_tile_f16.h, which states the tile, the chunk loop, the octet read and the
+// forward's fuse_input once for this unit and hghalf.hip.  Every tensor between two launches is PIXEL-MAJOR with
 // the channels innermost and padded with zeros to a multiple of 8, binary16 (the G_*, d1, f, gS, h(x)) or float32 (an input gradient before its gather).
-//   hght_conv3_kernel<CA, CB, COUT, EPI>  the 3 x 3 implicit GEMM of hgh_conv3_kernel on the 16 x 16 tile (M = COUT rows of the packed weight, N = 16 pixels
-//     of a row, K = (octet of [a | b], tap)), the input read plain.  With the weight packed transposed and flipped it is a layer's input gradient from its G;
+//   hght_conv3_kernel<CA, CB, COUT, EPI>  cth_conv3, the 3 x 3 implicit GEMM hgh_conv3_kernel runs too, on the 16 x 16 tile (M = COUT rows of the packed weight,
+//     N = 16 pixels of a row, K = (octet of [a | b], tap)), the input read plain.  With the weight packed transposed and flipped it is a layer's input gradient from its G;
 //     its epilogue stores the float32 accumulation (EPI_F32), masks by a stage, rounds and stores binary16 (EPI_MASK), or adds 2^-k times it to grad_x's planes
-//     (EPI_GRADX).  EPI_HEAD is the last launch of the forward again -- dec1, fuse_input on [d1, h(x)], the same k order and bits -- followed by the head of
-//     the backward in registers: gS, G_f, G_d1 and the head's share of grad_x.
+//     (EPI_GRADX).  EPI_HEAD is the last launch of the forward again -- dec1 from its rounded bias, then cth_fuse_input on [d1, h(x)]: the definition the forward
+//     runs, so the same k order and bits -- followed by the head of the backward in registers: gS, G_f, G_d1 and the head's share of grad_x.
 //   hght_wgrad_kernel<CA, CB, COUT, MODE, TAPS>  a GEMM whose K is the pixels, 32 of them per instruction: M = output channels (rows: G), N = 16 input channels
 //     of a slice for each tap, and one column of ones (the bias gradient).  A workgroup owns a slice and a strip of 8 x 16 tiles; G and the input window are
 //     staged CHANNEL-major in LDS (the window in three copies shifted by one column, so that every operand is one aligned 16-byte read); each wave takes two
@@ -26,23 +26,13 @@
 #include "common.h"
 #include "shared/hg_net.h"
 #include "shared/conv_tile.h"
+#include "shared/conv_tile_f16.h"
 #include "../../include/ibgs_hourglass.h"
 #include "../../include/ibgs_hg_half.h"
 #include "../../include/ibgs_hg_half_train.h"
 
 namespace ibgs {
 
-typedef float hght_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 hght_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hght_h4 __attribute__((ext_vector_type(4)));
-
-constexpr int HGHT_TILE = 16;                        // side of a convolution workgroup's output tile
-constexpr int HGHT_THREADS = 256;
-constexpr int HGHT_ROWS = HGHT_TILE / (HGHT_THREADS / 64);
-constexpr int HGHT_WIN = HGHT_TILE + 2;
-constexpr int HGHT_NPIX = HGHT_WIN * HGHT_WIN;
-constexpr int HGHT_PSTRIDE = 5;                      // 16-byte units per staged pixel: four octets and one of padding (odd)
-constexpr int HGHT_XO = (HG_C + 7) / 8;              // octets of x
 constexpr int HGHT_WT_H = 8;                         // hght_wgrad_kernel: rows of a tile of its strip
 constexpr int HGHT_WT_W = 16;                        // ... and columns
 constexpr int HGHT_MAX_STRIPS = 128;                 // strips (partials) per weight gradient, at most
@@ -51,17 +41,11 @@ constexpr int HGHT_SLICE = 16;                       // input channels (two octe
 constexpr int HGHT_GROW = HGHT_WT_H * HGHT_WT_W + 8; // binary16 per staged channel of G (a multiple of 8: operands stay 16-byte aligned)
 constexpr int HGHT_E_TARGET = IBGS_HGHT_E_TARGET;
 constexpr int HGHT_SCALE_BLOCKS = 256;
-static_assert(HGHT_ROWS == 4 && HGHT_PSTRIDE % 2 == 1 && HGHT_WT_H * HGHT_WT_W == 32 * (HGHT_THREADS / 64), "the lane maps");
-
-constexpr int hght_octets(int c) { return (c + 7) / 8; }
-constexpr int hght_frags3(int octets, int rows) { return ((octets + 3) / 4) * 9 * ((rows + 15) / 16) * 64; }
-constexpr int HGHT_FUSE_STEPS = 2 + (HGHT_XO + 3) / 4;          // k-steps of fuse_input (d1: 2, x: 2)
+static_assert(HGHT_WT_H * HGHT_WT_W == 32 * (CT_THREADS / 64), "the lane maps");
 
 // the control words at the head of the arena
 struct HghtCtrl { unsigned m_bits; int k; int nonfinite; unsigned ticket; };
 
-__device__ __forceinline__ hght_f32x4 hght_mfma(hght_h8 a, hght_h8 b, hght_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float hght_round(float v) { return (float)(_Float16)v; }
 __device__ __forceinline__ bool hght_bad(_Float16 v) { return !(__builtin_fabsf((float)v) <= 65504.0f); }          // inf or NaN
 // floor(log2 m) of a positive finite float32 given as bits (subnormals included)
 __device__ __forceinline__ int hght_floor_log2(unsigned bits)
@@ -72,16 +56,16 @@ __device__ __forceinline__ int hght_floor_log2(unsigned bits)
 
 // ---- the scale ---------------------------------------------------------------------------------------------------------------------------------------------
 // AUTO: the maximum of |g_res + g_ip| as bits (non-negative floats order as their bits; a NaN's bits lie above infinity's); the last workgroup to finish writes k.
-__global__ void __launch_bounds__(HGHT_THREADS) hght_scale_kernel(const float* __restrict__ g_res, const float* __restrict__ g_ip, size_t n, int fixed, int fixed_k,
-                                                                  HghtCtrl* ctrl)
+__global__ void __launch_bounds__(CT_THREADS) hght_scale_kernel(const float* __restrict__ g_res, const float* __restrict__ g_ip, size_t n, int fixed, int fixed_k,
+                                                                HghtCtrl* ctrl)
 {
     if (fixed) {
         if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->k = fixed_k;
         return;
     }
-    __shared__ unsigned s_max[HGHT_THREADS / 64];
+    __shared__ unsigned s_max[CT_THREADS / 64];
     unsigned best = 0;
-    for (size_t i = (size_t)blockIdx.x * HGHT_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * HGHT_THREADS) {
+    for (size_t i = (size_t)blockIdx.x * CT_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * CT_THREADS) {
         const float g = (g_res ? g_res[i] : 0.0f) + (g_ip ? g_ip[i] : 0.0f);
         best = max(best, __float_as_uint(g) & 0x7fffffffu);
     }
@@ -118,13 +102,13 @@ struct HghtPackItem {
 };
 constexpr int HGHT_ITEMS = 14;
 struct HghtPackArgs {
-    hght_h8* packed; int frags;
+    cth_h8* packed; int frags;
     HghtPackItem item[HGHT_ITEMS];
 };
 
-__global__ void __launch_bounds__(HGHT_THREADS) hght_pack_kernel(const HghtPackArgs a)
+__global__ void __launch_bounds__(CT_THREADS) hght_pack_kernel(const HghtPackArgs a)
 {
-    const int i = (int)blockIdx.x * HGHT_THREADS + (int)threadIdx.x;
+    const int i = (int)blockIdx.x * CT_THREADS + (int)threadIdx.x;
     if (i >= a.frags) return;
     HghtPackItem L = a.item[0];
 #pragma unroll
@@ -132,15 +116,12 @@ __global__ void __launch_bounds__(HGHT_THREADS) hght_pack_kernel(const HghtPackA
         if (i >= a.item[n].first) L = a.item[n];          // (selects: the table is never indexed by a register)
     const int local = i - L.first, lane = local & 63, rest = local >> 6, kq = lane >> 4;
     const int mtn = (L.rows + 15) / 16;
-    hght_h8 v;
+    cth_h8 v;
     if (L.kind == HGHT_P3_FWD || L.kind == HGHT_P3_T) {
-        const int noa = hght_octets(L.ca), nob = hght_octets(L.cb);
         const int mt = rest % mtn, t = (rest / mtn) % 9, c = rest / (mtn * 9), m = mt * 16 + (lane & 15), o = 4 * c + kq;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            int idx = -1;
-            if (o < noa) { if (8 * o + j < L.ca) idx = 8 * o + j; }
-            else if (o < noa + nob) { if (8 * (o - noa) + j < L.cb) idx = L.ca + 8 * (o - noa) + j; }
+            const int idx = cth_frag3_channel(o, j, L.ca, L.cb);
             float f = 0.0f;
             if (m < L.rows && idx >= 0)
                 f = L.kind == HGHT_P3_FWD ? L.w[((size_t)m * (L.ca + L.cb) + idx) * 9 + t] : L.w[((size_t)idx * L.wcin + L.m0 + m) * 9 + (8 - t)];
@@ -150,12 +131,10 @@ __global__ void __launch_bounds__(HGHT_THREADS) hght_pack_kernel(const HghtPackA
         const int mt = rest % mtn, s = rest / mtn, m = mt * 16 + (lane & 15);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int acc_ch = (2 * s + (j >> 2)) * 16 + 4 * kq + (j & 3);          // the order an accumulator tile gives
+            const int acc_ch = cth_acc_channel(s, kq, j);
             float f = 0.0f;
             if (L.kind == HGHT_P1_FWD) {
-                int idx = -1;
-                if (s < 2) { if (acc_ch < L.ca) idx = acc_ch; }
-                else { const int ch = 8 * (4 * (s - 2) + kq) + j; if (ch < L.cb) idx = L.ca + ch; }
+                const int idx = cth_frag1_channel(s, kq, j, L.ca, L.cb);
                 if (m < L.rows && idx >= 0) f = L.w[(size_t)m * (L.ca + L.cb) + idx];
             } else if (L.kind == HGHT_P1_T_ACC) {
                 if (m < L.rows && acc_ch < L.ca) f = L.w[(size_t)acc_ch * L.wcin + L.m0 + m];
@@ -173,135 +152,47 @@ __global__ void __launch_bounds__(HGHT_THREADS) hght_pack_kernel(const HghtPackA
 enum { HGHT_EPI_F32, HGHT_EPI_MASK, HGHT_EPI_GRADX, HGHT_EPI_HEAD };
 struct HghtConv {
     const _Float16* a; const _Float16* b;          // the two inputs ([a | b] along the channels), pixel-major, at h x w
-    const hght_h8* wfrag;
+    const cth_h8* wfrag;
     int h, w;
     HghtCtrl* ctrl;
     float* out32;                                  // EPI_F32: h x w pixels of CPOUT float32
     const _Float16* mask; _Float16* out16;         // EPI_MASK: the stage whose ReLU masks, the rounded result (both CPOUT per pixel)
     float* grad_x;                                 // EPI_GRADX and EPI_HEAD: 38 planes (EPI_HEAD: may be null)
     // EPI_HEAD
-    const float* bias; const _Float16* xh; const hght_h8* fuse_frag; const float* fuse_b;
-    const hght_h8* finalT_frag; const hght_h8* fuseT_lo; const hght_h8* fuseT_hi;
+    const float* bias; const _Float16* xh; const cth_h8* fuse_frag; const float* fuse_b;
+    const cth_h8* finalT_frag; const cth_h8* fuseT_lo; const cth_h8* fuseT_hi;
     const float* g_res; const float* g_ip; float burned;
     _Float16 *d1, *f, *Gf, *Gd1, *gs;
 };
 
-// M tiles 2 s and 2 s + 1 of a row of accumulator tiles (already rounded) as the B fragment of k-step s
-template <int MT>
-__device__ __forceinline__ hght_h8 hght_as_operand(const hght_f32x4 (&t)[MT][HGHT_ROWS], int nt, int s)
-{
-    hght_h8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int tile = 2 * s + (j >> 2);
-        float f = 0.0f;
-        if (tile < MT) f = t[tile][nt][j & 3];
-        v[j] = (_Float16)f;
-    }
-    return v;
-}
-
 // a row of three accumulator tiles (38 channels, padding rows exact zeros) as pixel-major binary16: 40 per pixel
-__device__ __forceinline__ void hght_store40(_Float16* out, const hght_f32x4 (&t)[3][HGHT_ROWS], int nt, size_t p, int kq, bool in)
+__device__ __forceinline__ void hght_store40(_Float16* out, const ct_f32x4 (&t)[3][CT_ROWS], int nt, size_t p, int kq, bool in)
 {
 #pragma unroll
     for (int mt = 0; mt < 3; ++mt) {
         const int c0 = mt * 16 + kq * 4;
         if (c0 < 40 && in) {
-            hght_h4 v;
+            cth_h4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (_Float16)t[mt][nt][r];
-            *reinterpret_cast<hght_h4*>(out + p * 40 + c0) = v;
+            *reinterpret_cast<cth_h4*>(out + p * 40 + c0) = v;
         }
     }
 }
 
 template <int CA, int CB, int COUT, int EPI>
-__global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hght_conv3_kernel(const HghtConv a)
+__global__ void __launch_bounds__(CT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hght_conv3_kernel(const HghtConv a)
 {
-    constexpr int NOA = hght_octets(CA), NOB = hght_octets(CB), NO = NOA + NOB, NC = (NO + 3) / 4, MT = (COUT + 15) / 16, CPOUT = 8 * hght_octets(COUT);
-    constexpr int NWF = 9 * MT * 64;
-    constexpr int NPOS = (HGHT_NPIX * 4 + HGHT_THREADS - 1) / HGHT_THREADS, NW = (NWF + HGHT_THREADS - 1) / HGHT_THREADS;
+    constexpr int MT = (COUT + 15) / 16, CPOUT = 8 * cth_octets(COUT);
     static_assert(EPI != HGHT_EPI_HEAD || (COUT == HG_C && MT == 3), "the head is dec1");
     static_assert(EPI != HGHT_EPI_GRADX || COUT == HG_C, "grad_x has 38 planes");
-    __shared__ hght_h8 s_in[HGHT_NPIX * HGHT_PSTRIDE];
-    __shared__ hght_h8 s_w[NWF];
-
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, kq = lane >> 4;
-    const int tx0 = blockIdx.x * HGHT_TILE, ty0 = blockIdx.y * HGHT_TILE;
+    const int tx0 = blockIdx.x * CT_TILE, ty0 = blockIdx.y * CT_TILE;
     const int h = a.h, w = a.w;
 
-    hght_f32x4 acc[MT][HGHT_ROWS];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        hght_f32x4 start = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (EPI == HGHT_EPI_HEAD) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) start[r] = mt * 16 + kq * 4 + r < COUT ? hght_round(a.bias[mt * 16 + kq * 4 + r]) : 0.0f;
-        }
-#pragma unroll
-        for (int nt = 0; nt < HGHT_ROWS; ++nt) acc[mt][nt] = start;
-    }
-
-    const int o4 = tid & 3;
-    int pos[NPOS];
-    bool pos_in[NPOS];
-#pragma unroll
-    for (int r = 0; r < NPOS; ++r) {
-        const int p = (tid >> 2) + r * (HGHT_THREADS / 4), pc = p < HGHT_NPIX ? p : 0;
-        const int yy = pc / HGHT_WIN, xx = pc - yy * HGHT_WIN, y = ty0 + yy - 1, x = tx0 + xx - 1;
-        pos_in[r] = p < HGHT_NPIX && y >= 0 && y < h && x >= 0 && x < w;
-        pos[r] = ct_source_offset<CT_PLAIN>(y, x, h, w, h, w);
-    }
-    hght_h8 iv[NPOS], wv[NW];
-    const hght_h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto load_chunk = [&](const int c) {
-        const int oc = 4 * c + o4, occ = oc < NO ? oc : NO - 1;
-        const bool from_a = CB == 0 || occ < NOA;
-        const _Float16* const base = from_a ? a.a + occ * 8 : a.b + (occ - NOA) * 8;
-        const size_t cp = from_a ? NOA * 8 : NOB * 8;
-#pragma unroll
-        for (int r = 0; r < NPOS; ++r) {
-            const hght_h8 v = *reinterpret_cast<const hght_h8*>(base + (size_t)pos[r] * cp);
-            iv[r] = (oc < NO && pos_in[r]) ? v : zero;
-        }
-#pragma unroll
-        for (int n = 0; n < NW; ++n) wv[n] = a.wfrag[c * NWF + min(tid + n * HGHT_THREADS, NWF - 1)];
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int r = 0; r < NPOS; ++r) {
-            const int p = (tid >> 2) + r * (HGHT_THREADS / 4);
-            if (p < HGHT_NPIX) s_in[p * HGHT_PSTRIDE + o4] = iv[r];
-        }
-#pragma unroll
-        for (int n = 0; n < NW; ++n)
-            if (tid + n * HGHT_THREADS < NWF) s_w[tid + n * HGHT_THREADS] = wv[n];
-    };
-    const int window_at = (wave * HGHT_ROWS * HGHT_WIN + col) * HGHT_PSTRIDE + kq;
-    auto run_taps = [&]() {
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            hght_h8 av[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) av[mt] = s_w[(t * MT + mt) * 64 + lane];
-#pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-                const hght_h8 bv = s_in[window_at + ((nt + t / 3) * HGHT_WIN + t % 3) * HGHT_PSTRIDE];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = hght_mfma(av[mt], bv, acc[mt][nt]);
-            }
-        }
-    };
-    load_chunk(0);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {          // (uniform over the workgroup: every thread reaches the barriers)
-        __syncthreads();
-        store_chunk();
-        __syncthreads();
-        if (c + 1 < NC) load_chunk(c + 1);
-        run_taps();
-    }
+    ct_f32x4 acc[MT][CT_ROWS] = {};
+    if constexpr (EPI == HGHT_EPI_HEAD) cth_start<COUT>(acc, a.bias, kq);          // only the head is a forward layer
+    cth_conv3<CA, CB, COUT, CT_PLAIN>(acc, a.a, a.b, a.wfrag, h, w, h, w);
 
     const int x = tx0 + col, xc = min(x, w - 1);
     const size_t plane = (size_t)h * (size_t)w;
@@ -313,21 +204,21 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
             const int c0 = mt * 16 + kq * 4;
             if (c0 < CPOUT) {          // (whole groups of four: CPOUT is a multiple of 8; rows past COUT are exact zeros)
 #pragma unroll
-                for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-                    const int y = ty0 + wave * HGHT_ROWS + nt, yc = min(y, h - 1);
+                for (int nt = 0; nt < CT_ROWS; ++nt) {
+                    const int y = ty0 + wave * CT_ROWS + nt, yc = min(y, h - 1);
                     const size_t at = ((size_t)yc * w + xc) * CPOUT + c0;
                     const bool in = y < h && x < w;
                     if constexpr (EPI == HGHT_EPI_F32) {
-                        if (in) *reinterpret_cast<hght_f32x4*>(a.out32 + at) = acc[mt][nt];
+                        if (in) *reinterpret_cast<ct_f32x4*>(a.out32 + at) = acc[mt][nt];
                     } else {
-                        const hght_h4 m = *reinterpret_cast<const hght_h4*>(a.mask + at);
-                        hght_h4 v;
+                        const cth_h4 m = *reinterpret_cast<const cth_h4*>(a.mask + at);
+                        cth_h4 v;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             v[r] = m[r] > (_Float16)0.0f ? (_Float16)acc[mt][nt][r] : (_Float16)0.0f;
                             bad += (in && hght_bad(v[r])) ? 1 : 0;
                         }
-                        if (in) *reinterpret_cast<hght_h4*>(a.out16 + at) = v;
+                        if (in) *reinterpret_cast<cth_h4*>(a.out16 + at) = v;
                     }
                 }
             }
@@ -336,8 +227,8 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-                const int y = ty0 + wave * HGHT_ROWS + nt;
+            for (int nt = 0; nt < CT_ROWS; ++nt) {
+                const int y = ty0 + wave * CT_ROWS + nt;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int ch = mt * 16 + kq * 4 + r;
@@ -348,64 +239,39 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
                 }
             }
     } else {
-        // acc is d1 before its ReLU and rounding.  d1 and f as the forward forms them; then the head of the backward.
+        // acc is d1 before its ReLU and rounding.  d1 and f as the forward forms them (cth_fuse_input is its last launch's too); then the head of the backward.
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt)
+            for (int nt = 0; nt < CT_ROWS; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[mt][nt][r] = hght_round(acc[mt][nt][r] > 0.0f ? acc[mt][nt][r] : 0.0f);
-        hght_f32x4 f[3][HGHT_ROWS];
-#pragma unroll
-        for (int mt = 0; mt < 3; ++mt) {
-            hght_f32x4 start;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) start[r] = mt * 16 + kq * 4 + r < HG_C ? hght_round(a.fuse_b[mt * 16 + kq * 4 + r]) : 0.0f;
-#pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt) f[mt][nt] = start;
-        }
-#pragma unroll
-        for (int s = 0; s < HGHT_FUSE_STEPS; ++s) {
-            hght_h8 av[3];
-#pragma unroll
-            for (int mt = 0; mt < 3; ++mt) av[mt] = a.fuse_frag[(s * 3 + mt) * 64 + lane];
-#pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-                hght_h8 bv;
-                if (s < 2) bv = hght_as_operand<3>(acc, nt, s);
-                else {
-                    const int o = 4 * (s - 2) + kq, yc = min(ty0 + wave * HGHT_ROWS + nt, h - 1);
-                    const hght_h8 v = *reinterpret_cast<const hght_h8*>(a.xh + ((size_t)yc * w + xc) * (HGHT_XO * 8) + min(o, HGHT_XO - 1) * 8);
-                    bv = o < HGHT_XO ? v : zero;
-                }
-#pragma unroll
-                for (int mt = 0; mt < 3; ++mt) f[mt][nt] = hght_mfma(av[mt], bv, f[mt][nt]);
-            }
-        }
+                for (int r = 0; r < 4; ++r) acc[mt][nt][r] = cth_round(acc[mt][nt][r] > 0.0f ? acc[mt][nt][r] : 0.0f);
+        ct_f32x4 f[3][CT_ROWS];
+        cth_fuse_input<false>(f, acc, a.fuse_frag, a.fuse_b, a.xh, h, w);
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < HGHT_ROWS; ++nt)
+            for (int nt = 0; nt < CT_ROWS; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) f[mt][nt][r] = hght_round(f[mt][nt][r] > 0.0f ? f[mt][nt][r] : 0.0f);
+                for (int r = 0; r < 4; ++r) f[mt][nt][r] = cth_round(f[mt][nt][r] > 0.0f ? f[mt][nt][r] : 0.0f);
 
-        hght_h8 fin_t[3], lo_t[2][3], hi_t[2][3];
+        cth_h8 fin_t[3], lo_t[2][3], hi_t[2][3];
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt) {
             fin_t[mt] = a.finalT_frag[mt * 64 + lane];
 #pragma unroll
             for (int s = 0; s < 2; ++s) { lo_t[s][mt] = a.fuseT_lo[(s * 3 + mt) * 64 + lane]; hi_t[s][mt] = a.fuseT_hi[(s * 3 + mt) * 64 + lane]; }
         }
-        hght_f32x4 gf[3][HGHT_ROWS];
+        ct_f32x4 gf[3][CT_ROWS];
 #pragma unroll
-        for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-            const int y = ty0 + wave * HGHT_ROWS + nt, yc = min(y, h - 1);
+        for (int nt = 0; nt < CT_ROWS; ++nt) {
+            const int y = ty0 + wave * CT_ROWS + nt, yc = min(y, h - 1);
             const bool in = y < h && x < w;
             const size_t p = (size_t)yc * w + xc;
             hght_store40(a.d1, acc, nt, p, kq, in);
             hght_store40(a.f, f, nt, p, kq, in);
             // gS: the three channels of the scaled upstream, rounded, as rows k = 0 .. 2 of the B operand (lanes kq == 0)
-            hght_h8 gv = zero;
+            cth_h8 gv = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float g = (a.g_res ? a.g_res[(size_t)c * plane + p] : 0.0f) + (a.g_ip ? a.g_ip[(size_t)c * plane + p] : 0.0f);
@@ -413,11 +279,11 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
                 gv[c] = (kq == 0 && in) ? s : (_Float16)0.0f;
                 bad += (kq == 0 && in && hght_bad(s)) ? 1 : 0;
             }
-            if (kq == 0 && in) *reinterpret_cast<hght_h8*>(a.gs + p * 8) = gv;
-            const hght_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (kq == 0 && in) *reinterpret_cast<cth_h8*>(a.gs + p * 8) = gv;
+            const ct_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int mt = 0; mt < 3; ++mt) {
-                gf[mt][nt] = hght_mfma(fin_t[mt], gv, z4);
+                gf[mt][nt] = cth_mfma(fin_t[mt], gv, z4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const _Float16 v = f[mt][nt][r] > 0.0f ? (_Float16)gf[mt][nt][r] : (_Float16)0.0f;
@@ -429,15 +295,15 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
         }
         // g_cat = fuse_input^T G_f: rows 0 .. 37 masked by d1 (G_d1), rows 38 .. 75 the head's share of grad_x
 #pragma unroll
-        for (int nt = 0; nt < HGHT_ROWS; ++nt) {
-            const int y = ty0 + wave * HGHT_ROWS + nt, yc = min(y, h - 1);
+        for (int nt = 0; nt < CT_ROWS; ++nt) {
+            const int y = ty0 + wave * CT_ROWS + nt, yc = min(y, h - 1);
             const bool in = y < h && x < w;
             const size_t p = (size_t)yc * w + xc;
-            const hght_h8 b0 = hght_as_operand<3>(gf, nt, 0), b1 = hght_as_operand<3>(gf, nt, 1);
-            const hght_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+            const cth_h8 b0 = cth_as_operand<3, false>(gf, nt, 0), b1 = cth_as_operand<3, false>(gf, nt, 1);
+            const ct_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int mt = 0; mt < 3; ++mt) {
-                hght_f32x4 lo = hght_mfma(lo_t[1][mt], b1, hght_mfma(lo_t[0][mt], b0, z4));
+                ct_f32x4 lo = cth_mfma(lo_t[1][mt], b1, cth_mfma(lo_t[0][mt], b0, z4));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const _Float16 v = acc[mt][nt][r] > 0.0f ? (_Float16)lo[r] : (_Float16)0.0f;
@@ -449,7 +315,7 @@ __global__ void __launch_bounds__(HGHT_THREADS, EPI == HGHT_EPI_HEAD ? 1 : 2) hg
             if (a.grad_x) {
 #pragma unroll
                 for (int mt = 0; mt < 3; ++mt) {
-                    const hght_f32x4 hi = hght_mfma(hi_t[1][mt], b1, hght_mfma(hi_t[0][mt], b0, z4));
+                    const ct_f32x4 hi = cth_mfma(hi_t[1][mt], b1, cth_mfma(hi_t[0][mt], b0, z4));
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int ch = mt * 16 + kq * 4 + r;
@@ -476,9 +342,9 @@ struct HghtWgrad {
 };
 
 template <int CA, int CB, int COUT, int MODE, int TAPS>
-__global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtWgrad a)
+__global__ void __launch_bounds__(CT_THREADS, 2) hght_wgrad_kernel(const HghtWgrad a)
 {
-    constexpr int NOA = hght_octets(CA), NOB = hght_octets(CB), NO = NOA + NOB, NOG = hght_octets(COUT), MT = (COUT + 15) / 16, COUTP = MT * 16;
+    constexpr int NOA = cth_octets(CA), NOB = cth_octets(CB), NO = NOA + NOB, NOG = cth_octets(COUT), MT = (COUT + 15) / 16, COUTP = MT * 16;
     constexpr int PAD = TAPS == 9 ? 1 : 0, COPIES = TAPS == 9 ? 3 : 1, WINH = HGHT_WT_H + 2 * PAD, WINW = HGHT_WT_W + 2 * PAD;
     constexpr int ICH = WINH * HGHT_WT_W + 8;          // binary16 per staged channel of one copy (a multiple of 8; 84 or 68 dwords: the sixteen channels of a read fall into disjoint banks)
     constexpr int NTT = TAPS + 1, NCOLS = NTT * 16;
@@ -493,16 +359,15 @@ __global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtW
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, kq = lane >> 4;
     const int slice = blockIdx.x;
     const int h = a.h, w = a.w;
-    const hght_h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
 
-    for (int i = tid; i < (COUTP - 8 * NOG) * HGHT_GROW; i += HGHT_THREADS) s_g[8 * NOG * HGHT_GROW + i] = (_Float16)0.0f;          // the rows past the last octet, once
+    for (int i = tid; i < (COUTP - 8 * NOG) * HGHT_GROW; i += CT_THREADS) s_g[8 * NOG * HGHT_GROW + i] = (_Float16)0.0f;          // the rows past the last octet, once
 
-    hght_f32x4 acc[MT][NTT];
+    ct_f32x4 acc[MT][NTT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int t = 0; t < NTT; ++t) acc[mt][t] = hght_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    hght_h8 ones;
+        for (int t = 0; t < NTT; ++t) acc[mt][t] = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    cth_h8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = col == 0 ? (_Float16)1.0f : (_Float16)0.0f;
 
@@ -511,32 +376,20 @@ __global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtW
     for (int tile = first; tile < last; ++tile) {          // (uniform over the workgroup)
         const int tyi = tile / a.tiles_x, ty0 = tyi * HGHT_WT_H, tx0 = (tile - tyi * a.tiles_x) * HGHT_WT_W;
         __syncthreads();          // the tile before has been read
-        for (int i = tid; i < HGHT_WT_H * HGHT_WT_W * NOG; i += HGHT_THREADS) {
+        for (int i = tid; i < HGHT_WT_H * HGHT_WT_W * NOG; i += CT_THREADS) {
             const int p = i / NOG, o = i - p * NOG, yy = p / HGHT_WT_W, xx = p - yy * HGHT_WT_W, y = ty0 + yy, x = tx0 + xx;
-            hght_h8 v = *reinterpret_cast<const hght_h8*>(a.g + ((size_t)min(y, h - 1) * w + min(x, w - 1)) * (8 * NOG) + 8 * o);
-            v = (y < h && x < w) ? v : zero;
+            const cth_h8 v = cth_read<CT_PLAIN>(a.g + ((size_t)min(y, h - 1) * w + min(x, w - 1)) * (8 * NOG) + 8 * o, 8 * NOG, w, y < h && x < w);
 #pragma unroll
             for (int j = 0; j < 8; ++j) s_g[(8 * o + j) * HGHT_GROW + p] = v[j];
         }
-        for (int i = tid; i < WINH * WINW * 2; i += HGHT_THREADS) {
+        for (int i = tid; i < WINH * WINW * 2; i += CT_THREADS) {
             const int p = i >> 1, o2 = i & 1, yy = p / WINW, xx = p - yy * WINW, y = ty0 + yy - PAD, x = tx0 + xx - PAD;
             const int oc = 2 * slice + o2, occ = min(oc, NO - 1);
             const bool from_a = CB == 0 || occ < NOA;
             const bool in = oc < NO && y >= 0 && y < h && x >= 0 && x < w;
-            hght_h8 v;
-            if (from_a) {
-                const _Float16* const q = a.a + (size_t)ct_source_offset<MODE>(y, x, h, w, a.hs, a.ws) * (8 * NOA) + 8 * occ;
-                v = *reinterpret_cast<const hght_h8*>(q);
-                if (MODE == CT_POOL) {
-                    const size_t cp = 8 * NOA;
-                    const hght_h8 v1 = *reinterpret_cast<const hght_h8*>(q + cp), v2 = *reinterpret_cast<const hght_h8*>(q + (size_t)a.ws * cp),
-                                  v3 = *reinterpret_cast<const hght_h8*>(q + ((size_t)a.ws + 1) * cp);
-                    v = __builtin_elementwise_max(__builtin_elementwise_max(v, v1), __builtin_elementwise_max(v2, v3));
-                }
-            } else {
-                v = *reinterpret_cast<const hght_h8*>(a.b + (size_t)ct_source_offset<CT_PLAIN>(y, x, h, w, h, w) * (8 * (NOB > 0 ? NOB : 1)) + 8 * (occ - NOA));
-            }
-            v = in ? v : zero;
+            constexpr size_t CPA = 8 * NOA, CPB = 8 * (NOB > 0 ? NOB : 1);          // binary16 per pixel of the two inputs
+            const cth_h8 v = from_a ? cth_read<MODE>(a.a + (size_t)ct_source_offset<MODE>(y, x, h, w, a.hs, a.ws) * CPA + 8 * occ, CPA, a.ws, in)
+                                    : cth_read<CT_PLAIN>(a.b + (size_t)ct_source_offset<CT_PLAIN>(y, x, h, w, h, w) * CPB + 8 * (occ - NOA), CPB, w, in);
 #pragma unroll
             for (int d = 0; d < COPIES; ++d) {          // copy d holds the window shifted by d columns: every tap's eight pixels start at a multiple of 8
                 const int xs = xx - d;
@@ -547,19 +400,19 @@ __global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtW
             }
         }
         __syncthreads();
-        hght_h8 av[MT];
+        cth_h8 av[MT];
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) av[mt] = *reinterpret_cast<const hght_h8*>(s_g + (mt * 16 + col) * HGHT_GROW + 32 * wave + 8 * kq);
+        for (int mt = 0; mt < MT; ++mt) av[mt] = *reinterpret_cast<const cth_h8*>(s_g + (mt * 16 + col) * HGHT_GROW + 32 * wave + 8 * kq);
 #pragma unroll
         for (int t = 0; t < TAPS; ++t) {
             const int dy = TAPS == 9 ? t / 3 : 0, dx = TAPS == 9 ? t % 3 : 0;
-            const hght_h8 bv = *reinterpret_cast<const hght_h8*>(s_i + (dx * HGHT_SLICE + col) * ICH + (row + dy) * HGHT_WT_W + xo);
+            const cth_h8 bv = *reinterpret_cast<const cth_h8*>(s_i + (dx * HGHT_SLICE + col) * ICH + (row + dy) * HGHT_WT_W + xo);
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt][t] = hght_mfma(av[mt], bv, acc[mt][t]);
+            for (int mt = 0; mt < MT; ++mt) acc[mt][t] = cth_mfma(av[mt], bv, acc[mt][t]);
         }
         if (slice == 0) {          // (uniform over the workgroup) the bias gradient is read from the first slice's partial
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt][TAPS] = hght_mfma(av[mt], ones, acc[mt][TAPS]);
+            for (int mt = 0; mt < MT; ++mt) acc[mt][TAPS] = cth_mfma(av[mt], ones, acc[mt][TAPS]);
         }
     }
     // the four waves' sums are added in wave order through LDS, one row of result tiles at a time: the workgroup's partial
@@ -573,7 +426,7 @@ __global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtW
 #pragma unroll
             for (int r = 0; r < 4; ++r) s_red[((wave * NTT + t) * 4 + r) * 64 + lane] = acc[mt][t][r];
         __syncthreads();
-        for (int i = tid; i < NTT * 256; i += HGHT_THREADS) {
+        for (int i = tid; i < NTT * 256; i += CT_THREADS) {
             const float sum = ((s_red[i] + s_red[NTT * 256 + i]) + s_red[2 * NTT * 256 + i]) + s_red[3 * NTT * 256 + i];
             const int l = i & 63, r = (i >> 6) & 3, t = i >> 8;
             out[(mt * 16 + (l >> 4) * 4 + r) * NCOLS + t * 16 + (l & 15)] = sum;
@@ -582,10 +435,10 @@ __global__ void __launch_bounds__(HGHT_THREADS, 2) hght_wgrad_kernel(const HghtW
 }
 
 // dW[o, i, t] and db[o]: the partials of the strips, in strip order, in double; times 2^-k
-__global__ void __launch_bounds__(HGHT_THREADS) hght_wsum_kernel(const float* __restrict__ partial, int strips, int slices, int coutp, int taps, int cout, int ca, int cb,
-                                                                 const HghtCtrl* ctrl, float* __restrict__ dw, float* __restrict__ db)
+__global__ void __launch_bounds__(CT_THREADS) hght_wsum_kernel(const float* __restrict__ partial, int strips, int slices, int coutp, int taps, int cout, int ca, int cb,
+                                                               const HghtCtrl* ctrl, float* __restrict__ dw, float* __restrict__ db)
 {
-    const int cin = ca + cb, e = blockIdx.x * HGHT_THREADS + threadIdx.x, nw = cout * cin * taps, ncols = (taps + 1) * 16;
+    const int cin = ca + cb, e = blockIdx.x * CT_THREADS + threadIdx.x, nw = cout * cin * taps, ncols = (taps + 1) * 16;
     if (e >= nw + cout) return;
     int o, slice, n;
     if (e < nw) {
@@ -609,22 +462,22 @@ __global__ void __launch_bounds__(HGHT_THREADS) hght_wsum_kernel(const float* __
 // ---- routing -----------------------------------------------------------------------------------------------------------------------------------------------
 // out[y, x, c] = h((add[y, x, c] + (g_pool[y / 2, x / 2, c] if (y, x) is the first maximum of its window of t, else 0)) [t[y, x, c] > 0]), four channels per
 // thread.  t, out: binary16, add, g_pool: float32, all pixel-major with cp channels; t, add, out at h x w, g_pool at h2 x w2 = (h / 2) x (w / 2).
-__global__ void __launch_bounds__(HGHT_THREADS) hght_unpool_kernel(const float* __restrict__ g_pool, const _Float16* __restrict__ t, const float* __restrict__ add,
-                                                                   _Float16* __restrict__ out, int cp, int h, int w, int h2, int w2, HghtCtrl* ctrl)
+__global__ void __launch_bounds__(CT_THREADS) hght_unpool_kernel(const float* __restrict__ g_pool, const _Float16* __restrict__ t, const float* __restrict__ add,
+                                                                 _Float16* __restrict__ out, int cp, int h, int w, int h2, int w2, HghtCtrl* ctrl)
 {
     const int groups = cp >> 2;
-    const size_t i = (size_t)blockIdx.x * HGHT_THREADS + threadIdx.x, n = (size_t)h * w * groups;
+    const size_t i = (size_t)blockIdx.x * CT_THREADS + threadIdx.x, n = (size_t)h * w * groups;
     if (i >= n) return;
     const int c0 = 4 * (int)(i % groups), p = (int)(i / groups), y = p / w, x = p - y * w;
     const int py = y >> 1, px = x >> 1, pyc = min(py, h2 - 1), pxc = min(px, w2 - 1);
     const _Float16* const q = t + ((size_t)(2 * pyc) * w + 2 * pxc) * cp + c0;          // 2 pyc + 1 <= 2 h2 - 1 <= h - 1
-    const hght_h4 v0 = *reinterpret_cast<const hght_h4*>(q), v1 = *reinterpret_cast<const hght_h4*>(q + cp),
-                  v2 = *reinterpret_cast<const hght_h4*>(q + (size_t)w * cp), v3 = *reinterpret_cast<const hght_h4*>(q + ((size_t)w + 1) * cp);
-    const hght_f32x4 routed = *reinterpret_cast<const hght_f32x4*>(g_pool + ((size_t)pyc * w2 + pxc) * cp + c0);
-    const hght_f32x4 skip = *reinterpret_cast<const hght_f32x4*>(add + (size_t)p * cp + c0);
-    const hght_h4 me = *reinterpret_cast<const hght_h4*>(t + (size_t)p * cp + c0);
+    const cth_h4 v0 = *reinterpret_cast<const cth_h4*>(q), v1 = *reinterpret_cast<const cth_h4*>(q + cp),
+                  v2 = *reinterpret_cast<const cth_h4*>(q + (size_t)w * cp), v3 = *reinterpret_cast<const cth_h4*>(q + ((size_t)w + 1) * cp);
+    const ct_f32x4 routed = *reinterpret_cast<const ct_f32x4*>(g_pool + ((size_t)pyc * w2 + pxc) * cp + c0);
+    const ct_f32x4 skip = *reinterpret_cast<const ct_f32x4*>(add + (size_t)p * cp + c0);
+    const cth_h4 me = *reinterpret_cast<const cth_h4*>(t + (size_t)p * cp + c0);
     const int mine_k = 2 * (y & 1) + (x & 1);
-    hght_h4 res;
+    cth_h4 res;
     int bad = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -638,32 +491,32 @@ __global__ void __launch_bounds__(HGHT_THREADS) hght_unpool_kernel(const float* 
         res[r] = me[r] > (_Float16)0.0f ? (_Float16)sum : (_Float16)0.0f;
         bad += hght_bad(res[r]) ? 1 : 0;
     }
-    *reinterpret_cast<hght_h4*>(out + (size_t)p * cp + c0) = res;
+    *reinterpret_cast<cth_h4*>(out + (size_t)p * cp + c0) = res;
     if (bad) atomicAdd(&ctrl->nonfinite, bad);
 }
 
 // out[Y, X, c] = h((the sum of g[y, x, c] over the (y, x) of the h x w frame whose nearest source is (Y, X), rows then columns) [t[Y, X, c] > 0]).  t, out: hl x wl.
-__global__ void __launch_bounds__(HGHT_THREADS) hght_unup_kernel(const float* __restrict__ g, const _Float16* __restrict__ t, _Float16* __restrict__ out, int cp, int h, int w,
-                                                                 int hl, int wl, HghtCtrl* ctrl)
+__global__ void __launch_bounds__(CT_THREADS) hght_unup_kernel(const float* __restrict__ g, const _Float16* __restrict__ t, _Float16* __restrict__ out, int cp, int h, int w,
+                                                               int hl, int wl, HghtCtrl* ctrl)
 {
     const int groups = cp >> 2;
-    const size_t i = (size_t)blockIdx.x * HGHT_THREADS + threadIdx.x, n = (size_t)hl * wl * groups;
+    const size_t i = (size_t)blockIdx.x * CT_THREADS + threadIdx.x, n = (size_t)hl * wl * groups;
     if (i >= n) return;
     const int c0 = 4 * (int)(i % groups), p = (int)(i / groups), Y = p / wl, X = p - Y * wl;
     const int y0 = (int)(((int64_t)Y * h + hl - 1) / hl), y1 = min((int)(((int64_t)(Y + 1) * h + hl - 1) / hl), h);
     const int x0 = (int)(((int64_t)X * w + wl - 1) / wl), x1 = min((int)(((int64_t)(X + 1) * w + wl - 1) / wl), w);
-    hght_f32x4 sum = {0.0f, 0.0f, 0.0f, 0.0f};
+    ct_f32x4 sum = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int y = y0; y < y1; ++y)
-        for (int x = x0; x < x1; ++x) sum += *reinterpret_cast<const hght_f32x4*>(g + ((size_t)y * w + x) * cp + c0);
-    const hght_h4 me = *reinterpret_cast<const hght_h4*>(t + (size_t)p * cp + c0);
-    hght_h4 res;
+        for (int x = x0; x < x1; ++x) sum += *reinterpret_cast<const ct_f32x4*>(g + ((size_t)y * w + x) * cp + c0);
+    const cth_h4 me = *reinterpret_cast<const cth_h4*>(t + (size_t)p * cp + c0);
+    cth_h4 res;
     int bad = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         res[r] = me[r] > (_Float16)0.0f ? (_Float16)sum[r] : (_Float16)0.0f;
         bad += hght_bad(res[r]) ? 1 : 0;
     }
-    *reinterpret_cast<hght_h4*>(out + (size_t)p * cp + c0) = res;
+    *reinterpret_cast<cth_h4*>(out + (size_t)p * cp + c0) = res;
     if (bad) atomicAdd(&ctrl->nonfinite, bad);
 }
 
@@ -680,7 +533,7 @@ struct HghtStrips {          // how a frame of h x w is cut into strips of tiles
     }
 };
 
-constexpr int hght_slices(int ca, int cb) { return (hght_octets(ca) + hght_octets(cb) + 1) / 2; }
+constexpr int hght_slices(int ca, int cb) { return (cth_octets(ca) + cth_octets(cb) + 1) / 2; }
 
 // the floats of the partials of the weight gradients of layers I .. of HG_LAYERS, each at its own resolution: the most any of them takes
 template <int I = 0>
@@ -698,8 +551,8 @@ static size_t hght_partial_floats(const int (&h)[3], const int (&w)[3])
 // the operand fragments, in the order of the packing launch's table
 enum { HGHT_W_DEC1, HGHT_W_FUSE, HGHT_W_FINAL_T, HGHT_W_FUSE_T_LO, HGHT_W_FUSE_T_HI, HGHT_W_DEC1_T_A, HGHT_W_DEC1_T_B, HGHT_W_UP1_T, HGHT_W_DEC2_T_A,
        HGHT_W_DEC2_T_B, HGHT_W_UP2_T, HGHT_W_ENC3_T, HGHT_W_ENC2_T, HGHT_W_ENC1_T };
-constexpr int HGHT_ITEM_FRAGS[HGHT_ITEMS] = {hght_frags3(10, 38), HGHT_FUSE_STEPS * 3 * 64, 3 * 64, 2 * 3 * 64, 2 * 3 * 64, hght_frags3(5, 38), hght_frags3(5, 38),
-                                             hght_frags3(5, 19), hght_frags3(3, 19), hght_frags3(3, 19), hght_frags3(3, 9), hght_frags3(2, 19), hght_frags3(3, 38), hght_frags3(5, 38)};
+constexpr int HGHT_ITEM_FRAGS[HGHT_ITEMS] = {cth_frags3(10, 38), CTH_FUSE_STEPS * 3 * 64, 3 * 64, 2 * 3 * 64, 2 * 3 * 64, cth_frags3(5, 38), cth_frags3(5, 38),
+                                             cth_frags3(5, 19), cth_frags3(3, 19), cth_frags3(3, 19), cth_frags3(3, 9), cth_frags3(2, 19), cth_frags3(3, 38), cth_frags3(5, 38)};
 constexpr int hght_at(int i) { return i == 0 ? 0 : hght_at(i - 1) + HGHT_ITEM_FRAGS[i - 1]; }
 constexpr int HGHT_FRAGS = hght_at(HGHT_ITEMS);
 static_assert((size_t)HGHT_FRAGS * 16 == IBGS_HGHT_PACKED_WEIGHT_BYTES, "the header's size of the packed weights");
@@ -708,7 +561,7 @@ struct HghtScratch {          // the arena of the header, in its order
     HghtCtrl* ctrl;
     _Float16 *d1, *f, *Gf, *Gd1, *gs, *Gd2, *Gu2, *Ge2, *Gb;
     float *e1a, *Iup1, *e2a, *Iup2, *Ienc2, *Ienc3, *partial;
-    hght_h8* packed;
+    cth_h8* packed;
     size_t bytes;
     HghtScratch(char* base, int H, int W)
     {
@@ -731,7 +584,7 @@ struct HghtScratch {          // the arena of the header, in its order
         Ienc2 = c.take<float>(40 * p2);
         Gb = c.take<_Float16>(16 * p4);
         Ienc3 = c.take<float>(24 * p4);
-        packed = c.take<hght_h8>(HGHT_FRAGS);
+        packed = c.take<cth_h8>(HGHT_FRAGS);
         partial = c.take<float>(hght_partial_floats(h, w));
         bytes = hg_carved_bytes(c, base);
     }
@@ -740,24 +593,24 @@ struct HghtScratch {          // the arena of the header, in its order
 template <int CA, int CB, int COUT, int EPI>
 static void hght_conv(hipStream_t st, const HghtConv& a)
 {
-    const dim3 grid((unsigned)((a.w + HGHT_TILE - 1) / HGHT_TILE), (unsigned)((a.h + HGHT_TILE - 1) / HGHT_TILE));
-    hipLaunchKernelGGL((hght_conv3_kernel<CA, CB, COUT, EPI>), grid, dim3(HGHT_THREADS), 0, st, a);
+    const dim3 grid((unsigned)((a.w + CT_TILE - 1) / CT_TILE), (unsigned)((a.h + CT_TILE - 1) / CT_TILE));
+    hipLaunchKernelGGL((hght_conv3_kernel<CA, CB, COUT, EPI>), grid, dim3(CT_THREADS), 0, st, a);
 }
 
 // the input gradient of a 3 x 3 layer from its G (CL channels): COUT rows of the transposed weight
-static HghtConv hght_dgrad(const _Float16* G, const hght_h8* wfrag, HghtCtrl* ctrl, int h, int w)
+static HghtConv hght_dgrad(const _Float16* G, const cth_h8* wfrag, HghtCtrl* ctrl, int h, int w)
 {
     HghtConv a = {};
     a.a = G; a.wfrag = wfrag; a.ctrl = ctrl; a.h = h; a.w = w;
     return a;
 }
-static HghtConv hght_dgrad_f32(const _Float16* G, const hght_h8* wfrag, HghtCtrl* ctrl, int h, int w, float* out)
+static HghtConv hght_dgrad_f32(const _Float16* G, const cth_h8* wfrag, HghtCtrl* ctrl, int h, int w, float* out)
 {
     HghtConv a = hght_dgrad(G, wfrag, ctrl, h, w);
     a.out32 = out;
     return a;
 }
-static HghtConv hght_dgrad_mask(const _Float16* G, const hght_h8* wfrag, HghtCtrl* ctrl, int h, int w, const _Float16* mask, _Float16* out)
+static HghtConv hght_dgrad_mask(const _Float16* G, const cth_h8* wfrag, HghtCtrl* ctrl, int h, int w, const _Float16* mask, _Float16* out)
 {
     HghtConv a = hght_dgrad(G, wfrag, ctrl, h, w);
     a.mask = mask; a.out16 = out;
@@ -772,9 +625,9 @@ static void hght_wgrad(hipStream_t st, const _Float16* G, const _Float16* in_a, 
     HghtWgrad a = {};
     a.g = G; a.a = in_a; a.b = in_b; a.partial = sc.partial; a.h = h; a.w = w; a.hs = hs; a.ws = ws;
     a.tiles_x = strips.tiles_x; a.ntiles = strips.ntiles; a.strip_tiles = strips.strip_tiles;
-    hipLaunchKernelGGL((hght_wgrad_kernel<CA, CB, COUT, MODE, TAPS>), dim3(SLICES, (unsigned)strips.strips), dim3(HGHT_THREADS), 0, st, a);
+    hipLaunchKernelGGL((hght_wgrad_kernel<CA, CB, COUT, MODE, TAPS>), dim3(SLICES, (unsigned)strips.strips), dim3(CT_THREADS), 0, st, a);
     const int n = COUT * (CA + CB) * TAPS + COUT;
-    hipLaunchKernelGGL(hght_wsum_kernel, dim3(grid_for((size_t)n, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, sc.partial, strips.strips, SLICES, ((COUT + 15) / 16) * 16, TAPS, COUT,
+    hipLaunchKernelGGL(hght_wsum_kernel, dim3(grid_for((size_t)n, CT_THREADS)), dim3(CT_THREADS), 0, st, sc.partial, strips.strips, SLICES, ((COUT + 15) / 16) * 16, TAPS, COUT,
                        CA, CB, sc.ctrl, dw, db);
 }
 
@@ -824,7 +677,7 @@ int32_t ibgs_hgh_train_backward(void* stream, int32_t H, int32_t W, const float*
     const HghtScratch sc(static_cast<char*>(scratch), H, W);
     if (!arena_ok(who, "scratch", scratch, scratch_bytes, sc.bytes)) return -IBGS_ERR_INVALID;
     Carver fa(static_cast<char*>(const_cast<void*>(forward_arena)));          // the arena of ibgs_hgh_forward, read only: h(x), then the six stages
-    const _Float16* const xh = fa.take<_Float16>(8 * HGHT_XO * (size_t)H * (size_t)W);
+    const _Float16* const xh = fa.take<_Float16>(8 * CTH_XO * (size_t)H * (size_t)W);
     const HgStages<const _Float16> sg = hg_carve_stages<const _Float16>(fa, (size_t)H, (size_t)W, 8);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2;
@@ -835,7 +688,7 @@ int32_t ibgs_hgh_train_backward(void* stream, int32_t H, int32_t W, const float*
     // the control words, the scale, the operands
     IBGS_HIP(hipMemsetAsync(ctrl, 0, sizeof(HghtCtrl), st));
     const bool fixed = scale_mode == IBGS_HGHT_SCALE_FIXED;
-    hipLaunchKernelGGL(hght_scale_kernel, dim3(fixed ? 1u : (grid_for(3 * p1, HGHT_THREADS) < (unsigned)HGHT_SCALE_BLOCKS ? grid_for(3 * p1, HGHT_THREADS) : (unsigned)HGHT_SCALE_BLOCKS)), dim3(HGHT_THREADS), 0, st, grad_residual,
+    hipLaunchKernelGGL(hght_scale_kernel, dim3(fixed ? 1u : (grid_for(3 * p1, CT_THREADS) < (unsigned)HGHT_SCALE_BLOCKS ? grid_for(3 * p1, CT_THREADS) : (unsigned)HGHT_SCALE_BLOCKS)), dim3(CT_THREADS), 0, st, grad_residual,
                        grad_image_pred, 3 * p1, fixed ? 1 : 0, (int)grad_scale_log2, ctrl);
     HghtPackArgs pk = {};
     pk.packed = sc.packed; pk.frags = HGHT_FRAGS;
@@ -846,7 +699,7 @@ int32_t ibgs_hgh_train_backward(void* stream, int32_t H, int32_t W, const float*
         {dec2_w, HGHT_P3_T, 19, 19, 0, 38, 0, 0},            {dec2_w, HGHT_P3_T, 19, 19, 0, 38, 19, 0},          {up2_conv_w, HGHT_P3_T, 9, 19, 0, 9, 0, 0},
         {enc3_w, HGHT_P3_T, 19, 9, 0, 19, 0, 0},             {enc2_w, HGHT_P3_T, 38, 19, 0, 38, 0, 0},           {enc1_w, HGHT_P3_T, 38, 38, 0, 38, 0, 0}};
     for (int i = 0; i < HGHT_ITEMS; ++i) { pk.item[i] = items[i]; pk.item[i].first = hght_at(i); }
-    hipLaunchKernelGGL(hght_pack_kernel, dim3(grid_for(HGHT_FRAGS, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, pk);
+    hipLaunchKernelGGL(hght_pack_kernel, dim3(grid_for(HGHT_FRAGS, CT_THREADS)), dim3(CT_THREADS), 0, st, pk);
 
     // the head: d1, f, gS, G_f, G_d1 and the head's share of grad_x
     HghtConv head = {};
@@ -867,7 +720,7 @@ int32_t ibgs_hgh_train_backward(void* stream, int32_t H, int32_t W, const float*
     // up1_conv: G_d2
     if (want_params) hght_wgrad<19, 0, 38, CT_UP, 9>(st, Gu1, sg.d2, nullptr, sc, grad_up1_conv_w, grad_up1_conv_b, H, W, H2, W2);
     hght_conv<38, 0, 19, HGHT_EPI_F32>(st, hght_dgrad_f32(Gu1, frag(HGHT_W_UP1_T), ctrl, H, W, sc.Iup1));
-    hipLaunchKernelGGL(hght_unup_kernel, dim3(grid_for(6 * p2, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, sc.Iup1, sg.d2, sc.Gd2, 24, H, W, H2, W2, ctrl);
+    hipLaunchKernelGGL(hght_unup_kernel, dim3(grid_for(6 * p2, CT_THREADS)), dim3(CT_THREADS), 0, st, sc.Iup1, sg.d2, sc.Gd2, 24, H, W, H2, W2, ctrl);
     // dec2: G_u2, g_e2a
     if (want_params) hght_wgrad<19, 19, 19, CT_PLAIN, 9>(st, sc.Gd2, sg.u2, sg.e2, sc, grad_dec2_w, grad_dec2_b, H2, W2, H2, W2);
     hght_conv<19, 0, 19, HGHT_EPI_MASK>(st, hght_dgrad_mask(sc.Gd2, frag(HGHT_W_DEC2_T_A), ctrl, H2, W2, sg.u2, sc.Gu2));
@@ -875,16 +728,16 @@ int32_t ibgs_hgh_train_backward(void* stream, int32_t H, int32_t W, const float*
     // up2_conv: G_b
     if (want_params) hght_wgrad<9, 0, 19, CT_UP, 9>(st, sc.Gu2, sg.b, nullptr, sc, grad_up2_conv_w, grad_up2_conv_b, H2, W2, H4, W4);
     hght_conv<19, 0, 9, HGHT_EPI_F32>(st, hght_dgrad_f32(sc.Gu2, frag(HGHT_W_UP2_T), ctrl, H2, W2, sc.Iup2));
-    hipLaunchKernelGGL(hght_unup_kernel, dim3(grid_for(4 * p4, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, sc.Iup2, sg.b, sc.Gb, 16, H2, W2, H4, W4, ctrl);
+    hipLaunchKernelGGL(hght_unup_kernel, dim3(grid_for(4 * p4, CT_THREADS)), dim3(CT_THREADS), 0, st, sc.Iup2, sg.b, sc.Gb, 16, H2, W2, H4, W4, ctrl);
     // enc3: G_e2
     if (want_params) hght_wgrad<19, 0, 9, CT_POOL, 9>(st, sc.Gb, sg.e2, nullptr, sc, grad_enc3_w, grad_enc3_b, H4, W4, H2, W2);
     hght_conv<9, 0, 19, HGHT_EPI_F32>(st, hght_dgrad_f32(sc.Gb, frag(HGHT_W_ENC3_T), ctrl, H4, W4, sc.Ienc3));
-    hipLaunchKernelGGL(hght_unpool_kernel, dim3(grid_for(6 * p2, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, sc.Ienc3, sg.e2, sc.e2a, sc.Ge2, 24, H2, W2, H4, W4, ctrl);
+    hipLaunchKernelGGL(hght_unpool_kernel, dim3(grid_for(6 * p2, CT_THREADS)), dim3(CT_THREADS), 0, st, sc.Ienc3, sg.e2, sc.e2a, sc.Ge2, 24, H2, W2, H4, W4, ctrl);
     // enc2: G_e1 (in G_d1's place)
     _Float16* const Ge1 = sc.Gd1;
     if (want_params) hght_wgrad<38, 0, 19, CT_POOL, 9>(st, sc.Ge2, sg.e1, nullptr, sc, grad_enc2_w, grad_enc2_b, H2, W2, H, W);
     hght_conv<19, 0, 38, HGHT_EPI_F32>(st, hght_dgrad_f32(sc.Ge2, frag(HGHT_W_ENC2_T), ctrl, H2, W2, sc.Ienc2));
-    hipLaunchKernelGGL(hght_unpool_kernel, dim3(grid_for(10 * p1, HGHT_THREADS)), dim3(HGHT_THREADS), 0, st, sc.Ienc2, sg.e1, sc.e1a, Ge1, 40, H, W, H2, W2, ctrl);
+    hipLaunchKernelGGL(hght_unpool_kernel, dim3(grid_for(10 * p1, CT_THREADS)), dim3(CT_THREADS), 0, st, sc.Ienc2, sg.e1, sc.e1a, Ge1, 40, H, W, H2, W2, ctrl);
     // enc1
     if (want_params) hght_wgrad<38, 0, 38, CT_PLAIN, 9>(st, Ge1, xh, nullptr, sc, grad_enc1_w, grad_enc1_b, H, W, H, W);
     if (want_x) {

@@ -12,7 +12,7 @@
 // THE STAGING DISCIPLINE (tests/test_gpu_dirty_buffers.py)  coordinates are clamped INTO the frame before an offset is formed, every
 // load is unconditional and from a valid address (so the loads of a chunk are all in flight together), and what lies outside the frame or past the last
 // channel is replaced by zero afterwards.
-// ibgs_amd/_build.py lists this header under the five units (UNIT_HEADERS; SIDE_UNITS for hghtrain.hip) and no other.
+// ibgs_amd/_build.py lists this header under the five units (UNIT_HEADERS) and no other; conv_tile_f16.h, next to this file, is the f16 tile of the two half units.
 #pragma once
 #include "../common.h"
 

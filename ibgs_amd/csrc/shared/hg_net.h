@@ -6,8 +6,8 @@
 // e1, e2, u2, d2, u1 and b are the STAGES: the outputs of the first six layers, at level 0 (H x W), 1 (H / 2 x W / 2) or 2 (H / 2 / 2 x W / 2 / 2).  THE ARENA
 // of a forward holds them in the order of their layers -- e1, e2, b, u2, d2, u1 -- each at the next multiple of 128 bytes; d1 and f never reach memory.
 // Host code and what lies outside a kernel body only.  The geometry of the float32 kernels (tile, threads, window, staged planes), their lane map and the rule
-// by which a layer reads its first input (a kernel's MODE: CT_PLAIN, CT_POOL, CT_UP) are conv_tile.h's, next to this file; the half-precision kernel's staging
-// is its own unit's.  ibgs_amd/_build.py lists this header under the four units (UNIT_HEADERS; SIDE_UNITS for hghtrain.hip) and no other: it sits in a subdirectory of csrc/ so that no
+// by which a layer reads its first input (a kernel's MODE: CT_PLAIN, CT_POOL, CT_UP) are conv_tile.h's, next to this file; the half-precision kernels' staging
+// is conv_tile_f16.h's.  ibgs_amd/_build.py lists this header under the four units (UNIT_HEADERS) and no other: it sits in a subdirectory of csrc/ so that no
 // other unit's profile stamp holds it.
 #pragma once
 #include "../common.h"

@@ -72,10 +72,10 @@ def test_kernels_attributed_to_the_coloragg_unit():
     assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp_bwd.h", "../../include/ibgs_color_agg.h"]          # (pv_mlp_bwd.h includes pv_mlp.h)
     assert re.findall(r'#include "([^"]+)"', open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "pv_mlp_bwd.h")).read()) == ["pv_mlp.h"]
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["conv_tile.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
+    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["conv_tile.h", "conv_tile_f16.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
     for unit, headers in (("coloragg", ["pv_mlp.h", "pv_mlp_bwd.h"]), ("resample", ["pv_mlp.h", "rsz_taps.h"]), ("ssim", ["ssim_window.h"]), ("geoloss", ["ssim_window.h"])):
         assert [os.path.basename(h) for h in _build.UNIT_HEADERS[unit]][1:] == headers, unit
-    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 9          # no other unit's stamp holds them (rsztrain is the eighth, lpips with conv_tile.h the ninth)
+    assert sum(any("shared" in h for h in hs) for hs in _build.UNIT_HEADERS.values()) == 10          # no other unit's stamp holds them (rsztrain is the eighth, lpips with conv_tile.h the ninth, hghtrain the tenth)
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

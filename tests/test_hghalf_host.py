@@ -17,6 +17,7 @@ from tests.test_hourglass_host import _layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ibgs_amd", "csrc", "hghalf.hip")
+TILE_H = os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "conv_tile_f16.h")          # the f16 tile, the octet read and fuse_input as hghalf.hip and hghtrain.hip share them
 HEADER = os.path.join(ROOT, "include", "ibgs_hg_half.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -60,19 +61,23 @@ def test_build_registration_and_the_kernels():
     assert _build.SOURCES[-1] == "hourglass" and _build.SOURCES.index("hghalf") < _build.SOURCES.index("hourglass")
     assert "hghalf" in _build.UNIT_HEADERS and "hghalf" in _build.tu_shas() and "hghalf" not in _build.EXTRA
     assert _build.compile_flags("hghalf") == _build.compile_flags("hourglass")
-    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h", "conv_tile.h"]
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghalf"]] == ["ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h", "conv_tile.h", "conv_tile_f16.h"]
     assert all(os.path.exists(h) for h in _build.UNIT_HEADERS["hghalf"])
     # the float32 unit's kernel still goes where it went
     assert _build.tu_of("hg_conv3_kernel") == "hourglass" and _build.tu_of("hgb_wgrad_kernel") == "hgtrain"
-    code = _build._code_only(src)
+    mine, tile = _build._code_only(src), _build._code_only(open(TILE_H).read())
+    code = mine + "\n" + tile          # the unit's own code and the shared header's: the pins hold on both
     assert "atomic" not in code.lower() and "asm" not in code.lower()          # nothing crosses a workgroup; builtins only
     assert "__builtin_amdgcn_mfma_f32_16x16x32_f16" in code and "16x16x4f32" not in code
-    assert len(re.findall(r"__builtin_amdgcn_mfma_\w+", code)) == 1          # the one f16 form, nothing else
-    assert "pkrtz" not in code and "(_Float16)" in code          # conversions are casts: to nearest even
-    assert re.search(r"constexpr int HGH_TILE = 16;", code) and re.search(r"constexpr int HGH_THREADS = 256;", code)
-    assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ HGH_TILE - 1\) / HGH_TILE\), \(unsigned\)\(\(a\.h \+ HGH_TILE - 1\) / HGH_TILE\)\);", code)
+    assert len(re.findall(r"__builtin_amdgcn_mfma_\w+", code)) == 1 and "__builtin_amdgcn_mfma" not in mine          # the one f16 form, nothing else, and it is the header's
+    assert "pkrtz" not in code and "(_Float16)" in mine and "(_Float16)" in tile          # conversions are casts: to nearest even
+    assert re.search(r"constexpr int HGH_TILE = 16;", mine) and re.search(r"constexpr int HGH_THREADS = 256;", mine)
+    assert re.search(r"static_assert\(HGH_TILE == CT_TILE && HGH_THREADS == CT_THREADS,", mine)          # the tile is conv_tile.h's, which the header includes
+    assert re.search(r"const dim3 grid\(\(unsigned\)\(\(a\.w \+ HGH_TILE - 1\) / HGH_TILE\), \(unsigned\)\(\(a\.h \+ HGH_TILE - 1\) / HGH_TILE\)\);", mine)
     assert len(re.findall(r"hgh_launch<", code)) == 7 and len(re.findall(r"hipLaunchKernelGGL\(hgh_pack_kernel", code)) == 1
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "shared/conv_tile_f16.h", "../../include/ibgs_hourglass.h",
+                                                      "../../include/ibgs_hg_half.h"]
+    assert re.findall(r'#include "([^"]+)"', open(TILE_H).read()) == ["conv_tile.h", "hg_net.h"]
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

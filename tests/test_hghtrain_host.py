@@ -15,9 +15,11 @@ from tests import hghalf_bwd_ref as hbref
 from tests import hourglass_bwd_ref as bref
 from tests import hourglass_ref as ref
 from tests import test_gpu_hourglass as fwd
+from tests.test_resample_train_host import DEFINES, _csrc_code
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ibgs_amd", "csrc", "hghtrain.hip")
+TILE_H = os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "conv_tile_f16.h")          # the f16 tile, the octet read and fuse_input as this unit and hghalf.hip share them
 HEADER = os.path.join(ROOT, "include", "ibgs_hg_half_train.h")
 
 
@@ -54,33 +56,70 @@ def test_build_registration_and_the_kernels():
         assert not any(sub in k for sub in others), k          # whatever the order of the table
     assert [e for e in _build.KERNEL_TU if e[1] == "hghtrain"] == [("hght_", "hghtrain")]
     assert _build.tu_of("hgh_conv3_kernel") == "hghalf" and _build.tu_of("hgb_wgrad_kernel") == "hgtrain" and _build.tu_of("hg_conv3_kernel") == "hourglass"
-    # outside the stamped tables (SOURCES, UNIT_HEADERS, tu_shas(): what the committed profile summaries were stamped against), in a table of its own: compiled
-    # with the library's flags, rebuilt on an edit of any header it includes, linked into the same library
-    assert list(_build.SIDE_UNITS) == ["hghtrain"] and "hghtrain" not in _build.SOURCES and "hghtrain" not in _build.UNIT_HEADERS and "hghtrain" not in _build.tu_shas()
+    # registered like every other unit: one table of sources, one of headers, a profile stamp
+    assert _build.SOURCES[-1] == "hourglass" and _build.SOURCES.index("hghalf") < _build.SOURCES.index("hghtrain") < _build.SOURCES.index("hourglass")
+    assert "hghtrain" in _build.UNIT_HEADERS and "hghtrain" in _build.tu_shas() and _build.UNSTAMPED == ("export",)
+    assert not hasattr(_build, "SIDE_UNITS") and not hasattr(_build, "_headers_of")
     assert "hghtrain" not in _build.EXTRA and _build.compile_flags("hghtrain") == _build.compile_flags("hghalf")
-    assert [os.path.basename(h) for h in _build.SIDE_UNITS["hghtrain"]] == ["ibgs_hg_half_train.h", "ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h", "conv_tile.h"]
-    assert all(os.path.exists(h) for h in _build.SIDE_UNITS["hghtrain"])
-    for h in _build.SIDE_UNITS["hghtrain"]:
-        assert _build._newest_dep() >= os.path.getmtime(h) and h in _build._headers_of("hghtrain")
-    assert _build._headers_of("hghalf") == _build.UNIT_HEADERS["hghalf"] and _build._headers_of("api") == []
-    seen, todo = set(), [SRC]          # the table is the truth: what the unit and its shared headers include outside csrc/*.h and include/ibgs_rast.h
-    while todo:
-        f = todo.pop()
-        for inc in re.findall(r'#include "([^"]+)"', open(f).read()):
-            path = os.path.normpath(os.path.join(os.path.dirname(f), inc))
-            if os.path.dirname(path) != os.path.dirname(SRC) and os.path.basename(path) != "ibgs_rast.h" and path not in seen:
-                seen.add(path)
-                todo.append(path)
-    assert seen == {os.path.normpath(h) for h in _build.SIDE_UNITS["hghtrain"]}
-    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "../../include/ibgs_hourglass.h", "../../include/ibgs_hg_half.h",
-                                                      "../../include/ibgs_hg_half_train.h"]
-    code = _build._code_only(src)
+    assert [os.path.basename(h) for h in _build.UNIT_HEADERS["hghtrain"]] == ["ibgs_hg_half_train.h", "ibgs_hg_half.h", "ibgs_hourglass.h", "hg_net.h", "conv_tile.h",
+                                                                              "conv_tile_f16.h"]
+    assert all(os.path.exists(h) for h in _build.UNIT_HEADERS["hghtrain"])
+    for h in _build.UNIT_HEADERS["hghtrain"]:
+        assert _build._newest_dep() >= os.path.getmtime(h)
+    assert {k for k, hs in _build.UNIT_HEADERS.items() if TILE_H in [os.path.normpath(h) for h in hs]} == {"hghalf", "hghtrain"}
+    for unit in ("hghtrain", "hghalf"):          # the table is the truth: what the unit and its shared headers include outside csrc/*.h and include/ibgs_rast.h
+        seen, todo = set(), [os.path.join(os.path.dirname(SRC), unit + ".hip")]
+        while todo:
+            f = todo.pop()
+            for inc in re.findall(r'#include "([^"]+)"', open(f).read()):
+                path = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+                if os.path.dirname(path) != os.path.dirname(SRC) and os.path.basename(path) != "ibgs_rast.h" and path not in seen:
+                    seen.add(path)
+                    todo.append(path)
+        assert seen == {os.path.normpath(h) for h in _build.UNIT_HEADERS[unit]}, unit
+    assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/hg_net.h", "shared/conv_tile.h", "shared/conv_tile_f16.h", "../../include/ibgs_hourglass.h",
+                                                      "../../include/ibgs_hg_half.h", "../../include/ibgs_hg_half_train.h"]
+    mine, tile = _build._code_only(src), _build._code_only(open(TILE_H).read())
+    code = mine + "\n" + tile          # the unit's own code and the shared header's: the pins hold on both
     assert "asm" not in code.lower()          # builtins only
-    assert sorted(set(re.findall(r"\b(atomic\w*)\s*\(", code))) == ["atomicAdd", "atomicMax"]          # integer words only: the control block's
-    assert re.search(r"struct HghtCtrl \{ unsigned m_bits; int k; int nonfinite; unsigned ticket; \};", code)
+    assert sorted(set(re.findall(r"\b(atomic\w*)\s*\(", code))) == ["atomicAdd", "atomicMax"] and "atomic" not in tile          # integer words only: the control block's
+    assert re.search(r"struct HghtCtrl \{ unsigned m_bits; int k; int nonfinite; unsigned ticket; \};", mine)
     assert "__builtin_amdgcn_mfma_f32_16x16x32_f16" in code and len(re.findall(r"__builtin_amdgcn_mfma_\w+", code)) == 1 and "16x16x4f32" not in code
-    assert "pkrtz" not in code and "(_Float16)" in code          # conversions are casts: to nearest even
-    assert re.search(r"constexpr int HGHT_E_TARGET = IBGS_HGHT_E_TARGET;", code)
+    assert "__builtin_amdgcn_mfma" not in mine          # the one builtin is the header's
+    assert "pkrtz" not in code and "(_Float16)" in mine and "(_Float16)" in tile          # conversions are casts: to nearest even
+    assert re.search(r"constexpr int HGHT_E_TARGET = IBGS_HGHT_E_TARGET;", mine)
+
+
+def test_the_f16_tile_is_defined_once_and_both_units_call_it():
+    """csrc/shared/conv_tile_f16.h: the mfma wrapper, the octet read, the main loop of the implicit GEMM, an accumulator tile as an operand, fuse_input on
+    [d1 | h(x)] (the forward's last launch and the backward's recomputed head: no test could see two copies drift, neither d1 nor f is stored by the forward)
+    and the order of a forward fragment's elements."""
+    code = _csrc_code()
+    shared = ("cth_mfma", "cth_round", "cth_read", "cth_start", "cth_conv3", "cth_as_operand", "cth_fuse_input", "cth_frag3_channel", "cth_acc_channel", "cth_frag1_channel")
+    for name in shared:
+        assert [f for f, text in code.items() for _ in re.findall(DEFINES % name, text, re.M)] == ["shared/conv_tile_f16.h"], name
+    units = ("hghalf.hip", "hghtrain.hip")
+    users = lambda pattern: sorted(f for f, text in code.items() if re.search(pattern, text))
+    for name in shared:          # no other user, and no second name for the same thing
+        assert set(users(r"\b%s\b" % name)) <= {"shared/conv_tile_f16.h", "hghalf.hip", "hghtrain.hip"}, name
+    assert users(r"\bhgh?t?_(?:mfma|round|octets|frags3?|as_operand|h8|h4|f32x4)\b") == [] and users(r"\bHGHT?_(?:ROWS|WIN|NPIX|PSTRIDE|XO|FUSE_STEPS)\b") == []
+    for unit in units:
+        for call in (r"cth_mfma\(", r"cth_conv3<CA, CB, COUT, \w+>\(acc, a\.a, a\.b, a\.wfrag,", r"cth_start<COUT>\(acc, a\.bias, kq\)", r"cth_as_operand<3, (?:true|false)>\(",
+                     r"cth_fuse_input<(?:true|false)>\(f, acc, a\.fuse_frag, a\.fuse_b, a\.xh, h, w\)", r"= cth_frag3_channel\(o, j, L\.ca, L\.cb\)",
+                     r"= cth_frag1_channel\(s, kq, j, L\.ca, L\.cb\)"):
+            assert re.search(call, code[unit]), (unit, call)
+        # the unit's own text holds none of the shared state: no maximum of a 2 x 2 window, no staged window, no vector type, no second lane-map constant
+        assert "__builtin_elementwise_max" not in code[unit] and not re.search(r"__shared__ \w+ s_(?:in|w)\[", code[unit]), unit
+        assert not re.search(r"typedef\s+_Float16\b[^;]*ext_vector_type", code[unit]) and "__builtin_amdgcn_mfma" not in code[unit], unit
+    # the octet read: the chunk loop and h(x) in the header; G and the two inputs of a weight gradient in hghtrain.hip (the forward reads through cth_conv3 only)
+    calls = {f: re.findall(r"cth_read<(\w+)>\(", text) for f, text in code.items() if re.search(r"cth_read<", text)}
+    assert calls == {"shared/conv_tile_f16.h": ["MODE", "CT_PLAIN"], "hghtrain.hip": ["CT_PLAIN", "MODE", "CT_PLAIN"]}
+    tile = code["shared/conv_tile_f16.h"]
+    assert len(re.findall(r"__builtin_elementwise_max", tile)) == 3 and len(re.findall(r"__shared__ cth_h8 s_(?:in|w)\[", tile)) == 2 and len(re.findall(r"__syncthreads\(\)", tile)) == 2
+    assert re.search(r"typedef _Float16 cth_h8 __attribute__\(\(ext_vector_type\(8\)\)\);", tile)
+    # the two kernels differ in how the accumulators start and in the epilogue, and the head hands the product clamped and rounded values
+    assert re.search(r"ct_f32x4 acc\[MT\]\[CT_ROWS\] = \{\};\n\s*if constexpr \(EPI == HGHT_EPI_HEAD\) cth_start<COUT>", code["hghtrain.hip"])
+    assert re.search(r"cth_fuse_input<true>", code["hghalf.hip"]) and re.search(r"cth_fuse_input<false>", code["hghtrain.hip"])
 
 
 def test_sizes_and_validation_before_any_gpu_work(built_lib):

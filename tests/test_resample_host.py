@@ -66,7 +66,7 @@ def test_unit_is_registered_and_its_kernels_attributed():
     assert re.findall(r'#include "([^"]+)"', src) == ["common.h", "shared/pv_mlp.h", "shared/rsz_taps.h", "../../include/ibgs_resample.h"]
     assert [os.path.basename(h) for h in _build.UNIT_HEADERS["resample"]] == ["ibgs_resample.h", "pv_mlp.h", "rsz_taps.h"] and all(os.path.exists(h) for h in _build.UNIT_HEADERS["resample"])
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc")) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["conv_tile.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
+    assert sorted(os.listdir(os.path.join(ROOT, "ibgs_amd", "csrc", "shared"))) == ["conv_tile.h", "conv_tile_f16.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
     chain = _build._code_only(open(os.path.join(ROOT, "ibgs_amd", "csrc", "shared", "pv_mlp.h")).read())
     assert re.search(r"__builtin_amdgcn_mfma_f32_32x32x2f32", chain) and not re.search(r"mfma", code.replace("pv_mfma", ""))
     assert re.search(r"pv_mlp\(", code) and re.search(r"pv_slot\(", code)

@@ -24,14 +24,15 @@ NAMES = ["ibgs_rzt_required_scratch", "ibgs_rzt_features_backward", "ibgs_rzt_up
 BWD_H, TAPS_H = os.path.join(CSRC, "shared", "pv_mlp_bwd.h"), os.path.join(CSRC, "shared", "rsz_taps.h")
 KERNELS = ["rzt_features_bwd_kernel", "rzt_gather_kernel", "rzt_upsample_bwd_kernel"]          # the final pass of the parameter gradients is coloragg.hip's cagg_final_kernel
 # _build.tu_shas() of the commit that gave coloragg, resample and rsztrain one definition of the tap rule and of the per-view backward: those three stamps are
-# that commit's; lpips, hgtrain, hghalf and hourglass are those of the commit that gave them csrc/shared/conv_tile.h; every other one is still that of the
+# that commit's; lpips, hgtrain and hourglass are those of the commit that gave them csrc/shared/conv_tile.h; hghalf and hghtrain (which had no stamp before) are
+# those of the commit that gave the two csrc/shared/conv_tile_f16.h and left conv_tile.h's and hg_net.h's code alone; every other one is still that of the
 # commit rsztrain was added to
 PARENT_SHAS = {"api": "d2cea40a3180", "preprocess": "de228898d0b1", "scan_sort": "01e63032a313", "binning": "f337b73e1959", "render_fwd": "6ae05116c8bc",
                "render_bwd": "052d2dbf3751", "preprocess_bwd": "a45a137dac86", "knn": "e9bfb2e02f4f", "adam": "6a3146aa7716", "compact": "99a39d9227b5",
                "deterministic": "a24d88fa046d", "loss": "1f16fa584baf", "depth_normal": "6cf4fb76b878", "activate": "62185582088c", "tsdf": "80be8448d09b",
                "mesh": "59c42111558a", "mesh_eval": "8214092e1449", "registration": "5a0bad737c95", "dtu": "f17c4e79d7ed", "ssim": "da26b26bfdb8",
                "geoloss": "9a7cae8f65e6", "coloragg": "0e34556dbaa7", "exposure": "315be22df182", "resample": "7bb6e6901370", "rsztrain": "c66c6940738e", "lpips": "4e4cd0b29e2b",
-               "hgtrain": "f5c55b05eb06", "hghalf": "d2e14c309633", "hourglass": "d97fb1d55e22"}
+               "hgtrain": "f5c55b05eb06", "hghalf": "524cc488b11b", "hghtrain": "695f31dcc08f", "hourglass": "d97fb1d55e22"}
 
 
 # ---- 1. the ABI and the build ----------------------------------------------------------------------------------------------------------------------------
@@ -69,7 +70,7 @@ def test_unit_is_registered_and_its_kernels_attributed():
     assert re.findall(r'#include "([^"]+)"', open(BWD_H).read()) == ["pv_mlp.h"] and re.findall(r'#include "([^"]+)"', open(TAPS_H).read()) == ["../common.h", "../../../include/ibgs_resample.h"]
     assert re.search(r"pv_mlp\(", code) and re.search(r"pv_slot\(", code) and not re.search(r"mfma", code.replace("pv_mfma", ""))          # the forward's own chain
     assert sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) == ["adam_math.h", "blend.h", "block_ops.h", "common.h", "sh_color.h", "wave_bits.h", "wave_reduce.h"]
-    assert sorted(os.listdir(os.path.join(CSRC, "shared"))) == ["conv_tile.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
+    assert sorted(os.listdir(os.path.join(CSRC, "shared"))) == ["conv_tile.h", "conv_tile_f16.h", "hg_net.h", "pv_mlp.h", "pv_mlp_bwd.h", "rsz_taps.h", "ssim_window.h"]
 
 
 def test_borrowed_headers_reach_the_rebuild_check_and_the_stamp(tmp_path, monkeypatch):
@@ -81,9 +82,9 @@ def test_borrowed_headers_reach_the_rebuild_check_and_the_stamp(tmp_path, monkey
     assert not hasattr(_build, "BORROWED_HEADERS") and not hasattr(_build, "unit_headers") and "api" not in _build.UNIT_HEADERS
     before = _build.tu_shas()
     for header, users in (("pv_mlp.h", {"coloragg", "resample", "rsztrain"}), ("pv_mlp_bwd.h", {"coloragg", "rsztrain"}), ("rsz_taps.h", {"resample", "rsztrain"}),
-                          ("ibgs_resample.h", {"resample", "rsztrain"}), ("ibgs_resample_train.h", {"rsztrain"})):
+                          ("ibgs_resample.h", {"resample", "rsztrain"}), ("ibgs_resample_train.h", {"rsztrain"}), ("conv_tile_f16.h", {"hghalf", "hghtrain"})):
         assert {k for k, hs in _build.UNIT_HEADERS.items() if header in base(hs)} == users, header
-        real = [h for h in _build.UNIT_HEADERS["rsztrain"] if os.path.basename(h) == header][0]
+        real = [h for h in _build.UNIT_HEADERS[sorted(users)[-1]] if os.path.basename(h) == header][0]          # (any of its users lists it: rsztrain, hghtrain)
         edited = tmp_path / header
         edited.write_text(open(real).read() + "\nstatic const int edited_for_the_test = 1;\n")
         swap = lambda hs: [str(edited) if os.path.basename(h) == header else h for h in hs]

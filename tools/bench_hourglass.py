@@ -103,8 +103,17 @@ def min_bytes_half(h, w):
     return 4 * 38 * p1 + 2 * (3 * 40 * p1 + 3 * 40 * p1 + 3 * 24 * p2 + 2 * 16 * p4 + 2 * 24 * p2 + 2 * 24 * p2 + 2 * 40 * p1) + 4 * 9 * p1
 
 
-def resource_report(say, unit="hourglass", kernel="hg_conv3_kernel"):
-    """hipcc's own report for hourglass.hip (or hghalf.hip) with the build's flags (compiled to a scratch file)."""
+# unit: (the legend above its rows, the width of a row's name, whether its template arguments are printed as the forward's <.., read mode, last launch>)
+REPORTS = {"hourglass": ("hipcc's report for hourglass.hip per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):", 48, True),
+           "hghalf": ("hipcc's report for hghalf.hip per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):", 48, True),
+           "hgtrain": ("hipcc's report per instantiation of hgtrain.hip (hgb_conv_kernel<channels of A, of B, Cout, taps, transposed>; hgb_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):", 44, False),
+           "hghtrain": ("hipcc's report per instantiation of hghtrain.hip (hght_conv3_kernel<channels of A, of B, rows, epilogue: 0 float32, 1 masked binary16, 2 grad_x, 3 head>; "
+                        "hght_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):", 44, False)}
+
+
+def resource_report(say, unit):
+    """hipcc's own report for one of the four hourglass units with the build's flags (compiled to a scratch file): a row per kernel and instantiation."""
+    legend, width, forward = REPORTS[unit]
     src = os.path.join(_build.CSRC, unit + ".hip")
     with tempfile.TemporaryDirectory() as d:
         r = subprocess.run([_build._hipcc()] + _build.compile_flags(unit) + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hg.o")],
@@ -118,17 +127,21 @@ def resource_report(say, unit="hourglass", kernel="hg_conv3_kernel"):
         if not m:
             continue
         if m.group(1):
-            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", m.group(1))
-            k = re.search(r"(hgh?_[a-z0-9_]+?)(?:I|E)", m.group(1))
-            cur = {"name": "%s<%s, %s, %s, %s, %s>" % (kernel, t.group(1), t.group(2), t.group(3), ("plain", "pool", "up")[int(t.group(4))], "fused" if t.group(5) == "1" else "-")
-                   if t else (k.group(1) if k else m.group(1))}
+            k = re.search(r"(hg[a-z]*_[a-z0-9_]+?)(?:I|E)", m.group(1))
+            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)(?:EL[ib]([0-9]+))?E", m.group(1))
+            name = k.group(1) if k else m.group(1)
+            if t and forward:
+                name += "<%s, %s, %s, %s, %s>" % (t.group(1), t.group(2), t.group(3), ("plain", "pool", "up")[int(t.group(4))], "fused" if t.group(5) == "1" else "-")
+            elif t:
+                name += "<%s>" % ", ".join(v for v in t.groups() if v is not None)
+            cur = {"name": name}
             rows.append(cur)
         elif cur is not None:
             cur[m.group(2).strip()] = int(m.group(3))
-    say("hipcc's report for %s.hip per instantiation (<channels of A, channels of B, Cout, read mode of A, last launch>):" % unit)
+    say(legend)
     for c in rows:
-        say("  %-48s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
-            % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
+        say("  %-*s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
+            % (width, c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
 
 
 TRAIN_MARK = "# --train"
@@ -144,36 +157,6 @@ def min_bytes_half_train(h, w):
     routing = 2208 * p1 + 1120 * p2 + 320 * p4          # the head, the nine input gradients, the four gathers, grad_x
     wgrad = 816 * p1 + 656 * p2 + 256 * p4             # G and the layer's input, once per layer
     return routing, routing + wgrad
-
-
-def train_resource_report(say, unit="hgtrain", prefix="hgb_"):
-    src = os.path.join(_build.CSRC, unit + ".hip")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([_build._hipcc()] + _build.compile_flags(unit) + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "hgb.o")],
-                           capture_output=True, text=True)
-    if r.returncode != 0:
-        say("hipcc's resource report could not be produced (exit %d)" % r.returncode)
-        return
-    rows, cur = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(?:Function Name: (\S+)|\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            k = re.search(r"(%s[a-z0-9_]+?)(?:I|E)" % prefix, name)
-            t = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)(?:EL[ib]([0-9]+))?E", name)
-            cur = {"name": (k.group(1) if k else name) + ("<%s>" % ", ".join(v for v in t.groups() if v is not None) if t else "")}
-            rows.append(cur)
-        elif cur is not None:
-            cur[m.group(2).strip()] = int(m.group(3))
-    if unit == "hgtrain":
-        say("hipcc's report per instantiation of hgtrain.hip (hgb_conv_kernel<channels of A, of B, Cout, taps, transposed>; hgb_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
-    else:
-        say("hipcc's report per instantiation of hghtrain.hip (hght_conv3_kernel<channels of A, of B, rows, epilogue: 0 float32, 1 masked binary16, 2 grad_x, 3 head>; hght_wgrad_kernel<channels of A, of B, Cout, read mode of A, taps>):")
-    for c in rows:
-        say("  %-44s VGPRs %3d  AGPRs %3d  spilled VGPRs %d  SGPRs %d  scratch %d B/lane  LDS %5d B  occupancy %d waves/SIMD"
-            % (c["name"], c.get("VGPRs", -1), c.get("AGPRs", -1), c.get("VGPRs Spill", -1), c.get("SGPRs Spill", -1), c.get("ScratchSize", -1), c.get("LDS Size", -1), c.get("Occupancy", -1)))
 
 
 def main_train(args):
@@ -319,8 +302,8 @@ def main_train(args):
     say("hourglass_train + backward faster than the torch float32 composition + autograd: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
     say("precision=\"float16\" faster than the float32 unit: %s" % ", ".join("%s %s" % kv for kv in verdict16.items()))
     say()
-    train_resource_report(say)
-    train_resource_report(say, "hghtrain", "hght_")
+    resource_report(say, "hgtrain")
+    resource_report(say, "hghtrain")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     kept = []
     if os.path.exists(args.out):
@@ -438,8 +421,8 @@ def main():
     say("the hip hourglass faster than the torch float32 composition: %s" % ", ".join("%s %s" % kv for kv in verdict.items()))
     say("hip float16 faster than both the float32 kernel and torch autocast by more than 5 %%: %s" % ", ".join("%s %s" % kv for kv in verdict16.items()))
     say()
-    resource_report(say)
-    resource_report(say, "hghalf", "hgh_conv3_kernel")
+    resource_report(say, "hourglass")
+    resource_report(say, "hghalf")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     head, rest = [], []
     if args.append and os.path.exists(args.out):          # after the forward reports the file holds, in front of the training report
